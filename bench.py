@@ -6,10 +6,11 @@ reference Optimizer.cpp:291) over one device-resident synthetic graph of the BAS
 configs[3] shape (10k cams / 2k ellipsoids / ~200k bbox edges, SURVEY.md §8 d), restarted from the
 same initial estimate every step (device-side state restore, no PCIe in the timed region).
 Default = configs[3] AS NAMED: SLAM mode (free cameras, camera 0 fixed, odometry edges: the reference's bSLAM_mode
-branch) with the Schur solve; `--mode mapping` times the reference's shipped setting (all cameras fixed), which the
-default line carries as the `mapping` record.
+branch) with the Schur solve; `--mode mapping` times the reference's shipped setting (all cameras fixed), which a
+`--full` run of the default mode carries as the `mapping` record.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--mode slam|mapping] [--config C4|C3] [--solver auto|camera|ellipsoid]
+                  [--full] [--dump-outputs DIR]
 
 N > 1 is launched by the driver through torch.distributed.run, one rank per GPU (RCCL).  The path
 shards by ellipsoid (SURVEY.md §8 e): the ellipsoids of the ONE named graph are partitioned over the ranks
@@ -17,10 +18,18 @@ shards by ellipsoid (SURVEY.md §8 e): the ellipsoids of the ONE named graph are
 trial, in SLAM mode additionally the all-reduce of the camera blocks and of the reduced camera system.
 value = LM iterations of that one global optimisation / max-over-ranks wall time.
 
-The default single-GPU line also carries: `slam_reduced_camera` (the same C4 steps with the reduced CAMERA system of the
-north star, FP64-MFMA roofline of its Cholesky) when the timed steps ran the camera-first elimination, `mapping` (C4 with
-all cameras fixed: HBM roofline of the linearisation, repeat blocks, its own CPU baseline), `slam_c3`, `fit` (per-frame
-ellipsoid fit), `ground_plane`, `streaming_c5`, `cpu_baseline` and `host`.
+A plain run sets up, warms up, times the K steps and prints the line: the headline, the roofline of the timed steps' dominant
+kernel (HIP events of those same steps) and `host`.  `--full` adds everything else, each from runs of its own after the timed
+steps: `cpu_baseline`; with a single GPU in SLAM mode `slam_reduced_camera` (the same C4 steps with the reduced CAMERA system of
+the north star, FP64-MFMA roofline of its Cholesky) when the timed steps ran the camera-first elimination,
+`slam_numeric_jacobians`, `mapping` (C4 with all cameras fixed: HBM roofline of the linearisation, repeat blocks, its own CPU
+baseline), `slam_c3`, `fit` (per-frame ellipsoid fit), `ground_plane`, `streaming_c5`; in mapping mode the repeat blocks, the
+untimed every-kernel profile pass, `fit`, `ground_plane`, `streaming_c5`; with N ranks in SLAM mode `slam_ellipsoid_partition`.
+
+`--dump-outputs DIR` writes what the timed path hands its caller after the last timed step, as float64 .npy files: the
+optimised states (cameras.npy (F, 7), ellipsoids.npy (N, 10): esl_states_download) and the LM report's per-iteration
+trace_chi2.npy, trace_lambda.npy and trace_trials.npy.  Every step restarts from the same seeded graph, so the same arguments give
+the same inputs in every run.
 """
 import argparse
 import importlib
@@ -83,6 +92,20 @@ def host_info():
     except OSError:
         pass
     return {"cpu_model": model, "nproc": os.cpu_count(), "cores_usable": len(os.sched_getaffinity(0))}
+
+
+def timed_outputs(ctx, rep):
+    """What a caller of the timed path receives from its last step: the optimised states and the LM report's traces."""
+    cams, objs = ctx.download_states()
+    return {"cameras": cams, "ellipsoids": objs, "trace_chi2": rep["trace_chi2"], "trace_lambda": rep["trace_lambda"],
+            "trace_trials": rep["trace_trials"]}
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: one float64 .npy per array (C4: 0.7 MB in all)."""
+    os.makedirs(path, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 class pinned_to_one_core:
@@ -326,9 +349,10 @@ def slam_roofline(prof, n_c, n_o, solver, trials, stats=None, dt=None):
             "trial_frac": (fl["actual"] / (trial_ms * 1e-3) / 1e12 / FP64_MFMA_PEAK_TF) if trial_ms else None}
 
 
-def slam_run(pkg, ctx, g, c, o, solver, steps, warmup, jacobian=1, barrier=None):
+def slam_run(pkg, ctx, g, c, o, solver, steps, warmup, jacobian=1, barrier=None, outputs=None):
     """K timed optimize(10) steps in SLAM mode on the resident graph (states restored device-side every step); HIP-event classes on
-    (an event pair per kernel class and trial: nothing against the milliseconds of a trial)."""
+    (an event pair per kernel class and trial: nothing against the milliseconds of a trial).  outputs: a dict that receives the
+    last step's timed_outputs."""
     params = pkg.default_lm_params(jacobian_mode=jacobian, linear_solver=solver)
     for _ in range(warmup):
         ctx.restore_states(); ctx.optimize_resident(params)
@@ -345,6 +369,8 @@ def slam_run(pkg, ctx, g, c, o, solver, steps, warmup, jacobian=1, barrier=None)
     dt = time.perf_counter() - t0
     prof = ctx.profile_get()
     ctx.profile_enable(False)
+    if outputs is not None:
+        outputs.update(timed_outputs(ctx, rep))
     used = ctx.lm_solver_used()
     n_c, n_o = 6 * int((~g.cam_fixed.astype(bool)).sum()), 9 * g.n_objs
     return {"value": its / dt, "unit": "LM iterations/s", "ms_per_optimize": 1e3 * dt / steps, "steps": steps, "warmup": warmup,
@@ -472,9 +498,10 @@ def cpu_baseline_c4_slam(g, cpu, its, trials, gpu_flops_per_trial=None):
             "anchors": same["anchors"], "estimate_note": same["note"], "block_schur_extrapolation": block}
 
 
-def mapping_bench(pkg, ctx, config="C4", jacobian="analytic", steps=20, warmup=10, blocks=10, extra=True):
+def mapping_bench(pkg, ctx, config="C4", jacobian="analytic", steps=20, warmup=10, blocks=10, extra=True, outputs=None):
     """The shipped setting of the reference (bSLAM_mode = false: all cameras fixed, per-ellipsoid 9x9 systems): device-driven LM,
-    HBM roofline of the linearisation kernel from a sampled HIP-event pair (one launch of every fourth run)."""
+    HBM roofline of the linearisation kernel from a sampled HIP-event pair (one launch of every fourth run).  outputs: a dict that
+    receives the last timed step's timed_outputs."""
     g, c, o, _ = pkg.synth.make_config(config, seed=0, slam=False)
     params = pkg.default_lm_params(jacobian_mode=1 if jacobian == "analytic" else 0)
     ctx.upload_graph(g); ctx.upload_states(c, o); ctx.snapshot_states()
@@ -496,6 +523,8 @@ def mapping_bench(pkg, ctx, config="C4", jacobian="analytic", steps=20, warmup=1
     dt = time.perf_counter() - t0
     prof = ctx.profile_get()
     ctx.profile_enable(False)
+    if outputs is not None:
+        outputs.update(timed_outputs(ctx, rep))
     blk = []
     for _ in range(blocks):
         ctx.synchronize()
@@ -746,8 +775,13 @@ def main():
     ap.add_argument("--config", default="C4")
     ap.add_argument("--jacobian", default="analytic", choices=["analytic", "numeric"])
     ap.add_argument("--solver", default="auto", choices=["auto", "camera", "ellipsoid"], help="esl_linear_solver of the SLAM-mode steps")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed region (no mapping / fit / streaming / C3 / reduced-camera records)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines and the records of other eliminations, Jacobians, modes, configs and workloads, each from runs "
+                         "of its own after the timed steps (off: only the timed steps and their line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (states, LM traces) to DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no mapping / fit / streaming / C3 / reduced-camera records")
     ap.add_argument("--extras", default=os.path.join(ROOT, "bench_extras.json"),
                     help="side file for everything that is not the driver's line (the full record: secondary kernels, other configs, anchors)")
     a = ap.parse_args()
@@ -790,7 +824,9 @@ def main():
     # odometry) replicated -> strong scaling of one global LM in both modes
     sharded = world > 1 or force_dist
     ctx = pkg.Context(local_rank)
-    with_cpu = not a.no_cpu_baseline
+    with_cpu = a.full and not a.no_cpu_baseline
+    with_extras = a.full and not a.no_extras
+    outputs = {} if a.dump_outputs else None
     out = None
 
     def barrier():
@@ -803,7 +839,8 @@ def main():
         # ---- the headline: BASELINE.json configs[3] as named -- 10k cams / 2k ellipsoids / ~200k edges, free cameras, Schur solve
         g, c, o, _ = pkg.synth.make_config(a.config, seed=0, slam=True)
         ctx.upload_graph(g); ctx.upload_states(c, o); ctx.snapshot_states()
-        r = slam_run(pkg, ctx, g, c, o, solver, a.steps, a.warmup, jacobian=1 if a.jacobian == "analytic" else 0, barrier=barrier)
+        r = slam_run(pkg, ctx, g, c, o, solver, a.steps, a.warmup, jacobian=1 if a.jacobian == "analytic" else 0, barrier=barrier,
+                     outputs=outputs)
         out = {
             "metric": "LM iterations/sec (cams+ellipsoids)", "value": r["value"], "unit": "LM iterations/s",
             "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * r["_dt"] / a.steps,
@@ -813,7 +850,7 @@ def main():
                        "unknowns": r["unknowns"], "parallelism": "single GPU"},
             "kernel_ms": r["kernel_ms"], "chi2": r["chi2"], "roofline": r["roofline"], "host": host_info(),
         }
-        if not a.no_extras:
+        if with_extras:
             if r["linear_solver"] == 2:   # the elimination the north star names, beside the one that was timed: 2 steps after 1 warm-up
                 rc_ = slam_run(pkg, ctx, g, c, o, 1, steps=2, warmup=1, jacobian=1 if a.jacobian == "analytic" else 0)
                 out["slam_reduced_camera"] = {k: v for k, v in rc_.items() if not k.startswith("_")}
@@ -848,7 +885,8 @@ def main():
                                        "(that is roofline.frac / roofline.trial_frac)")
     elif not sharded:
         # ---- mapping mode as the timed region (--mode mapping): the reference as shipped
-        m, (g, c, o) = mapping_bench(pkg, ctx, a.config, a.jacobian, steps=a.steps, warmup=a.warmup)
+        m, (g, c, o) = mapping_bench(pkg, ctx, a.config, a.jacobian, steps=a.steps, warmup=a.warmup, blocks=10 if a.full else 0, extra=a.full,
+                                     outputs=outputs)
         out = {"metric": "LM iterations/sec (cams+ellipsoids)", "value": m["value"], "unit": "LM iterations/s", "n_gpus": 1, "steps": a.steps,
                "warmup": a.warmup, "ms_per_step": m["ms_per_step"], "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
                "data": "synthetic", "config": {"workload": m["workload"], "lm_iterations_per_step": m["lm_iterations_per_step"],
@@ -856,7 +894,7 @@ def main():
                "kernel_ms": m["kernel_ms"], "chi2": m["chi2"], "roofline": m["roofline"], "host": host_info()}
         if "repeat_blocks" in m:
             out["repeat_blocks"] = m["repeat_blocks"]
-        if not a.no_extras:
+        if with_extras:
             out["fit"] = fit_bench(pkg, ctx, with_cpu=with_cpu)
             out["ground_plane"] = ground_plane_bench(pkg, ctx, with_cpu=with_cpu)
             out["streaming_c5"] = streaming_bench(pkg, ctx)
@@ -873,9 +911,10 @@ def main():
         first_replicated = slam and os.environ.get("ESL_BENCH_SHARDED_SLAM") != "1"
         params = pkg.default_lm_params(jacobian_mode=1 if a.jacobian == "analytic" else 0, linear_solver=solver)
 
-        def ranked_run(replicated, steps, warmup):
+        def ranked_run(replicated, steps, warmup, outputs=None):
             """one N-rank run of the named graph: communicator (mode first, then the graph: esl.h ABI 4), warm-up, timed steps bracketed by
-            barrier + synchronize, max over ranks; returns the JSON record on rank 0 (None elsewhere)"""
+            barrier + synchronize, max over ranks; returns the JSON record on rank 0 (None elsewhere).  outputs: a dict that receives the
+            last step's timed_outputs (the ellipsoids gathered from their ranks)"""
             mine = np.arange(g_full.n_objs) if replicated else np.nonzero(pkg.lib.partition_objects(g_full, world) == rank)[0]
             g, o = g_full.subset_objects(mine), o_full[mine]
             runner = None
@@ -929,6 +968,14 @@ def main():
             t = torch.tensor([dt], dtype=torch.float64, device="cpu" if host_transport else f"cuda:{local_rank}")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
+            if outputs is not None:
+                outputs.update(timed_outputs(ctx, rep))
+                if not replicated:   # every rank holds its own ellipsoids: back into the graph's order
+                    parts = [None] * world
+                    dist.all_gather_object(parts, (mine, outputs["ellipsoids"]))
+                    outputs["ellipsoids"] = np.zeros((g_full.n_objs, 10))
+                    for idx, part in parts:
+                        outputs["ellipsoids"][idx] = part
             if rank != 0:
                 return None
             if slam:
@@ -967,8 +1014,8 @@ def main():
                     "kernel_ms": prof, "chi2": {"initial": rep["chi2_initial"], "final": rep["chi2_final"], "trace": rep["trace_chi2"], "trials": rep["trace_trials"]},
                     "roofline": roof, "host": host_info()}
 
-        out = ranked_run(first_replicated, a.steps, a.warmup)
-        if slam and first_replicated and os.environ.get("ESL_BENCH_ONE_LINE") != "1" and not a.no_extras:
+        out = ranked_run(first_replicated, a.steps, a.warmup, outputs)
+        if slam and first_replicated and os.environ.get("ESL_BENCH_ONE_LINE") != "1" and with_extras:
             # the design BASELINE.json's north_star NAMES, beside the one that was timed: the ellipsoids partitioned over
             # the ranks, camera blocks all-reduced, every rank's partial reduced CAMERA system summed panel by panel to its owner, the
             # factorisation distributed.  16x the flops of the camera-first form at this shape: 1 step after 1 warm-up.
@@ -980,6 +1027,8 @@ def main():
             except Exception as e:  # noqa: BLE001  (the timed line above must survive a failure of the extra record)
                 if rank == 0:
                     out["slam_ellipsoid_partition"] = {"error": str(e)}
+    if rank == 0 and outputs is not None:
+        dump_outputs(a.dump_outputs, outputs)
     final_line = None
     if rank == 0 and out is not None:
         final_line = json.dumps(driver_line(out, os.path.relpath(a.extras, ROOT) if os.path.abspath(a.extras).startswith(ROOT) else a.extras))

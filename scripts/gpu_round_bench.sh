@@ -11,8 +11,8 @@ ROOT=$(pwd)
 timeout 900 python -m pytest tests -m gpu -q -s --durations=15 > $R/gputest.log 2>&1; echo rc=$? >> $R/gputest.log
 # the DRIVER's command (BENCH_rNN.json: `python3 bench.py --gpus 1 --steps 20 --warmup 5`), and rocprofv3 kernel stats of the same command
 # (round 6: stdout is the driver's line alone, < 4 KB; the full record -- what these scripts summarise -- is the --extras side file)
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --extras $R/bench_default.json > $R/bench_default_line.json 2> $R/bench_default.err; echo rc=$? >> $R/bench_default.err
-(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $ROOT/$R/prof_bench -- python $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --extras $ROOT/$R/prof_bench_extras.json > $ROOT/$R/prof_bench.json 2> $ROOT/$R/prof_bench.log)
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full --extras $R/bench_default.json > $R/bench_default_line.json 2> $R/bench_default.err; echo rc=$? >> $R/bench_default.err
+(cd "$TMPDIR" && timeout 900 rocprofv3 --kernel-trace --stats -d $ROOT/$R/prof_bench -- python $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --full --extras $ROOT/$R/prof_bench_extras.json > $ROOT/$R/prof_bench.json 2> $ROOT/$R/prof_bench.log)
 python profiles/summarize_rocpd.py $(ls -t $R/prof_bench/*/*_results.db | head -1) > $R/bench_default_kernel_stats.md
 rm -rf $R/prof_bench
 # HBM traffic of ONE C4 SLAM optimize (5 trials, camera-first elimination): two separate --pmc passes, kernel trace only

@@ -81,12 +81,12 @@ def test_two_processes_on_one_gpu_take_the_single_gpu_run(single, mode, env, tol
 
 
 def test_two_rank_default_line_carries_both_slam_designs(single):
-    """`bench.py --gpus N` as the driver launches it (no --no-extras) reports the timed replicated-graph run AND, as the record
+    """`bench.py --gpus N --full` (no --no-extras) reports the timed replicated-graph run AND, as the record
     `slam_ellipsoid_partition`, the design BASELINE.json's north_star names: ellipsoids partitioned over the ranks, camera blocks
     all-reduced, the partial reduced camera systems summed to the panels' owners.  Both must take the
     single-GPU LM run."""
     port = 29600 + (os.getpid() % 300) + 71
-    multi = run_bench(["--mode", "slam"], 2, {"ESL_CHOL_DIST": "1"}, port, common=["--steps", "1", "--warmup", "0", "--config", "C3", "--no-cpu-baseline"])
+    multi = run_bench(["--mode", "slam"], 2, {"ESL_CHOL_DIST": "1"}, port, common=["--steps", "1", "--warmup", "0", "--config", "C3", "--full", "--no-cpu-baseline"])
     ref = single["slam"]
     assert "replicated graph" in multi["config"]["parallelism"]
     sec = multi["slam_ellipsoid_partition"]
@@ -96,3 +96,22 @@ def test_two_rank_default_line_carries_both_slam_designs(single):
         assert rec["chi2"]["trials"] == ref["chi2"]["trials"]
         np.testing.assert_allclose(rec["chi2"]["trace"], ref["chi2"]["trace"], rtol=tol)
     print("both designs in one line: replicated %.1f it/s, ellipsoid partition %.1f it/s (host transport: not timings)" % (multi["value"], sec["value"]))
+
+
+def test_dump_outputs_hold_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR`: the states and LM traces of the last timed step as float64 .npy files -- the chi2 trace of the record,
+    and with two ellipsoid-sharded ranks the ellipsoids gathered back into the graph's order (the one-GPU run's states)."""
+    port = 29600 + (os.getpid() % 300) + 97
+    recs, dumps = {}, {}
+    for n in (1, 2):
+        d = str(tmp_path / f"outputs_{n}")
+        recs[n] = run_bench(["--mode", "mapping", "--dump-outputs", d], n, {}, port)
+        dumps[n] = {f[:-len(".npy")]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+        assert set(dumps[n]) == {"cameras", "ellipsoids", "trace_chi2", "trace_lambda", "trace_trials"}
+        assert all(v.dtype == np.float64 for v in dumps[n].values())
+        assert sum(v.nbytes for v in dumps[n].values()) < 64 << 20
+        np.testing.assert_array_equal(dumps[n]["trace_chi2"], recs[n]["chi2"]["trace"])
+        np.testing.assert_array_equal(dumps[n]["trace_trials"], recs[n]["chi2"]["trials"])
+    assert dumps[1]["cameras"].shape == (500, 7) and dumps[1]["ellipsoids"].shape == (50, 10)
+    np.testing.assert_array_equal(dumps[2]["cameras"], dumps[1]["cameras"])
+    np.testing.assert_allclose(dumps[2]["ellipsoids"], dumps[1]["ellipsoids"], rtol=0, atol=1e-9)
