@@ -9,6 +9,8 @@
 //
 // What it mirrors (reference src/core/Optimizer.cpp):
 //   :88-90   config keys Optimizer.Edges.3DEllipsoid.Scale / GravityPrior.Open / GravityPrior.Scale
+//   :224     e->setRobustKernel (commented out there): config keys Optimizer.Edges.2D / 3DEllipsoid .RobustKernel / .RobustDelta
+//            -> esl_lm_set_robust (absent keys: no kernel); the summary adds the bbox edges the kernel down-weighted
 //   :126     bSLAM_mode -- a constant `false` in the reference; here the config key Optimizer.SLAMMode (absent from the
 //            shipped yaml => 0 => the shipped mapping mode), esl_adapter::Options::slam_mode in the template below
 //   :127-139 one camera vertex per frame (Tcw), all fixed in mapping mode; SLAM mode: only frame 0 fixed (:137)
@@ -175,14 +177,37 @@ void Optimizer::GlobalObjectGraphOptimization(std::vector<Frame*>& pFrames, Map*
     for (int k = 0; k < 4; ++k) ground[k] = mGroundPlaneNormal[k];
   esl_graph g = esl_adapter::MakeGraph(f, K, mbGroundPlaneSet ? ground : nullptr, grav_scale, opt);
   esl_lm_params p; esl_lm_params_default(&p);
+  // e->setRobustKernel (commented out at Optimizer.cpp:224): kind (esl_robust_kind, 0 = none) and delta per edge class; a missing key
+  // reads 0 (cv::FileStorage), so the shipped yaml keeps the plain least squares; delta <= 0 is g2o's default 1 (robust_kernel.cpp:32)
+  esl_robust_params rp;
+  for (int k = 0; k < ESL_EDGE_CLASSES; ++k) { rp.kind[k] = ESL_ROBUST_NONE; rp.delta[k] = 1.0; }
+  auto robust_key = [&](const char* cls, int edge_class) {
+    rp.kind[edge_class] = Config::Get<int>(std::string("Optimizer.Edges.") + cls + ".RobustKernel");
+    const double d = Config::Get<double>(std::string("Optimizer.Edges.") + cls + ".RobustDelta");
+    rp.delta[edge_class] = d > 0 ? d : 1.0;
+  };
+  robust_key("2D", ESL_EDGE_BBOX);
+  robust_key("3DEllipsoid", ESL_EDGE_E3D);
   esl_lm_report rep;
+  int n_down = -1;   // bbox edges with weight < 1 after the optimisation (only counted with a 2D kernel set)
   {
     std::lock_guard<std::mutex> lock(esl_adapter::CtxMutex());
     esl_ctx* ctx = esl_adapter::SharedCtx();
     if (!ctx) return;
+    if (esl_lm_set_robust(ctx, &rp) != ESL_OK) {
+      std::cerr << "esl_lm_set_robust: " << esl_last_error() << std::endl;
+      return;
+    }
     if (esl_optimize(ctx, &g, f.cams.data(), f.objs.data(), &p, &rep) != ESL_OK) {
       std::cerr << "esl_optimize: " << esl_last_error() << std::endl;  // the reference never throws here
       return;
+    }
+    if (rp.kind[ESL_EDGE_BBOX] != ESL_ROBUST_NONE && g.n_bbox > 0) {
+      std::vector<double> w((size_t)g.n_bbox);
+      if (esl_edge_chi2(ctx, ESL_EDGE_BBOX, nullptr, w.data(), g.n_bbox) == ESL_OK) {
+        n_down = 0;
+        for (double x : w) n_down += x < 1.0 ? 1 : 0;
+      }
     }
   }
   // graph summary the reference prints before optimising (Optimizer.cpp:281-288)
@@ -191,7 +216,9 @@ void Optimizer::GlobalObjectGraphOptimization(std::vector<Frame*>& pFrames, Map*
   std::cout << " * Vertices: " << g.n_cams + g.n_objs << std::endl;
   std::cout << " * 2d Edges [Valid/Invalid] : " << g.n_bbox << " [" << rep.n_bbox_valid << "/" << rep.n_bbox_dropped << "]" << std::endl;
   std::cout << " * 3d Edges : " << g.n_e3d << std::endl;
-  std::cout << " * Gravity edges: " << g.n_grav << std::endl << std::endl;
+  std::cout << " * Gravity edges: " << g.n_grav << std::endl;
+  if (n_down >= 0) std::cout << " * 2d Edges down-weighted by the robust kernel (weight < 1) : " << n_down << std::endl;
+  std::cout << std::endl;
   for (size_t o = 0; o < f.instance_of_obj.size(); ++o) {      // Optimizer.cpp:294-306: in-place write-back
     g2o::ellipsoid* e = ells[f.instance_of_obj[o]];
     Vector10d v; for (int k = 0; k < 10; ++k) v[k] = f.objs[o * 10 + k];

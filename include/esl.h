@@ -45,7 +45,9 @@ extern "C" {
                              * 4: ESL_PROF_KINDS 10 (class 9: the dense factorisation alone), esl_ctx_trim, esl_comm_set_replicated refuses a
                              *    mode change under a resident graph, esl_graph_append accepts SLAM-mode graphs (free cameras + odometry)
                              * 5: esl_lm_params::e3d_half_turn (1 = the yaw-hypothesis minimum exactly as Ellipsoid.cpp:92-117 writes it),
-                             *    esl_plane_params::max_curvature (PCL's maximum_curvature_ model test; min_inliers is a strict >) */
+                             *    esl_plane_params::max_curvature (PCL's maximum_curvature_ model test; min_inliers is a strict >);
+                             *    additive part of 5: robust kernels per edge class (esl_robust_params, esl_lm_set_robust, esl_edge_chi2) --
+                             *    detect them by the symbol */
 #define ESL_MAX_TRACE 32
 
 typedef enum {
@@ -190,6 +192,29 @@ int esl_ctx_synchronize(esl_ctx* ctx);
  * trial step needs is built again.  Uploading a graph WITHOUT free cameras over a SLAM-mode one trims by itself. */
 int esl_ctx_trim(esl_ctx* ctx);
 void esl_lm_params_default(esl_lm_params* p);
+
+/* ---- robust kernels (g2o core/robust_kernel_impl.cpp; Optimizer.cpp:224 e->setRobustKernel) ---------------------------
+ * Per edge CLASS: an edge with raw chi2 e = r^T Omega r contributes rho1(e) J^T Omega J to H, -rho1(e) J^T Omega r to b
+ * (g2o's robustInformation; the rho2 term is left out, as in g2o) and rho0(e) to the chi2 the LM uses everywhere (initial,
+ * trial, rho ratio, stop rule, trace, report); lambda_0 = tau * max diag of the weighted H.  Kernels, with e <= delta^2 the
+ * inlier test: Huber, PseudoHuber, Cauchy, Tukey exactly as g2o writes them.  The bbox class includes the plane-tangency
+ * residual; the gravity prior stays merged per ellipsoid (count * rho(grav_weight r^2)).  The NaN pre-check and the
+ * visibility test keep deciding on the RAW chi2 (Optimizer.cpp:234-243). */
+typedef enum { ESL_ROBUST_NONE = 0, ESL_ROBUST_HUBER = 1, ESL_ROBUST_PSEUDO_HUBER = 2, ESL_ROBUST_CAUCHY = 3, ESL_ROBUST_TUKEY = 4 } esl_robust_kind;
+typedef enum { ESL_EDGE_BBOX = 0, ESL_EDGE_E3D = 1, ESL_EDGE_GRAVITY = 2, ESL_EDGE_ODOM = 3, ESL_EDGE_CLASSES = 4 } esl_edge_class;
+typedef struct {
+  int32_t kind[ESL_EDGE_CLASSES];    /* esl_robust_kind per esl_edge_class */
+  double delta[ESL_EDGE_CLASSES];    /* kernel width; must be finite and > 0 where kind != ESL_ROBUST_NONE */
+} esl_robust_params;                 /* 48 bytes */
+/* The setting belongs to the context: it survives esl_graph_upload, esl_graph_append and esl_ctx_trim, and every run reads it at
+ * its start (esl_optimize, esl_optimize_resident, esl_lm_begin).  p = NULL: every class ESL_ROBUST_NONE (the default).
+ * ESL_ERR_INVALID for a kind out of range or a bad delta.  Sharded runs: every rank must set the same values. */
+int esl_lm_set_robust(esl_ctx* ctx, const esl_robust_params* p);
+/* Every edge of one class at the states the context holds (e.g. after an optimize call): chi2[i] = raw chi2 e, weight[i] = rho1(e)
+ * as the solver applies it, in CALLER order (upload order, then append order).  Bbox edges dropped by the NaN pre-check or the
+ * visibility test report weight 0; a class without a kernel reports weight 1.  Gravity edges report the value of their
+ * ellipsoid's prior.  count must equal the class's edge count (ESL_ERR_INVALID otherwise); either array may be NULL. */
+int esl_edge_chi2(esl_ctx* ctx, int32_t edge_class, double* chi2, double* weight, int64_t count);
 
 /* ---- one-shot optimiser (host buffers in, host buffers out) ------------------------------------*/
 int esl_optimize(esl_ctx* ctx, const esl_graph* g, double* cams_io /* n_cams x 7 */,

@@ -6,7 +6,7 @@ The directory name carries a hyphen, so import it with
     importlib.import_module("object-oriented-slam_amd")
 """
 from . import abi, lib, synth  # noqa: F401
-from .abi import Graph, default_lm_params  # noqa: F401
+from .abi import Graph, default_lm_params, default_robust_params  # noqa: F401
 from .lib import Context, EslError  # noqa: F401
 
-__all__ = ["abi", "lib", "synth", "Graph", "default_lm_params", "Context", "EslError"]
+__all__ = ["abi", "lib", "synth", "Graph", "default_lm_params", "default_robust_params", "Context", "EslError"]

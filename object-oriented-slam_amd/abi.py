@@ -113,6 +113,31 @@ def default_plane_params(**kw):
 
 SOLVER_AUTO, SOLVER_REDUCED_CAMERA, SOLVER_REDUCED_ELLIPSOID = 0, 1, 2   # esl_linear_solver (include/esl.h)
 
+ROBUST_KINDS = {"none": 0, "huber": 1, "pseudo_huber": 2, "cauchy": 3, "tukey": 4}   # esl_robust_kind (include/esl.h)
+EDGE_CLASSES = {"bbox": 0, "e3d": 1, "grav": 2, "odom": 3}                         # esl_edge_class
+
+
+class EslRobustParams(C.Structure):
+    """esl_robust_params: g2o robust kernel (kind, delta) per edge class (esl_lm_set_robust)."""
+    _fields_ = [("kind", C.c_int32 * 4), ("delta", C.c_double * 4)]
+
+
+def default_robust_params(**kw):
+    """Every class without a kernel (the default).  Keywords bbox / e3d / grav / odom = (kind name, delta), e.g. ("huber", 1.0)."""
+    p = EslRobustParams()
+    for k in range(4):
+        p.kind[k], p.delta[k] = 0, 1.0
+    for cls, v in kw.items():
+        if cls not in EDGE_CLASSES:
+            raise ValueError(f"unknown edge class {cls!r}: one of {sorted(EDGE_CLASSES)}")
+        if v is None:
+            continue
+        kind, delta = v
+        if kind not in ROBUST_KINDS:
+            raise ValueError(f"unknown robust kernel {kind!r}: one of {sorted(ROBUST_KINDS)}")
+        p.kind[EDGE_CLASSES[cls]], p.delta[EDGE_CLASSES[cls]] = ROBUST_KINDS[kind], float(delta)
+    return p
+
 
 def default_lm_params(**kw):
     """Reference settings: optimize(10) (Optimizer.cpp:291), tau 1e-5, 10 trials

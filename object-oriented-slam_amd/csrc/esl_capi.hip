@@ -274,6 +274,7 @@ int esl_ctx_destroy(esl_ctx* c) {
   if (c->stage_host) (void)hipHostFree(c->stage_host);
   if (c->append_dev) (void)hipFree(c->append_dev);
   if (c->slam_tab_dev) (void)hipFree(c->slam_tab_dev);
+  if (c->eq_buf) (void)hipFree(c->eq_buf);
   fit_release(c);
   plane_release(c);
   for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
@@ -454,6 +455,9 @@ int esl_graph_upload(esl_ctx* c, const esl_graph* g) {
     if ((rc = up.flush())) return rc;
     c->h_bb_cam.assign(b_cam, b_cam + nb); c->h_bb_obj.assign(b_obj, b_obj + nb);
     c->h_e3_cam.assign(e_cam, e_cam + ne); c->h_e3_obj.assign(e_obj, e_obj + ne);
+    c->h_bb_slot_of.resize(nb); c->h_e3_slot_of.resize(ne);   // caller order -> slot (esl_edge_chi2)
+    for (size_t k = 0; k < nb; ++k) c->h_bb_slot_of[perm[k]] = (int)k;
+    for (size_t k = 0; k < ne; ++k) c->h_e3_slot_of[perm3[k]] = (int)k;
     // camera-side CSRs over the SORTED edges
     int* cs = up.alloc(&d.cbb_start, (size_t)F + 1);
     int* cp = up.alloc(&d.cbb_edge, nb);
@@ -468,6 +472,7 @@ int esl_graph_upload(esl_ctx* c, const esl_graph* g) {
   {
     std::vector<int> cnt((size_t)N, 0);
     for (int i = 0; i < g->n_grav; ++i) cnt[g->grav_obj[i]]++;
+    c->h_grav_obj.assign(g->grav_obj, g->grav_obj + g->n_grav);
     c->n_grav_edges = g->n_grav;
     for (int o = 0; o < N; ++o)
       if (cnt[o] > 64) { set_error("more than 64 gravity edges on one ellipsoid"); return ESL_ERR_INVALID; }
@@ -908,6 +913,7 @@ int esl_graph_append(esl_ctx* c, const esl_graph_delta* dl) {
       const int o = dl->bbox_obj[i];
       const size_t s = (size_t)I.bb_begin[o] + I.bb_cnt[o]++;
       I.bb_cam[s] = dl->bbox_cam[i]; I.bb_obj[s] = o; I.bb_w[s] = dl->bbox_weight[i];
+      c->h_bb_slot_of.push_back((int)s);
       for (int q = 0; q < 4; ++q) I.bb_meas[s * 4 + q] = dl->bbox_meas[(size_t)i * 4 + q];
       if (record) {
         AppendBb r{(int)s, dl->bbox_cam[i], o, 0, {0, 0, 0, 0}, dl->bbox_weight[i]};
@@ -919,6 +925,7 @@ int esl_graph_append(esl_ctx* c, const esl_graph_delta* dl) {
       const int o = dl->e3d_obj[i];
       const size_t s = (size_t)I.e3_begin[o] + I.e3_cnt[o]++;
       I.e3_cam[s] = dl->e3d_cam[i]; I.e3_obj[s] = o; I.e3_w[s] = dl->e3d_weight[i];
+      c->h_e3_slot_of.push_back((int)s);
       for (int q = 0; q < 10; ++q) I.e3_meas[s * 10 + q] = dl->e3d_meas[(size_t)i * 10 + q];
       if (record) {
         AppendE3 r{(int)s, dl->e3d_cam[i], o, 0, {0}, dl->e3d_weight[i]};
@@ -928,6 +935,7 @@ int esl_graph_append(esl_ctx* c, const esl_graph_delta* dl) {
     }
     for (int o = 0; o < N; ++o) I.gr_cnt[o] += add_gr[o];
     I.n_grav += dl->n_grav;
+    c->h_grav_obj.insert(c->h_grav_obj.end(), dl->grav_obj, dl->grav_obj + dl->n_grav);
   };
   if (!fits) {
     // full re-layout with doubled slack: the states that live on the device come back first
@@ -939,6 +947,9 @@ int esl_graph_append(esl_ctx* c, const esl_graph_delta* dl) {
     for (size_t k = 0; k < (size_t)dl->n_new_objs * 10; ++k) objs[(size_t)im.n_objs * 10 + k] = dl->new_objs[k];
     HostImage* ni = new HostImage();
     image_relayout(im, *ni, add_bb, add_e3, F, N);
+    // the caller's edges move with their ellipsoid's slice (same position inside it)
+    for (int& sl : c->h_bb_slot_of) { const int o = im.bb_obj[sl]; sl = ni->bb_begin[o] + (sl - im.bb_begin[o]); }
+    for (int& sl : c->h_e3_slot_of) { const int o = im.e3_obj[sl]; sl = ni->e3_begin[o] + (sl - im.e3_begin[o]); }
     place(*ni, false);
     add_cameras_and_odometry(*ni);
     c->append_img = nullptr;   // free_graph (inside image_upload) must not drop the image under construction
@@ -1058,60 +1069,65 @@ static int map_launch_linearize(esl_ctx* c, bool finalize, const double* src_obj
   const bool an = c->lm.p.jacobian_mode == ESL_JAC_ANALYTIC;
   const int nb_e3 = (c->n_ids_e3 + 2 * kLinWaves - 1) / (2 * kLinWaves);   // two 32-edge chunks per wave
   const int nb_bb = (c->n_ids_bb + kLinWaves - 1) / kLinWaves;
-  if (ct.n_chunks > 0) {
-    ProfScope ps(c, 0);
-    const dim3 block(64 * kLinWaves);
-    int* cnt = c->chol_info + 2;
-    if (an && g.bbox_mode) {   // plane-tangency rows instead of the reprojection residual (never NaN: nothing to validate, but the
-                               // flags are (re)set to valid by the VALIDATE instantiation)
-      if (validate && g.check_vis)
-        hipLaunchKernelGGL((k_chunk_linearize_both<ESL_JAC_ANALYTIC, 2, true>), dim3(nb_e3 + nb_bb), block, 0, c->stream, g, ct, c->ck_ids_e3,
-                           c->n_ids_e3, nb_e3, c->ck_ids_bb, c->n_ids_bb, c->cams, src_objs, objs_b, c->lm.p.numeric_delta, dst_chunk,
-                           chunk_b, c->blk_chi, st, cnt);
-      else if (validate)
-        hipLaunchKernelGGL((k_chunk_linearize_both<ESL_JAC_ANALYTIC, 1, true>), dim3(nb_e3 + nb_bb), block, 0, c->stream, g, ct, c->ck_ids_e3,
-                           c->n_ids_e3, nb_e3, c->ck_ids_bb, c->n_ids_bb, c->cams, src_objs, objs_b, c->lm.p.numeric_delta, dst_chunk,
-                           chunk_b, c->blk_chi, st, cnt);
-      else
-        hipLaunchKernelGGL((k_chunk_linearize_both<ESL_JAC_ANALYTIC, 0, true>), dim3(nb_e3 + nb_bb), block, 0, c->stream, g, ct, c->ck_ids_e3,
-                           c->n_ids_e3, nb_e3, c->ck_ids_bb, c->n_ids_bb, c->cams, src_objs, objs_b, c->lm.p.numeric_delta, dst_chunk,
-                           chunk_b, c->blk_chi, st, cnt);
-    } else if (an) {   // both edge types in one launch, 3-D workgroups first
-      if (validate && g.check_vis)
-        hipLaunchKernelGGL((k_chunk_linearize_both<ESL_JAC_ANALYTIC, 2>), dim3(nb_e3 + nb_bb), block, 0, c->stream, g, ct, c->ck_ids_e3,
-                           c->n_ids_e3, nb_e3, c->ck_ids_bb, c->n_ids_bb, c->cams, src_objs, objs_b, c->lm.p.numeric_delta, dst_chunk,
-                           chunk_b, c->blk_chi, st, cnt);
-      else if (validate)
-        hipLaunchKernelGGL((k_chunk_linearize_both<ESL_JAC_ANALYTIC, 1>), dim3(nb_e3 + nb_bb), block, 0, c->stream, g, ct, c->ck_ids_e3,
-                           c->n_ids_e3, nb_e3, c->ck_ids_bb, c->n_ids_bb, c->cams, src_objs, objs_b, c->lm.p.numeric_delta, dst_chunk,
-                           chunk_b, c->blk_chi, st, cnt);
-      else
-        hipLaunchKernelGGL((k_chunk_linearize_both<ESL_JAC_ANALYTIC, 0>), dim3(nb_e3 + nb_bb), block, 0, c->stream, g, ct, c->ck_ids_e3,
-                           c->n_ids_e3, nb_e3, c->ck_ids_bb, c->n_ids_bb, c->cams, src_objs, objs_b, c->lm.p.numeric_delta, dst_chunk,
-                           chunk_b, c->blk_chi, st, cnt);
-    } else {    // numeric Jacobians: one kernel per edge type (very different register needs), the long tasks first
-      if (nb_e3 > 0)
-        hipLaunchKernelGGL((k_chunk_linearize<ESL_JAC_NUMERIC, 1, 0>), dim3(nb_e3), block, 0, c->stream, g, ct, c->ck_ids_e3,
-                           c->n_ids_e3, c->cams, src_objs, objs_b, c->lm.p.numeric_delta, dst_chunk, chunk_b, c->blk_chi, 0, st, cnt);
-      if (nb_bb > 0) {
-        auto launch_bb = [&](auto kern) {
-          hipLaunchKernelGGL(kern, dim3(nb_bb), block, 0, c->stream, g, ct, c->ck_ids_bb, c->n_ids_bb, c->cams, src_objs, objs_b,
-                             c->lm.p.numeric_delta, dst_chunk, chunk_b, c->blk_chi, nb_e3, st, cnt);
-        };
-        const int vmode = !validate ? 0 : (g.check_vis ? 2 : 1);
-        if (g.bbox_mode) { if (vmode == 2) launch_bb(k_chunk_linearize<ESL_JAC_NUMERIC, 0, 2, true>); else if (vmode == 1) launch_bb(k_chunk_linearize<ESL_JAC_NUMERIC, 0, 1, true>); else launch_bb(k_chunk_linearize<ESL_JAC_NUMERIC, 0, 0, true>); }
-        else { if (vmode == 2) launch_bb(k_chunk_linearize<ESL_JAC_NUMERIC, 0, 2, false>); else if (vmode == 1) launch_bb(k_chunk_linearize<ESL_JAC_NUMERIC, 0, 1, false>); else launch_bb(k_chunk_linearize<ESL_JAC_NUMERIC, 0, 0, false>); }
+  robust_dispatch(c->robust_on, [&](auto robust) {
+    constexpr bool R = decltype(robust)::value;
+    if (ct.n_chunks > 0) {
+      ProfScope ps(c, 0);
+      const dim3 block(64 * kLinWaves);
+      int* cnt = c->chol_info + 2;
+      if (an && g.bbox_mode) {   // plane-tangency rows instead of the reprojection residual (never NaN: nothing to validate, but the
+                                 // flags are (re)set to valid by the VALIDATE instantiation)
+        if (validate && g.check_vis)
+          hipLaunchKernelGGL((k_chunk_linearize_both<ESL_JAC_ANALYTIC, 2, true, R>), dim3(nb_e3 + nb_bb), block, 0, c->stream, g, ct, c->ck_ids_e3,
+                             c->n_ids_e3, nb_e3, c->ck_ids_bb, c->n_ids_bb, c->cams, src_objs, objs_b, c->lm.p.numeric_delta, dst_chunk,
+                             chunk_b, c->blk_chi, st, cnt);
+        else if (validate)
+          hipLaunchKernelGGL((k_chunk_linearize_both<ESL_JAC_ANALYTIC, 1, true, R>), dim3(nb_e3 + nb_bb), block, 0, c->stream, g, ct, c->ck_ids_e3,
+                             c->n_ids_e3, nb_e3, c->ck_ids_bb, c->n_ids_bb, c->cams, src_objs, objs_b, c->lm.p.numeric_delta, dst_chunk,
+                             chunk_b, c->blk_chi, st, cnt);
+        else
+          hipLaunchKernelGGL((k_chunk_linearize_both<ESL_JAC_ANALYTIC, 0, true, R>), dim3(nb_e3 + nb_bb), block, 0, c->stream, g, ct, c->ck_ids_e3,
+                             c->n_ids_e3, nb_e3, c->ck_ids_bb, c->n_ids_bb, c->cams, src_objs, objs_b, c->lm.p.numeric_delta, dst_chunk,
+                             chunk_b, c->blk_chi, st, cnt);
+      } else if (an) {   // both edge types in one launch, 3-D workgroups first
+        if (validate && g.check_vis)
+          hipLaunchKernelGGL((k_chunk_linearize_both<ESL_JAC_ANALYTIC, 2, false, R>), dim3(nb_e3 + nb_bb), block, 0, c->stream, g, ct, c->ck_ids_e3,
+                             c->n_ids_e3, nb_e3, c->ck_ids_bb, c->n_ids_bb, c->cams, src_objs, objs_b, c->lm.p.numeric_delta, dst_chunk,
+                             chunk_b, c->blk_chi, st, cnt);
+        else if (validate)
+          hipLaunchKernelGGL((k_chunk_linearize_both<ESL_JAC_ANALYTIC, 1, false, R>), dim3(nb_e3 + nb_bb), block, 0, c->stream, g, ct, c->ck_ids_e3,
+                             c->n_ids_e3, nb_e3, c->ck_ids_bb, c->n_ids_bb, c->cams, src_objs, objs_b, c->lm.p.numeric_delta, dst_chunk,
+                             chunk_b, c->blk_chi, st, cnt);
+        else
+          hipLaunchKernelGGL((k_chunk_linearize_both<ESL_JAC_ANALYTIC, 0, false, R>), dim3(nb_e3 + nb_bb), block, 0, c->stream, g, ct, c->ck_ids_e3,
+                             c->n_ids_e3, nb_e3, c->ck_ids_bb, c->n_ids_bb, c->cams, src_objs, objs_b, c->lm.p.numeric_delta, dst_chunk,
+                             chunk_b, c->blk_chi, st, cnt);
+      } else {    // numeric Jacobians: one kernel per edge type (very different register needs), the long tasks first
+        if (nb_e3 > 0)
+          hipLaunchKernelGGL((k_chunk_linearize<ESL_JAC_NUMERIC, 1, 0, false, R>), dim3(nb_e3), block, 0, c->stream, g, ct, c->ck_ids_e3,
+                             c->n_ids_e3, c->cams, src_objs, objs_b, c->lm.p.numeric_delta, dst_chunk, chunk_b, c->blk_chi, 0, st, cnt);
+        if (nb_bb > 0) {
+          auto launch_bb = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(nb_bb), block, 0, c->stream, g, ct, c->ck_ids_bb, c->n_ids_bb, c->cams, src_objs, objs_b,
+                               c->lm.p.numeric_delta, dst_chunk, chunk_b, c->blk_chi, nb_e3, st, cnt);
+          };
+          const int vmode = !validate ? 0 : (g.check_vis ? 2 : 1);
+          if (g.bbox_mode) { if (vmode == 2) launch_bb(k_chunk_linearize<ESL_JAC_NUMERIC, 0, 2, true, R>); else if (vmode == 1) launch_bb(k_chunk_linearize<ESL_JAC_NUMERIC, 0, 1, true, R>); else launch_bb(k_chunk_linearize<ESL_JAC_NUMERIC, 0, 0, true, R>); }
+          else { if (vmode == 2) launch_bb(k_chunk_linearize<ESL_JAC_NUMERIC, 0, 2, false, R>); else if (vmode == 1) launch_bb(k_chunk_linearize<ESL_JAC_NUMERIC, 0, 1, false, R>); else launch_bb(k_chunk_linearize<ESL_JAC_NUMERIC, 0, 0, false, R>); }
+        }
       }
     }
-  }
+  });
   ESL_HIP_TRY(hipGetLastError());
   c->sys_combined = false;
   if (finalize) {
     ProfScope ps(c, 4);
-    hipLaunchKernelGGL(k_chunk_finalize_rows, dim3(std::max(1, (g.n_objs + kStepWaves - 1) / kStepWaves)), dim3(64 * kStepWaves), 0, c->stream, g, ct, dst_chunk, src_objs,
-                       c->lm.p.jacobian_mode, c->lm.p.numeric_delta, c->blk_part,
-                       c->tickets, c->dev_scal, (LmScalars*)c->host_scal_dev, c->lm.p.tau, (LmCore*)nullptr, (int*)nullptr, 0,
-                       (LmHostView*)nullptr);
+    robust_dispatch(c->robust_on, [&](auto robust) {
+      hipLaunchKernelGGL(k_chunk_finalize_rows<decltype(robust)::value>, dim3(std::max(1, (g.n_objs + kStepWaves - 1) / kStepWaves)), dim3(64 * kStepWaves), 0,
+                         c->stream, g, ct, dst_chunk, src_objs, c->lm.p.jacobian_mode, c->lm.p.numeric_delta, c->blk_part,
+                         c->tickets, c->dev_scal, (LmScalars*)c->host_scal_dev, c->lm.p.tau, (LmCore*)nullptr, (int*)nullptr, 0,
+                         (LmHostView*)nullptr);
+    });
     ESL_HIP_TRY(hipGetLastError());
   }
   return ESL_OK;
@@ -1122,9 +1138,11 @@ static int map_launch_solve(esl_ctx* c, double lambda, const double* chunk = nul
   const DevGraph& g = c->g;
   if (!chunk) chunk = c->chunk_out;
   ProfScope ps(c, 1);
-  hipLaunchKernelGGL(k_obj_solve, dim3((g.n_objs + 63) / 64), dim3(64), 0, c->stream, g, chunk_table(c), chunk, c->objs,
-                     c->lm.p.jacobian_mode, c->lm.p.numeric_delta, lambda,
-                     c->lm.p.tau, c->dev_scal, c->xo, c->objs_trial, c->obj_part, c->solve_part);
+  robust_dispatch(c->robust_on, [&](auto robust) {
+    hipLaunchKernelGGL(k_obj_solve<decltype(robust)::value>, dim3((g.n_objs + 63) / 64), dim3(64), 0, c->stream, g, chunk_table(c), chunk, c->objs,
+                       c->lm.p.jacobian_mode, c->lm.p.numeric_delta, lambda,
+                       c->lm.p.tau, c->dev_scal, c->xo, c->objs_trial, c->obj_part, c->solve_part);
+  });
   ESL_HIP_TRY(hipGetLastError());
   return ESL_OK;
 }
@@ -1137,21 +1155,26 @@ static int map_launch_try(esl_ctx* c, double lambda, const double* chunk = nullp
   {
     ProfScope ps(c, 1);
     // 3-D chunks first (no reduction), then the bbox chunks whose last workgroup reduces everything
-    if (c->n_ids_e3 > 0)
-      hipLaunchKernelGGL((k_chunk_chi2<1, false>), dim3((c->n_ids_e3 + 7) / 8), dim3(256), 0, c->stream, g, ct, c->ck_ids_e3, c->n_ids_e3,
-                         c->cams, c->objs_trial, c->obj_part, c->chunk_chi, c->tickets + 1, lambda, c->lm.p.tau, c->dev_scal,
+    robust_dispatch(c->robust_on, [&](auto robust) {
+      constexpr bool R = decltype(robust)::value;
+      if (c->n_ids_e3 > 0)
+        hipLaunchKernelGGL((k_chunk_chi2<1, false, R>), dim3((c->n_ids_e3 + 7) / 8), dim3(256), 0, c->stream, g, ct, c->ck_ids_e3, c->n_ids_e3,
+                           c->cams, c->objs_trial, c->obj_part, c->chunk_chi, c->tickets + 1, lambda, c->lm.p.tau, c->dev_scal,
+                           (LmScalars*)c->host_scal_dev);
+      hipLaunchKernelGGL((k_chunk_chi2<0, true, R>), dim3(std::max(1, (c->n_ids_bb + 3) / 4)), dim3(256), 0, c->stream, g, ct, c->ck_ids_bb,
+                         c->n_ids_bb, c->cams, c->objs_trial, c->obj_part, c->chunk_chi, c->tickets + 1, lambda, c->lm.p.tau, c->dev_scal,
                          (LmScalars*)c->host_scal_dev);
-    hipLaunchKernelGGL((k_chunk_chi2<0, true>), dim3(std::max(1, (c->n_ids_bb + 3) / 4)), dim3(256), 0, c->stream, g, ct, c->ck_ids_bb,
-                       c->n_ids_bb, c->cams, c->objs_trial, c->obj_part, c->chunk_chi, c->tickets + 1, lambda, c->lm.p.tau, c->dev_scal,
-                       (LmScalars*)c->host_scal_dev);
+    });
   }
   ESL_HIP_TRY(hipGetLastError());
   return ESL_OK;
 }
 static int map_combine(esl_ctx* c) {
   if (c->sys_combined || c->g.n_objs == 0) return ESL_OK;
-  hipLaunchKernelGGL(k_chunk_combine, dim3((c->g.n_objs * 54 + 255) / 256), dim3(256), 0, c->stream, c->g, chunk_table(c),
-                     c->chunk_out, c->objs, c->lm.p.jacobian_mode, c->lm.p.numeric_delta, c->Hoo, c->bo);
+  robust_dispatch(c->robust_on, [&](auto robust) {
+    hipLaunchKernelGGL(k_chunk_combine<decltype(robust)::value>, dim3((c->g.n_objs * 54 + 255) / 256), dim3(256), 0, c->stream, c->g, chunk_table(c),
+                       c->chunk_out, c->objs, c->lm.p.jacobian_mode, c->lm.p.numeric_delta, c->Hoo, c->bo);
+  });
   ESL_HIP_TRY(hipGetLastError());
   c->sys_combined = true;
   return ESL_OK;
@@ -1172,6 +1195,16 @@ static int read_parts(esl_ctx* c, double out[4]) {
   return ESL_OK;
 }
 
+// the context's robust setting (esl_lm_set_robust) into the device graph: read at the start of every run
+static void robust_to_graph(esl_ctx* c) {
+  c->robust_on = false;
+  for (int k = 0; k < ESL_EDGE_CLASSES; ++k) {
+    c->g.rk_kind[k] = c->robust.kind[k];
+    c->g.rk_delta[k] = c->robust.kind[k] != ESL_ROBUST_NONE ? c->robust.delta[k] : 1.0;
+    c->robust_on = c->robust_on || c->robust.kind[k] != ESL_ROBUST_NONE;
+  }
+}
+
 // NaN pre-check of the bbox edges at the start state (Optimizer.cpp:234-243); the dropped count stays on the device
 // (c->chol_info + 2) -- the synchronous caller reads it back, the device-driven run lets k_chunk_finalize report it.
 static int lm_begin_enqueue(esl_ctx* c, const esl_lm_params* p, bool validate_in_linearize = false) {
@@ -1180,6 +1213,7 @@ static int lm_begin_enqueue(esl_ctx* c, const esl_lm_params* p, bool validate_in
   c->lm.p = *p;
   c->g.bbox_mode = p->bbox_residual == ESL_BBOX_TANGENCY ? 1 : 0;
   c->g.yt.as_written = p->e3d_half_turn ? 1 : 0;
+  robust_to_graph(c);
   c->lm.slam = c->g.n_free_cams > 0;
   c->lm.have_trial = false;
   int* cnt = c->chol_info + 2;
@@ -1313,10 +1347,12 @@ static int optimize_mapping_device(esl_ctx* c, const esl_lm_params* p, esl_lm_re
   if (rc) return rc;
   {
     ProfScope ps(c, 4);
-    hipLaunchKernelGGL(k_chunk_finalize_rows, dim3(std::max(1, (g.n_objs + kStepWaves - 1) / kStepWaves)), dim3(64 * kStepWaves), 0, c->stream, g, chunk_table(c), c->chunk_out,
-                       c->objs, c->lm.p.jacobian_mode, c->lm.p.numeric_delta, c->blk_part, c->tickets, c->dev_scal,
-                       (LmScalars*)c->host_scal_dev, p->tau, sharded ? (LmCore*)nullptr : core, c->chol_info + 2, c->n_grav_edges,
-                       (LmHostView*)c->lm_host_dev);
+    robust_dispatch(c->robust_on, [&](auto robust) {
+      hipLaunchKernelGGL(k_chunk_finalize_rows<decltype(robust)::value>, dim3(std::max(1, (g.n_objs + kStepWaves - 1) / kStepWaves)), dim3(64 * kStepWaves), 0,
+                         c->stream, g, chunk_table(c), c->chunk_out, c->objs, c->lm.p.jacobian_mode, c->lm.p.numeric_delta, c->blk_part, c->tickets,
+                         c->dev_scal, (LmScalars*)c->host_scal_dev, p->tau, sharded ? (LmCore*)nullptr : core, c->chol_info + 2, c->n_grav_edges,
+                         (LmHostView*)c->lm_host_dev);
+    });
     ESL_HIP_TRY(hipGetLastError());
   }
   if (sharded && (rc = comm_gather_scalars_device(c))) return rc;   // collective: every rank's {chi2, max diag, has_edges}
@@ -1346,11 +1382,13 @@ static int optimize_mapping_device(esl_ctx* c, const esl_lm_params* p, esl_lm_re
       LmCore* nxt = core + ((enq + 1) & 1);
       {
         ProfScope ps(c, 1);
-        hipLaunchKernelGGL(k_lm_step_rows, dim3(n_step_blocks), dim3(64 * kStepWaves), 0, c->stream, g, chunk_table(c), c->chunk_out,
-                           c->chunk_out2, c->objs, c->objs_trial, in, nxt, c->blk_chi, n_lin_blocks, c->solve_part + 4 * n_step_blocks * (enq & 1),
-                           c->solve_part + 4 * n_step_blocks * ((enq + 1) & 1), enq == 0 ? (sharded ? 2 : 1) : 0, p->max_iters, p->max_trials,
-                           (LmHostView*)c->lm_host_dev, c->lm.p.jacobian_mode, c->lm.p.numeric_delta, c->xo,
-                           sharded ? c->dev_gather : (const double*)nullptr, sharded ? c->comm_ranks : 0, p->tau);
+        robust_dispatch(c->robust_on, [&](auto robust) {
+          hipLaunchKernelGGL(k_lm_step_rows<decltype(robust)::value>, dim3(n_step_blocks), dim3(64 * kStepWaves), 0, c->stream, g, chunk_table(c), c->chunk_out,
+                             c->chunk_out2, c->objs, c->objs_trial, in, nxt, c->blk_chi, n_lin_blocks, c->solve_part + 4 * n_step_blocks * (enq & 1),
+                             c->solve_part + 4 * n_step_blocks * ((enq + 1) & 1), enq == 0 ? (sharded ? 2 : 1) : 0, p->max_iters, p->max_trials,
+                             (LmHostView*)c->lm_host_dev, c->lm.p.jacobian_mode, c->lm.p.numeric_delta, c->xo,
+                             sharded ? c->dev_gather : (const double*)nullptr, sharded ? c->comm_ranks : 0, p->tau);
+        });
         ESL_HIP_TRY(hipGetLastError());
       }
       // the second trial's linearisation (always a live launch when it exists) of every FOURTH run is the sampled one: an event
@@ -1554,6 +1592,56 @@ int esl_profile_get(esl_ctx* c, int64_t count[ESL_PROF_KINDS], double total_ms[E
   return ESL_OK;
 }
 
+int esl_lm_set_robust(esl_ctx* c, const esl_robust_params* p) {
+  if (!c) return ESL_ERR_INVALID;
+  esl_robust_params r = {{0, 0, 0, 0}, {1, 1, 1, 1}};
+  if (p) {
+    for (int k = 0; k < ESL_EDGE_CLASSES; ++k) {
+      if (p->kind[k] < ESL_ROBUST_NONE || p->kind[k] > ESL_ROBUST_TUKEY) { set_error("esl_lm_set_robust: unknown kernel kind"); return ESL_ERR_INVALID; }
+      if (p->kind[k] != ESL_ROBUST_NONE && !(std::isfinite(p->delta[k]) && p->delta[k] > 0)) {
+        set_error("esl_lm_set_robust: delta must be finite and > 0"); return ESL_ERR_INVALID;
+      }
+    }
+    r = *p;
+  }
+  c->robust = r;
+  return ESL_OK;
+}
+
+int esl_edge_chi2(esl_ctx* c, int32_t edge_class, double* chi2, double* weight, int64_t count) {
+  if (!c || edge_class < 0 || edge_class >= ESL_EDGE_CLASSES || count < 0) return ESL_ERR_INVALID;
+  if (!c->graph_loaded || !c->states_loaded) { set_error("esl_edge_chi2: upload graph and states first"); return ESL_ERR_STATE; }
+  DevGraph g = c->g;   // the context's robust setting (the one its runs apply), residual settings of the last run
+  for (int k = 0; k < ESL_EDGE_CLASSES; ++k) { g.rk_kind[k] = c->robust.kind[k]; g.rk_delta[k] = c->robust.kind[k] ? c->robust.delta[k] : 1.0; }
+  const std::vector<int>* slot_of = edge_class == ESL_EDGE_BBOX ? &c->h_bb_slot_of : edge_class == ESL_EDGE_E3D ? &c->h_e3_slot_of
+                                  : edge_class == ESL_EDGE_GRAVITY ? &c->h_grav_obj : nullptr;
+  const int64_t n_caller = slot_of ? (int64_t)slot_of->size() : (int64_t)c->h_od_i.size();
+  if (count != n_caller) { set_error("esl_edge_chi2: count is not the class's edge count"); return ESL_ERR_INVALID; }
+  if (count == 0) return ESL_OK;
+  const int n_slots = edge_class == ESL_EDGE_BBOX ? g.n_bbox : edge_class == ESL_EDGE_E3D ? g.n_e3d : edge_class == ESL_EDGE_GRAVITY ? g.n_objs : g.n_odom;
+  ESL_HIP_TRY(hipSetDevice(c->device));
+  const size_t need = (size_t)n_slots * 2;
+  if (need > c->eq_cap) {   // grow-only: a query per frame allocates nothing once the graph has stopped growing
+    if (c->eq_buf) ESL_HIP_TRY(hipFree(c->eq_buf));
+    c->eq_buf = nullptr; c->eq_cap = 0;
+    ESL_HIP_TRY(hipMalloc((void**)&c->eq_buf, need * sizeof(double)));
+    c->eq_cap = need;
+  }
+  double* d = c->eq_buf;
+  std::vector<double> h(need);
+  hipLaunchKernelGGL(k_edge_chi2, dim3((n_slots + 255) / 256), dim3(256), 0, c->stream, g, (int)edge_class, c->cams, c->objs, d, d + n_slots);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d, (size_t)n_slots * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) { set_error(std::string("esl_edge_chi2: ") + hipGetErrorString(e)); return ESL_ERR_HIP; }
+  for (int64_t i = 0; i < count; ++i) {   // slot -> caller order
+    const int sl = slot_of ? (*slot_of)[(size_t)i] : (int)i;
+    if (chi2) chi2[i] = h[(size_t)sl];
+    if (weight) weight[i] = h[(size_t)n_slots + sl];
+  }
+  return ESL_OK;
+}
+
 int esl_lm_download(esl_ctx* c, int32_t which, double* dst, int64_t count) {
   if (!c || !dst || count < 0) return ESL_ERR_INVALID;
   if (!c->graph_loaded) { set_error("esl_lm_download: no graph"); return ESL_ERR_STATE; }
@@ -1616,5 +1704,12 @@ template __global__ void k_chunk_linearize<ESL_JAC_ANALYTIC, 0, false>(DevGraph,
 template __global__ void k_chunk_linearize<ESL_JAC_ANALYTIC, 1, false>(DevGraph, ChunkTable, const int*, int, const double*, const double*,
                                                                        const double*, double, double*, double*, double*, int,
                                                                        const LmCore*, int*);
+// and their robust twins (esl_lm_set_robust)
+template __global__ void k_chunk_linearize<ESL_JAC_ANALYTIC, 0, 0, false, true>(DevGraph, ChunkTable, const int*, int, const double*, const double*,
+                                                                                const double*, double, double*, double*, double*, int,
+                                                                                const LmCore*, int*);
+template __global__ void k_chunk_linearize<ESL_JAC_ANALYTIC, 1, 0, false, true>(DevGraph, ChunkTable, const int*, int, const double*, const double*,
+                                                                                const double*, double, double*, double*, double*, int,
+                                                                                const LmCore*, int*);
 }  // namespace esl
 #endif

@@ -4,6 +4,7 @@
 
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/esl.h"
@@ -31,6 +32,8 @@ struct DevGraph {
   double grav_w = 0;
   int check_vis = 0, img_rows = 0, img_cols = 0;   // esl_graph::check_visibility / image_rows / image_cols
   int bbox_mode = 0;   // esl_lm_params::bbox_residual of the current run (0 reprojection, 1 plane tangency)
+  int rk_kind[ESL_EDGE_CLASSES] = {0, 0, 0, 0};       // esl_lm_set_robust of the current run, per esl_edge_class: read by the
+  double rk_delta[ESL_EDGE_CLASSES] = {1, 1, 1, 1};   // ROBUST = true kernel instantiations only
   YawTable yt;
   // per ellipsoid
   int* bb_start = nullptr;   // n_objs + 1
@@ -63,6 +66,34 @@ struct DevGraph {
   // replicated on every rank and must enter the summed system once -> only shard_rank 0 contributes them
   int shard_rank = 0;
 };
+
+// robust kernel of edge class `cls` on an edge's raw chi2: chi <- rho0(chi), w <- rho1(chi) w (g2o robustInformation).  The compile-time
+// switch keeps the default instantiations exactly what they were (a run-time flag costs registers and occupancy: esl_kernels_chunk.hpp).
+template <bool ROBUST>
+__device__ __forceinline__ void robust_edge(const DevGraph& g, int cls, double& chi, double& w) {
+  if (ROBUST) {
+    double r0, r1;
+    robustify(g.rk_kind[cls], g.rk_delta[cls], chi, r0, r1);
+    chi = r0; w *= r1;
+  }
+}
+// the merged gravity prior of an ellipsoid with ng edges, residual rg: weight of its J^T J (in: grav_w ng) and its chi2 (in: wg rg^2)
+// become ng rho1 grav_w and ng rho0(grav_w rg^2)
+template <bool ROBUST>
+__device__ __forceinline__ void robust_grav(const DevGraph& g, int ng, double rg, double& wg, double& chi) {
+  if (ROBUST) {
+    double r0, r1;
+    robustify(g.rk_kind[ESL_EDGE_GRAVITY], g.rk_delta[ESL_EDGE_GRAVITY], g.grav_w * rg * rg, r0, r1);
+    chi = ng * r0; wg = (g.grav_w * ng) * r1;
+  }
+}
+
+// launch helper: f(std::true_type) when the run has a robust kernel on some edge class, f(std::false_type) otherwise
+template <class F>
+inline void robust_dispatch(bool on, F&& f) {
+  if (on) f(std::true_type{});
+  else f(std::false_type{});
+}
 
 struct ChunkTableFwd;
 struct LmState {
@@ -135,6 +166,11 @@ struct esl_ctx {
   double* host_part = nullptr;  // pinned: 8 doubles
   double* dev_part = nullptr;
   esl::LmState lm;
+  esl_robust_params robust = {{0, 0, 0, 0}, {1, 1, 1, 1}};   // esl_lm_set_robust; copied into g at the start of every run
+  bool robust_on = false;                                     // the current run has a kernel on some class: ROBUST instantiations
+  // caller order -> slot of the ellipsoid-sorted edge arrays (esl_edge_chi2), kept across esl_graph_append; gravity: caller's ellipsoids
+  std::vector<int> h_bb_slot_of, h_e3_slot_of, h_grav_obj;
+  double* eq_buf = nullptr; size_t eq_cap = 0;   // grow-only device buffer of esl_edge_chi2 (2 doubles per slot)
   double* cams_snap = nullptr; double* objs_snap = nullptr;
   // profiling (HIP events on this stream)
   bool prof_on = false;

@@ -169,7 +169,9 @@ __device__ __forceinline__ void reduce_group_e3d_lds(const double* Jp, const dou
 // VALIDATE (bbox only): this is the first linearisation of a run and doubles as the reference's NaN pre-check of the
 // bbox edges (Optimizer.cpp:234-243): an edge whose residual is NaN at the start state is marked invalid for the
 // whole run and counted in *n_dropped (same residual code as k_bbox_validate, which the synchronous API still uses).
-template <int JAC, int TYPE, int VALIDATE = 0, bool TANG = false>
+// ROBUST: the edge classes' robust kernels (esl_lm_set_robust) weight each edge after the NaN / visibility test, which decides on
+// the raw chi2.
+template <int JAC, int TYPE, int VALIDATE = 0, bool TANG = false, bool ROBUST = false>
 __device__ __forceinline__ void chunk_linearize_body(const DevGraph& g, const ChunkTable& ct, const int* __restrict__ ids, int n_ids,
                                                      const double* __restrict__ cams, const double* __restrict__ objs, double delta,
                                                      double* __restrict__ chunk_out, double* __restrict__ wg_chi /* LDS, 8 slots */,
@@ -247,6 +249,7 @@ __device__ __forceinline__ void chunk_linearize_body(const DevGraph& g, const Ch
           for (int k = 0; k < 36; ++k) J[k] = 0;
         }
       }
+      robust_edge<ROBUST>(g, ESL_EDGE_BBOX, chi, w);
     } else {
 #pragma unroll
       for (int k = 0; k < 36; ++k) J[k] = 0;
@@ -287,6 +290,7 @@ __device__ __forceinline__ void chunk_linearize_body(const DevGraph& g, const Ch
 #pragma unroll
       for (int k = 0; k < 9; ++k) chi += r[k] * r[k];
       chi *= w;
+      robust_edge<ROBUST>(g, ESL_EDGE_E3D, chi, w);
     } else {
 #pragma unroll
       for (int k = 0; k < 36; ++k) Jp[k] = 0;
@@ -416,7 +420,7 @@ __device__ double block256_max(double v, double* sm) {
 // the rest the bbox chunks.  Launched back to back the two kernels ran 18 + 17.5 us at C4 although neither fills the
 // chip for long (3-D: ~0.7 waves per SIMD on a 4.8k-instruction stream; bbox: 3 waves per SIMD, 1.7k instructions);
 // together they take 27 us.
-template <int JAC, int VALIDATE = 0, bool TANG = false>
+template <int JAC, int VALIDATE = 0, bool TANG = false, bool ROBUST = false>
 static __global__ __launch_bounds__(64 * kLinWaves, ESL_LIN_MIN_WAVES) void k_chunk_linearize_both(DevGraph g, ChunkTable ct, const int* __restrict__ ids_e3, int n_e3,
                                                                      int nb_e3, const int* __restrict__ ids_bb, int n_bb,
                                                                      const double* __restrict__ cams,
@@ -433,11 +437,11 @@ static __global__ __launch_bounds__(64 * kLinWaves, ESL_LIN_MIN_WAVES) void k_ch
     if (st->cur == 0) { objs = objs_b; chunk_out = chunk_b; }   // trial = the pair that is NOT current
   }
   wg_chi_begin(wg_chi);
-  if ((int)blockIdx.x < nb_e3) chunk_linearize_body<JAC, 1>(g, ct, ids_e3, n_e3, cams, objs, delta, chunk_out, wg_chi, tr_all, blockIdx.x);
-  else chunk_linearize_body<JAC, 0, VALIDATE, TANG>(g, ct, ids_bb, n_bb, cams, objs, delta, chunk_out, wg_chi, tr_all, blockIdx.x - nb_e3, n_dropped);
+  if ((int)blockIdx.x < nb_e3) chunk_linearize_body<JAC, 1, 0, false, ROBUST>(g, ct, ids_e3, n_e3, cams, objs, delta, chunk_out, wg_chi, tr_all, blockIdx.x);
+  else chunk_linearize_body<JAC, 0, VALIDATE, TANG, ROBUST>(g, ct, ids_bb, n_bb, cams, objs, delta, chunk_out, wg_chi, tr_all, blockIdx.x - nb_e3, n_dropped);
   wg_chi_end(wg_chi, blk_chi, blockIdx.x);
 }
-template <int JAC, int TYPE, int VALIDATE = 0, bool TANG = false>
+template <int JAC, int TYPE, int VALIDATE = 0, bool TANG = false, bool ROBUST = false>
 static __global__ __launch_bounds__(64 * kLinWaves) void k_chunk_linearize(DevGraph g, ChunkTable ct, const int* __restrict__ ids, int n_ids,
                                                                 const double* __restrict__ cams,
                                                                 const double* __restrict__ objs_a, const double* __restrict__ objs_b,
@@ -453,10 +457,11 @@ static __global__ __launch_bounds__(64 * kLinWaves) void k_chunk_linearize(DevGr
     if (st->cur == 0) { objs = objs_b; chunk_out = chunk_b; }
   }
   wg_chi_begin(wg_chi);
-  chunk_linearize_body<JAC, TYPE, VALIDATE, TANG>(g, ct, ids, n_ids, cams, objs, delta, chunk_out, wg_chi, tr_all, blockIdx.x, n_dropped);
+  chunk_linearize_body<JAC, TYPE, VALIDATE, TANG, ROBUST>(g, ct, ids, n_ids, cams, objs, delta, chunk_out, wg_chi, tr_all, blockIdx.x, n_dropped);
   wg_chi_end(wg_chi, blk_chi, blk_offset + blockIdx.x);
 }
 
+template <bool ROBUST>
 __device__ __forceinline__ void obj_solve_one(const DevGraph& g, const ChunkTable& ct, const double* __restrict__ chunk_out,
                                               const double* __restrict__ objs, int jac, double delta, double lambda,
                                               double* __restrict__ xo, double* __restrict__ objs_trial, double* __restrict__ part, int o,
@@ -483,7 +488,7 @@ __device__ __forceinline__ void obj_solve_one(const DevGraph& g, const ChunkTabl
       for (int k = 0; k < 54; ++k) hb[k] += p[k];
     }
   }
-  const double wg = g.grav_w * ngrav;
+  const double wg0 = g.grav_w * ngrav;
   if (ngrav > 0) {  // the gravity prior is a unary edge on this ellipsoid: linearise it here
     double Jg[9], rg;
     if (jac == ESL_JAC_ANALYTIC) rg = jac_grav(e, g.grav_n, Jg);
@@ -491,6 +496,8 @@ __device__ __forceinline__ void obj_solve_one(const DevGraph& g, const ChunkTabl
       rg = res_grav(e, g.grav_n);
       numeric_jac_obj(e, delta, 1, Jg, [&](const Ell& ep, double* o1) { o1[0] = res_grav(ep, g.grav_n); });
     }
+    double wg = wg0, unused = 0;
+    robust_grav<ROBUST>(g, ngrav, rg, wg, unused);
     int p = 0;
 #pragma unroll
     for (int a = 0; a < 9; ++a) {
@@ -507,7 +514,7 @@ __device__ __forceinline__ void obj_solve_one(const DevGraph& g, const ChunkTabl
   const Ell en = ell_oplus(e, x);
   ell_store(en, objs_trial + 10 * o);
   double cg = 0;
-  if (ngrav > 0) { const double rg = res_grav(en, g.grav_n); cg = wg * rg * rg; }
+  if (ngrav > 0) { const double rg = res_grav(en, g.grav_n); double w = wg0; cg = wg0 * rg * rg; robust_grav<ROBUST>(g, ngrav, rg, w, cg); }
   part[o * 4 + 0] = cg;   // chi2 of the gravity prior at the trial state
   part[o * 4 + 2] = scale;
   part[o * 4 + 3] = ok ? 1.0 : 0.0;
@@ -519,6 +526,7 @@ __device__ __forceinline__ void obj_solve_one(const DevGraph& g, const ChunkTabl
 // unrolled register LDL^T of the 9x9, retraction, trial state.  (A wave per ellipsoid left 63 lanes idle on a
 // serial dependency chain; 2k ellipsoids are 32 full waves this way.)
 // lambda < 0: lambda = tau * max_diag read from device memory (first LM iteration, computeLambdaInit).
+template <bool ROBUST = false>
 static __global__ __launch_bounds__(64) void k_obj_solve(DevGraph g, ChunkTable ct, const double* __restrict__ chunk_out,
                                                          const double* __restrict__ objs, int jac, double delta, double lambda, double tau,
                                                          const double* __restrict__ dev_scal, double* __restrict__ xo,
@@ -527,7 +535,7 @@ static __global__ __launch_bounds__(64) void k_obj_solve(DevGraph g, ChunkTable 
   if (lambda < 0) lambda = tau * dev_scal[1];
   const int o = blockIdx.x * 64 + threadIdx.x;
   double cg = 0, scale = 0, okd = 1;
-  if (o < g.n_objs) obj_solve_one(g, ct, chunk_out, objs, jac, delta, lambda, xo, objs_trial, part, o, cg, scale, okd);
+  if (o < g.n_objs) obj_solve_one<ROBUST>(g, ct, chunk_out, objs, jac, delta, lambda, xo, objs_trial, part, o, cg, scale, okd);
   // this workgroup's share of the trial scalars (fixed order: shuffle tree over the 64 lanes)
   cg = wave_sum(cg); scale = wave_sum(scale);
   okd = -wave_max(-okd);
@@ -669,6 +677,7 @@ constexpr int kStepWaves = 4;
 // First iteration: chi2 of the linearisation point and max |H_kk| (computeLambdaInit).  One WAVE per ellipsoid: the chunk rows
 // are read as coalesced rows (lane = entry, up to four rows in flight); the last workgroup reduces the per-workgroup partials in
 // fixed order.  12.5 us (once per run): the ticket and the serial tail are what the time is, not the per-ellipsoid part.
+template <bool ROBUST = false>
 static __global__ __launch_bounds__(64 * kStepWaves) void k_chunk_finalize_rows(DevGraph g, ChunkTable ct, const double* __restrict__ chunk_out,
                                                                                  const double* __restrict__ objs, int jac, double delta,
                                                                                  double* __restrict__ blk_part /* gridDim x 2 */,
@@ -700,7 +709,7 @@ static __global__ __launch_bounds__(64 * kStepWaves) void k_chunk_finalize_rows(
     const int ng = g.gr_cnt[o];
     if (ng > 0) {   // gravity prior lives on the ellipsoid itself (see k_obj_solve); evaluated uniformly by the wave
       const Ell e = ell_load(objs + 10 * o);
-      const double wg = g.grav_w * ng;
+      double wg = g.grav_w * ng;
       double Jg[9], rg;
       if (jac == ESL_JAC_ANALYTIC) rg = jac_grav(e, g.grav_n, Jg);
       else {
@@ -708,6 +717,7 @@ static __global__ __launch_bounds__(64 * kStepWaves) void k_chunk_finalize_rows(
         numeric_jac_obj(e, delta, 1, Jg, [&](const Ell& ep, double* o1) { o1[0] = res_grav(ep, g.grav_n); });
       }
       gchi = wg * rg * rg;
+      robust_grav<ROBUST>(g, ng, rg, wg, gchi);
 #pragma unroll
       for (int a = 0; a < 9; ++a) if (a_of == a) v += wg * Jg[a] * Jg[a];
     }
@@ -754,7 +764,10 @@ static __global__ __launch_bounds__(64 * kStepWaves) void k_chunk_finalize_rows(
   }
 }
 
-static __global__ __launch_bounds__(64 * kStepWaves) void k_lm_step_rows(DevGraph g, ChunkTable ct, const double* __restrict__ chunk_a,
+// (ROBUST: the kernel weights take ~2 VGPRs over the 96 that keep 5 waves per SIMD; the occupancy of the plain form is requested
+// explicitly -- it fits without scratch)
+template <bool ROBUST = false>
+static __global__ __launch_bounds__(64 * kStepWaves) __attribute__((amdgpu_waves_per_eu(ROBUST ? 5 : 1))) void k_lm_step_rows(DevGraph g, ChunkTable ct, const double* __restrict__ chunk_a,
                                                                           const double* __restrict__ chunk_b, double* __restrict__ objs_a,
                                                                           double* __restrict__ objs_b, const LmCore* __restrict__ in,
                                                                           LmCore* __restrict__ out, const double* __restrict__ blk_chi, int n_lin_blocks,
@@ -838,7 +851,7 @@ static __global__ __launch_bounds__(64 * kStepWaves) void k_lm_step_rows(DevGrap
   const double* chunk_out = s.cur ? chunk_b : chunk_a;
   double* objs_trial = s.cur ? objs_a : objs_b;
   const double lambda = s.lambda;
-  double cg = 0, scale = 0, okd = 1;
+  double cg = 0, scale = 0, okd = 1, rg_trial = 0;
   if (own) {
     const double ev = s.cur ? eb : ea;
     double e10[10];
@@ -846,7 +859,8 @@ static __global__ __launch_bounds__(64 * kStepWaves) void k_lm_step_rows(DevGrap
     for (int k = 0; k < 10; ++k) e10[k] = lm_readlane(ev, k);
     Ell e = ell_load(e10);
     if (c0 < c1 || ngrav > 0) {   // an inactive vertex is never touched (sparse_optimizer.cpp:236-257)
-      const double wg = g.grav_w * ngrav;
+      const double wg0 = g.grav_w * ngrav;
+      double wg = wg0;
       if (ngrav > 0) {   // the gravity prior is a unary edge on this ellipsoid: linearised here (uniformly by the wave)
         double Jg[9], rg;
         if (jac == ESL_JAC_ANALYTIC) rg = jac_grav(e, g.grav_n, Jg);
@@ -859,6 +873,8 @@ static __global__ __launch_bounds__(64 * kStepWaves) void k_lm_step_rows(DevGrap
           for (int k = 0; k < 9; ++k) jgs[wave][k] = Jg[k];
           jgs[wave][9] = rg;
         }
+        double unused = 0;   // (after the store: Jg is dead by then)
+        robust_grav<ROBUST>(g, ngrav, rg, wg, unused);
         __builtin_amdgcn_wave_barrier();
       }
       if (lane < 54) {
@@ -887,9 +903,10 @@ static __global__ __launch_bounds__(64 * kStepWaves) void k_lm_step_rows(DevGrap
       }
       okd = ok ? 1.0 : 0.0;
       e = ell_oplus(e, x);
-      if (ngrav > 0) { const double rg = res_grav(e, g.grav_n); cg = wg * rg * rg; }   // chi2 of the gravity prior at the trial state
+      if (ngrav > 0) { rg_trial = res_grav(e, g.grav_n); cg = wg0 * rg_trial * rg_trial; }   // chi2 of the gravity prior at the trial state
     }
     if (lane == 0) ell_store(e, objs_trial + 10 * (size_t)o);
+    if (ROBUST && ngrav > 0) { double w = 0; robust_grav<ROBUST>(g, ngrav, rg_trial, w, cg); }   // (e is dead here: no extra registers)
   }
   // this workgroup's share of the trial scalars, ellipsoids in order
   __syncthreads();
@@ -921,7 +938,7 @@ static __global__ __launch_bounds__(256) void k_lm_partials(const double* __rest
 
 // chi2 of the trial states, one instantiation per edge type (bbox: one wave per chunk; 3-D: two 32-edge chunks per
 // wave).  FINAL: the last workgroup to arrive reduces all partials in fixed order -> mapped host memory.
-template <int TYPE, bool FINAL>
+template <int TYPE, bool FINAL, bool ROBUST = false>
 static __global__ __launch_bounds__(256) void k_chunk_chi2(DevGraph g, ChunkTable ct, const int* __restrict__ ids, int n_ids,
                                                            const double* __restrict__ cams,
                                                            const double* __restrict__ objs_trial, const double* __restrict__ part,
@@ -945,6 +962,8 @@ static __global__ __launch_bounds__(256) void k_chunk_chi2(DevGraph g, ChunkTabl
         double r[4];
         res_box_edge(g.bbox_mode, se3_load(cams + 7 * g.bb_cam[i]), e, g.K, g.bb_meas + 4 * i, r);
         chi = g.bb_w[i] * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]);
+        double w = 1;
+        robust_edge<ROBUST>(g, ESL_EDGE_BBOX, chi, w);
       }
     } else if (in) {
       double r[9];
@@ -952,6 +971,8 @@ static __global__ __launch_bounds__(256) void k_chunk_chi2(DevGraph g, ChunkTabl
 #pragma unroll
       for (int k = 0; k < 9; ++k) chi += r[k] * r[k];
       chi *= g.e3_w[i];
+      double w = 1;
+      robust_edge<ROBUST>(g, ESL_EDGE_E3D, chi, w);
     }
 #pragma unroll
     for (int off = kSeg / 2; off > 0; off >>= 1) chi += __shfl_xor(chi, off, 64);
@@ -975,6 +996,7 @@ static __global__ __launch_bounds__(256) void k_chunk_chi2(DevGraph g, ChunkTabl
 }
 
 // Hoo / b_o of every ellipsoid from the chunk partials (only used by esl_lm_download and the SLAM-free inspection path)
+template <bool ROBUST = false>
 static __global__ void k_chunk_combine(DevGraph g, ChunkTable ct, const double* __restrict__ chunk_out,
                                        const double* __restrict__ objs, int jac, double delta, double* __restrict__ Hoo,
                                        double* __restrict__ bo) {
@@ -985,13 +1007,15 @@ static __global__ void k_chunk_combine(DevGraph g, ChunkTable ct, const double* 
   for (int ch = ct.ostart[o]; ch < ct.ostart[o + 1]; ++ch) s += chunk_out[(size_t)ch * kChunkOut + k];
   if (g.gr_cnt[o] > 0) {
     const Ell e = ell_load(objs + 10 * o);
-    const double wg = g.grav_w * g.gr_cnt[o];
+    double wg = g.grav_w * g.gr_cnt[o];
     double Jg[9], rg;
     if (jac == ESL_JAC_ANALYTIC) rg = jac_grav(e, g.grav_n, Jg);
     else {
       rg = res_grav(e, g.grav_n);
       numeric_jac_obj(e, delta, 1, Jg, [&](const Ell& ep, double* o1) { o1[0] = res_grav(ep, g.grav_n); });
     }
+    double unused = 0;
+    robust_grav<ROBUST>(g, g.gr_cnt[o], rg, wg, unused);
     if (k < 45) {
       int a = 0, base = 0;
       while (k >= base + (9 - a)) { base += 9 - a; ++a; }

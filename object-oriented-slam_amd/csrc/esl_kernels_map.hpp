@@ -76,6 +76,7 @@ static __global__ void k_bbox_validate(DevGraph g, const double* __restrict__ ca
 }
 
 // chi2 of every edge hanging on ellipsoid `o` for state `e` (wave-cooperative; result valid in lane 0)
+template <bool ROBUST = false>
 __device__ __forceinline__ double obj_chi2(const DevGraph& g, const double* __restrict__ cams, const Ell& e,
                                            int o, int lane) {
   double chi = 0.0;
@@ -84,7 +85,13 @@ __device__ __forceinline__ double obj_chi2(const DevGraph& g, const double* __re
     const SE3 T = se3_load(cams + 7 * g.bb_cam[i]);
     double r[4];
     res_box_edge(g.bbox_mode, T, e, g.K, g.bb_meas + 4 * i, r);
-    chi += g.bb_w[i] * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]);
+    if (ROBUST) {
+      double c = g.bb_w[i] * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]), w = 1;
+      robust_edge<ROBUST>(g, ESL_EDGE_BBOX, c, w);
+      chi += c;
+    } else {
+      chi += g.bb_w[i] * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]);
+    }
   }
   for (int i = g.e3_start[o] + lane; i < g.e3_start[o + 1]; i += 64) {
     if (g.e3_obj[i] < 0) continue;   // slack slot of the appendable layout (its all-zero "measurement" has no rotation: 0 x NaN)
@@ -95,13 +102,70 @@ __device__ __forceinline__ double obj_chi2(const DevGraph& g, const double* __re
     double c = 0;
 #pragma unroll
     for (int k = 0; k < 9; ++k) c += r[k] * r[k];
-    chi += g.e3_w[i] * c;
+    if (ROBUST) {
+      c *= g.e3_w[i];
+      double w = 1;
+      robust_edge<ROBUST>(g, ESL_EDGE_E3D, c, w);
+      chi += c;
+    } else {
+      chi += g.e3_w[i] * c;
+    }
   }
   if (lane < g.gr_cnt[o]) {
     const double r = res_grav(e, g.grav_n);
-    chi += g.grav_w * r * r;
+    if (ROBUST) {
+      double c = g.grav_w * r * r, w = 1;
+      robust_edge<ROBUST>(g, ESL_EDGE_GRAVITY, c, w);
+      chi += c;
+    } else {
+      chi += g.grav_w * r * r;
+    }
   }
   return wave_sum(chi);
+}
+
+// ---- esl_edge_chi2: raw chi2 and robust weight rho1 of every slot of one edge class ---------------------------------------
+// One lane per slot (gravity: per ellipsoid, the value of each of its merged edges), with the residual settings and kernels of the
+// last run.  Dropped bbox edges (bb_valid = 0) get weight 0; slack slots of an appendable layout 0 / 0.
+static __global__ __launch_bounds__(256) void k_edge_chi2(DevGraph g, int cls, const double* __restrict__ cams, const double* __restrict__ objs,
+                                                         double* __restrict__ chi_out, double* __restrict__ w_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int n = cls == ESL_EDGE_BBOX ? g.n_bbox : cls == ESL_EDGE_E3D ? g.n_e3d : cls == ESL_EDGE_GRAVITY ? g.n_objs : g.n_odom;
+  if (i >= n) return;
+  double chi = 0;
+  bool live = true;
+  if (cls == ESL_EDGE_BBOX) {
+    live = g.bb_obj[i] >= 0 && g.bb_valid[i];
+    if (g.bb_obj[i] >= 0) {
+      double r[4];
+      res_box_edge(g.bbox_mode, se3_load(cams + 7 * g.bb_cam[i]), ell_load(objs + 10 * g.bb_obj[i]), g.K, g.bb_meas + 4 * i, r);
+      chi = g.bb_w[i] * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]);
+    }
+  } else if (cls == ESL_EDGE_E3D) {
+    live = g.e3_obj[i] >= 0;
+    if (live) {
+      double r[9];
+      res_e3d(se3_load(cams + 7 * g.e3_cam[i]), ell_load(objs + 10 * g.e3_obj[i]), ell_load(g.e3_meas + 10 * i), g.yt, r);
+      double c = 0;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) c += r[k] * r[k];
+      chi = g.e3_w[i] * c;
+    }
+  } else if (cls == ESL_EDGE_GRAVITY) {
+    if (g.gr_cnt[i] > 0) {
+      const double r = res_grav(ell_load(objs + 10 * i), g.grav_n);
+      chi = g.grav_w * r * r;
+    }
+  } else {
+    double r[6];
+    res_odom(se3_load(cams + 7 * g.od_i[i]), se3_load(cams + 7 * g.od_j[i]), se3_load(g.od_meas + 7 * i), r);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) chi += r[k] * g.od_info[6 * i + k] * r[k];
+  }
+  double r0, r1;
+  robustify(g.rk_kind[cls], g.rk_delta[cls], chi, r0, r1);
+  chi_out[i] = chi;
+  w_out[i] = live ? r1 : 0.0;
 }
 
 // ---- esl_graph_append: new edges into their slots of the ellipsoid-sorted arrays ----------------------------------------

@@ -165,7 +165,7 @@ __device__ __forceinline__ void reduce_group_lds_e3d64(const double* Jp, const d
 // kChunkOut doubles: 45 packed H, 9 b, chi2).  One instantiation per edge type (very different register needs).
 // Round 2's form ran one wave per ELLIPSOID over all its edges: 50 waves at C3 (186 us), its tail set by the ellipsoid with the
 // most edges.
-template <int JAC, int TYPE>
+template <int JAC, int TYPE, bool ROBUST = false>
 static __global__ __launch_bounds__(64 * kLinWaves) void k_slam_linearize_chunks(
     DevGraph g, ChunkTable ct, const int* __restrict__ ids, int n_ids, const double* __restrict__ cams, const double* __restrict__ objs,
     double delta, double* __restrict__ chunk_out, double* __restrict__ W, double* __restrict__ A) {
@@ -241,6 +241,7 @@ static __global__ __launch_bounds__(64 * kLinWaves) void k_slam_linearize_chunks
         }
       }
       chi = w * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]);
+      robust_edge<ROBUST>(g, ESL_EDGE_BBOX, chi, w);   // before W / A: the camera side carries the same weight
       if (cam_free) store_cam_terms<4>(Jc, Jo, r, w, W, A, EU, (long)i);
     }
     if (JAC == ESL_JAC_NUMERIC) __builtin_amdgcn_wave_barrier();   // the perturbed states have been read; the tile is reused
@@ -266,6 +267,7 @@ static __global__ __launch_bounds__(64 * kLinWaves) void k_slam_linearize_chunks
 #pragma unroll
       for (int k = 0; k < 9; ++k) cc += r[k] * r[k];
       chi = w * cc;
+      robust_edge<ROBUST>(g, ESL_EDGE_E3D, chi, w);
       if (cam_free) {   // exp(d) Tcw == right perturbation of E by Ad((Tcw T_est)^-1) d  (jac_e3d)
         double Ad[36], Jcp[36];
         se3_adj(se3_inv(se3_mul(T, e.pose)), Ad);
@@ -322,6 +324,7 @@ static __global__ __launch_bounds__(64 * kLinWaves) void k_slam_linearize_chunks
 #pragma unroll
       for (int k = 0; k < 9; ++k) cc += r[k] * r[k];
       chi = w * cc;
+      robust_edge<ROBUST>(g, ESL_EDGE_E3D, chi, w);
       if (cam_free) {
         double Jcp[36];
 #pragma unroll
@@ -353,7 +356,7 @@ static __global__ __launch_bounds__(64 * kLinWaves) void k_slam_linearize_chunks
 
 // Hoo (45 packed), b_o (9), chi2 and max |H_kk| of every ellipsoid from its chunk partials (chunk order: deterministic) + its
 // gravity prior; one wave per ellipsoid, lane k < 55 = entry k
-template <int JAC>
+template <int JAC, bool ROBUST = false>
 static __global__ __launch_bounds__(kWave* kWavesPerBlock) void k_slam_combine(DevGraph g, ChunkTable ct, const double* __restrict__ chunk_out,
                                                                          const double* __restrict__ objs, double delta,
                                                                          double* __restrict__ Hoo, double* __restrict__ bo,
@@ -367,13 +370,15 @@ static __global__ __launch_bounds__(kWave* kWavesPerBlock) void k_slam_combine(D
   const int ng = g.gr_cnt[o];
   if (ng > 0) {
     const Ell e = ell_load(objs + 10 * o);
-    const double wg = g.grav_w * ng;
+    double wg = g.grav_w * ng;
     double Jg[9], rg;
     if (JAC == ESL_JAC_ANALYTIC) rg = jac_grav(e, g.grav_n, Jg);
     else {
       rg = res_grav(e, g.grav_n);
       numeric_jac_obj(e, delta, 1, Jg, [&](const Ell& ep, double* o1) { o1[0] = res_grav(ep, g.grav_n); });
     }
+    double gchi = wg * rg * rg;
+    robust_grav<ROBUST>(g, ng, rg, wg, gchi);
     if (lane < 45) {
       double ja = 0, jc = 0;
 #pragma unroll
@@ -385,7 +390,7 @@ static __global__ __launch_bounds__(kWave* kWavesPerBlock) void k_slam_combine(D
       for (int q = 0; q < 9; ++q) if (q == lane - 45) ja = Jg[q];
       v -= ja * (wg * rg);
     } else if (lane == 54) {
-      v += wg * rg * rg;
+      v += gchi;
     }
   }
   if (lane < 45) Hoo[(size_t)o * 45 + lane] = v;
@@ -401,7 +406,7 @@ static __global__ __launch_bounds__(kWave* kWavesPerBlock) void k_slam_combine(D
 // odometry edges: Aod[e*90 ..] = Hii(21) bi(6) Hjj(21) bj(6) Hij(36, row-major i x j); od_part[e] = chi2
 // (launched with 128 threads: without the bound the compiler sizes the register file for 1,024 threads per workgroup -- 128 VGPRs --
 //  and the analytic instantiation spilt 540 B per lane, the numeric one 4.3 KB)
-template <int JAC>
+template <int JAC, bool ROBUST = false>
 static __global__ __launch_bounds__(128) void k_slam_odom(DevGraph g, const double* __restrict__ cams, double delta, double* __restrict__ Aod,
                             double* __restrict__ od_chi) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -428,6 +433,12 @@ static __global__ __launch_bounds__(128) void k_slam_odom(DevGraph g, const doub
   double w[6], chi = 0;
 #pragma unroll
   for (int k = 0; k < 6; ++k) { w[k] = g.od_info[6 * e + k]; chi += r[k] * w[k] * r[k]; }
+  if (ROBUST) {
+    double rho1 = 1;
+    robust_edge<ROBUST>(g, ESL_EDGE_ODOM, chi, rho1);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) w[k] *= rho1;
+  }
   od_chi[e] = chi;
   int p = 0;
 #pragma unroll
@@ -855,6 +866,7 @@ static __global__ void k_slam_fold_info(const int* __restrict__ info, double* __
 }
 
 // chi2 of the trial states in ONE launch: blocks [0, nb_obj) take a wave per ellipsoid (its bbox, 3-D and gravity edges), the rest a lane per odometry edge
+template <bool ROBUST = false>
 static __global__ __launch_bounds__(kWave* kWavesPerBlock) void k_slam_chi2_all(DevGraph g, int nb_obj, const double* __restrict__ cams,
                                                                                 const double* __restrict__ objs, double* __restrict__ part,
                                                                                 double* __restrict__ od_chi) {
@@ -863,7 +875,7 @@ static __global__ __launch_bounds__(kWave* kWavesPerBlock) void k_slam_chi2_all(
     const int o = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
     if (o >= g.n_objs) return;
     const Ell e = ell_load(objs + 10 * o);
-    const double chi = obj_chi2(g, cams, e, o, lane);
+    const double chi = obj_chi2<ROBUST>(g, cams, e, o, lane);
     if (lane == 0) part[o * 4 + 0] = chi;
     return;
   }
@@ -876,6 +888,8 @@ static __global__ __launch_bounds__(kWave* kWavesPerBlock) void k_slam_chi2_all(
   double chi = 0;
 #pragma unroll
   for (int k = 0; k < 6; ++k) chi += r[k] * g.od_info[6 * e + k] * r[k];
+  double w = 1;
+  robust_edge<ROBUST>(g, ESL_EDGE_ODOM, chi, w);
   od_chi[e] = chi;
 }
 

@@ -849,4 +849,24 @@ ESL_HD bool ldlt_solve_packed(const double* Hp, double lambda, const double* b, 
   return ok;
 }
 
+// g2o's robust kernels (core/robust_kernel_impl.cpp), rho0 = rho(e) and rho1 = rho'(e) of the squared error e for the
+// esl_robust_kind `kind` with width delta; e <= delta^2 is the inlier test.  The rho2 term is not needed (g2o leaves it out of
+// robustInformation).  g2o's Tukey keeps delta^2 and its reciprocal in float members; here they are double.
+__host__ __device__ __forceinline__ void robustify(int kind, double delta, double e, double& rho0, double& rho1) {
+  const double dsqr = delta * delta;
+  if (kind == 1) {          // Huber
+    if (e <= dsqr) { rho0 = e; rho1 = 1.; }
+    else { const double sqrte = sqrt(e); rho0 = 2 * sqrte * delta - dsqr; rho1 = delta / sqrte; }
+  } else if (kind == 2) {   // PseudoHuber
+    const double aux2 = sqrt((1. / dsqr) * e + 1.0);
+    rho0 = 2 * dsqr * (aux2 - 1); rho1 = 1. / aux2;
+  } else if (kind == 3) {   // Cauchy
+    const double aux = (1. / dsqr) * e + 1.0;
+    rho0 = dsqr * log(aux); rho1 = 1. / aux;
+  } else if (kind == 4) {   // Tukey
+    if (e <= dsqr) { const double d = 1 - e * (1. / dsqr), dd = d * d; rho0 = dsqr * (1 - dd * d); rho1 = 3 * dd; }
+    else { rho0 = dsqr; rho1 = 0.; }
+  } else { rho0 = e; rho1 = 1.; }
+}
+
 }  // namespace esl

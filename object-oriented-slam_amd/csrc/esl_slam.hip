@@ -715,8 +715,10 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
     hipLaunchKernelGGL(k_cf_updates, dim3((unsigned)(nb_obj + nb_cam)), dim3(256), 0, c->stream, g, nb_obj, lambda, c->objs, c->bo, c->xo, c->objs_trial, c->obj_part,
                        c->cams, c->xc, c->bc, c->cams_trial, c->cam_part);
     const int nb_co = (N + kWavesPerBlock - 1) / kWavesPerBlock, nb_od = (g.n_odom + kWave * kWavesPerBlock - 1) / (kWave * kWavesPerBlock);
-    hipLaunchKernelGGL(k_slam_chi2_all, dim3((unsigned)(nb_co + nb_od)), dim3(kWave * kWavesPerBlock), 0, c->stream, g, nb_co, c->cams_trial, c->objs_trial, c->obj_part,
-                       c->od_part);
+    robust_dispatch(c->robust_on, [&](auto robust) {
+      hipLaunchKernelGGL(k_slam_chi2_all<decltype(robust)::value>, dim3((unsigned)(nb_co + nb_od)), dim3(kWave * kWavesPerBlock), 0, c->stream, g, nb_co,
+                         c->cams_trial, c->objs_trial, c->obj_part, c->od_part);
+    });
     ESL_HIP_TRY(hipGetLastError());
   }
   return ESL_OK;
@@ -777,26 +779,32 @@ int slam_linearize(esl_ctx* c) {
       const dim3 block(64 * kLinWaves);
       const int nb_e3 = (c->n_ids_e3 + kLinWaves - 1) / kLinWaves, nb_bb = (c->n_ids_bb + kLinWaves - 1) / kLinWaves;
       // 3-D chunks first (the longer instruction stream), then the bbox chunks, then the per-ellipsoid sums
-      if (an) {
-        if (nb_e3) hipLaunchKernelGGL((k_slam_linearize_chunks<ESL_JAC_ANALYTIC, 1>), dim3(nb_e3), block, 0, c->stream, g, ct, c->ck_ids_e3, c->n_ids_e3, c->cams,
-                                      c->objs, delta, c->chunk_out, c->Wbb, c->Abb);
-        if (nb_bb) hipLaunchKernelGGL((k_slam_linearize_chunks<ESL_JAC_ANALYTIC, 0>), dim3(nb_bb), block, 0, c->stream, g, ct, c->ck_ids_bb, c->n_ids_bb, c->cams,
-                                      c->objs, delta, c->chunk_out, c->Wbb, c->Abb);
-        hipLaunchKernelGGL(k_slam_combine<ESL_JAC_ANALYTIC>, dim3((N + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kWave * kWavesPerBlock), 0, c->stream, g, ct,
-                           c->chunk_out, c->objs, delta, c->Hoo, c->bo, c->obj_part);
-      } else {
-        if (nb_e3) hipLaunchKernelGGL((k_slam_linearize_chunks<ESL_JAC_NUMERIC, 1>), dim3(nb_e3), block, 0, c->stream, g, ct, c->ck_ids_e3, c->n_ids_e3, c->cams,
-                                      c->objs, delta, c->chunk_out, c->Wbb, c->Abb);
-        if (nb_bb) hipLaunchKernelGGL((k_slam_linearize_chunks<ESL_JAC_NUMERIC, 0>), dim3(nb_bb), block, 0, c->stream, g, ct, c->ck_ids_bb, c->n_ids_bb, c->cams,
-                                      c->objs, delta, c->chunk_out, c->Wbb, c->Abb);
-        hipLaunchKernelGGL(k_slam_combine<ESL_JAC_NUMERIC>, dim3((N + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kWave * kWavesPerBlock), 0, c->stream, g, ct,
-                           c->chunk_out, c->objs, delta, c->Hoo, c->bo, c->obj_part);
-      }
+      robust_dispatch(c->robust_on, [&](auto robust) {
+        constexpr bool R = decltype(robust)::value;
+        if (an) {
+          if (nb_e3) hipLaunchKernelGGL((k_slam_linearize_chunks<ESL_JAC_ANALYTIC, 1, R>), dim3(nb_e3), block, 0, c->stream, g, ct, c->ck_ids_e3, c->n_ids_e3, c->cams,
+                                        c->objs, delta, c->chunk_out, c->Wbb, c->Abb);
+          if (nb_bb) hipLaunchKernelGGL((k_slam_linearize_chunks<ESL_JAC_ANALYTIC, 0, R>), dim3(nb_bb), block, 0, c->stream, g, ct, c->ck_ids_bb, c->n_ids_bb, c->cams,
+                                        c->objs, delta, c->chunk_out, c->Wbb, c->Abb);
+          hipLaunchKernelGGL((k_slam_combine<ESL_JAC_ANALYTIC, R>), dim3((N + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kWave * kWavesPerBlock), 0, c->stream, g, ct,
+                             c->chunk_out, c->objs, delta, c->Hoo, c->bo, c->obj_part);
+        } else {
+          if (nb_e3) hipLaunchKernelGGL((k_slam_linearize_chunks<ESL_JAC_NUMERIC, 1, R>), dim3(nb_e3), block, 0, c->stream, g, ct, c->ck_ids_e3, c->n_ids_e3, c->cams,
+                                        c->objs, delta, c->chunk_out, c->Wbb, c->Abb);
+          if (nb_bb) hipLaunchKernelGGL((k_slam_linearize_chunks<ESL_JAC_NUMERIC, 0, R>), dim3(nb_bb), block, 0, c->stream, g, ct, c->ck_ids_bb, c->n_ids_bb, c->cams,
+                                        c->objs, delta, c->chunk_out, c->Wbb, c->Abb);
+          hipLaunchKernelGGL((k_slam_combine<ESL_JAC_NUMERIC, R>), dim3((N + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kWave * kWavesPerBlock), 0, c->stream, g, ct,
+                             c->chunk_out, c->objs, delta, c->Hoo, c->bo, c->obj_part);
+        }
+      });
     }
     if (g.n_odom) {
       const dim3 grid((g.n_odom + 127) / 128), block(128);
-      if (an) hipLaunchKernelGGL(k_slam_odom<ESL_JAC_ANALYTIC>, grid, block, 0, c->stream, g, c->cams, delta, c->Aod, c->od_part);
-      else hipLaunchKernelGGL(k_slam_odom<ESL_JAC_NUMERIC>, grid, block, 0, c->stream, g, c->cams, delta, c->Aod, c->od_part);
+      robust_dispatch(c->robust_on, [&](auto robust) {
+        constexpr bool R = decltype(robust)::value;
+        if (an) hipLaunchKernelGGL((k_slam_odom<ESL_JAC_ANALYTIC, R>), grid, block, 0, c->stream, g, c->cams, delta, c->Aod, c->od_part);
+        else hipLaunchKernelGGL((k_slam_odom<ESL_JAC_NUMERIC, R>), grid, block, 0, c->stream, g, c->cams, delta, c->Aod, c->od_part);
+      });
     }
     hipLaunchKernelGGL(k_slam_cam_gather, dim3((F + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kWave * kWavesPerBlock), 0, c->stream, g, c->Abb, c->Aod,
                        c->Hcc, c->bc, c->cam_part);
@@ -908,8 +916,10 @@ int slam_try_step(esl_ctx* c, double lambda) {
                        c->cams_trial, c->cam_part);
     const int nb_co = (N + kWavesPerBlock - 1) / kWavesPerBlock, nb_od = (g.n_odom + kWave * kWavesPerBlock - 1) / (kWave * kWavesPerBlock);
     if (nb_co + nb_od > 0)
-      hipLaunchKernelGGL(k_slam_chi2_all, dim3((unsigned)(nb_co + nb_od)), dim3(kWave * kWavesPerBlock), 0, c->stream, g, nb_co, c->cams_trial, c->objs_trial,
-                         c->obj_part, c->od_part);
+      robust_dispatch(c->robust_on, [&](auto robust) {
+        hipLaunchKernelGGL(k_slam_chi2_all<decltype(robust)::value>, dim3((unsigned)(nb_co + nb_od)), dim3(kWave * kWavesPerBlock), 0, c->stream, g, nb_co,
+                           c->cams_trial, c->objs_trial, c->obj_part, c->od_part);
+      });
   }
   ESL_HIP_TRY(hipGetLastError());
   }

@@ -22,7 +22,7 @@ EXPORTS = [
     "esl_abi_version", "esl_last_error", "esl_device_count", "esl_ctx_create", "esl_ctx_destroy",
     "esl_ctx_synchronize", "esl_ctx_trim", "esl_lm_params_default", "esl_optimize", "esl_graph_upload", "esl_graph_append", "esl_graph_sizes", "esl_states_upload",
     "esl_states_download", "esl_optimize_resident", "esl_states_snapshot", "esl_states_restore", "esl_profile_enable", "esl_profile_get", "esl_lm_begin", "esl_lm_linearize", "esl_lm_reduced_system", "esl_lm_reduced_residual",
-    "esl_lm_try_step", "esl_lm_commit", "esl_lm_solver_used", "esl_lm_solver_stats", "esl_lm_download", "esl_comm_unique_id", "esl_comm_init", "esl_comm_init_host", "esl_comm_set_replicated", "esl_comm_destroy", "esl_partition_objects", "esl_fit_params_default", "esl_fit_frame", "esl_fit_frame_debug", "esl_fit_frame_ex", "esl_selftest_cholesky", "esl_debug_chol_plan",
+    "esl_lm_try_step", "esl_lm_commit", "esl_lm_solver_used", "esl_lm_solver_stats", "esl_lm_download", "esl_lm_set_robust", "esl_edge_chi2", "esl_comm_unique_id", "esl_comm_init", "esl_comm_init_host", "esl_comm_set_replicated", "esl_comm_destroy", "esl_partition_objects", "esl_fit_params_default", "esl_fit_frame", "esl_fit_frame_debug", "esl_fit_frame_ex", "esl_selftest_cholesky", "esl_debug_chol_plan",
     "esl_init_quadric", "esl_init_from_qstar", "esl_init_plane_error", "esl_plane_params_default", "esl_extract_ground_plane", "esl_extract_planes",
 ]
 
@@ -66,6 +66,10 @@ def device_count():
 _dp = C.POINTER(C.c_double)
 
 
+def _edge_counts(graph):
+    return [len(graph.bbox_cam), len(graph.e3d_cam), len(graph.grav_obj), len(graph.odom_i)]
+
+
 class Context:
     """One HIP device + stream + device-resident graph/states (esl_ctx)."""
 
@@ -75,6 +79,7 @@ class Context:
         self.device = int(device)
         _check(L.esl_ctx_create(C.c_int(device), C.byref(self._h)), "esl_ctx_create")
         self._graph = None
+        self._edge_counts = [0, 0, 0, 0]   # bbox, 3-D, gravity, odometry edges of the resident graph (esl_edge_chi2)
 
     def close(self):
         if self._h:
@@ -94,6 +99,7 @@ class Context:
         cams = np.array(cams, dtype=np.float64, order="C").reshape(-1, 7).copy()
         objs = np.array(objs, dtype=np.float64, order="C").reshape(-1, 10).copy()
         rep = abi.EslLmReport()
+        self._edge_counts = _edge_counts(graph)
         _check(load().esl_optimize(self._h, C.byref(g), cams.ctypes.data_as(_dp), objs.ctypes.data_as(_dp),
                                    C.byref(p), C.byref(rep)), "esl_optimize")
         return cams, objs, rep.as_dict()
@@ -103,6 +109,7 @@ class Context:
         self._graph = graph
         g = graph.c_struct()
         _check(load().esl_graph_upload(self._h, C.byref(g)), "esl_graph_upload")
+        self._edge_counts = _edge_counts(graph)
 
     def append_graph(self, new_cams=(), new_objs=(), bbox=None, e3d=None, grav_obj=(), new_cam_fixed=None, odom=None):
         """esl_graph_append: bbox = (cam, obj, meas (n,4), weight), e3d = (cam, obj, meas (n,10), weight); indices in the extended
@@ -142,6 +149,7 @@ class Context:
             if len(odom) > 3 and odom[3] is not None:
                 d.odom_info = arr(odom[3], np.float64, (6,)).ctypes.data_as(_dp)
         _check(load().esl_graph_append(self._h, C.byref(d)), "esl_graph_append")
+        self._edge_counts = [a + b for a, b in zip(self._edge_counts, (d.n_bbox, d.n_e3d, d.n_grav, d.n_odom))]
         if self._graph is not None:
             self._graph = _Sizes(self._graph.n_cams + d.n_new_cams, self._graph.n_objs + d.n_new_objs)
 
@@ -211,6 +219,22 @@ class Context:
         r = C.c_double(0)
         _check(load().esl_lm_reduced_residual(self._h, C.byref(r)), "esl_lm_reduced_residual")
         return r.value
+
+    def set_robust(self, bbox=None, e3d=None, grav=None, odom=None):
+        """esl_lm_set_robust: each argument None (no kernel) or (kind name, delta), e.g. bbox=("huber", 1.0); kinds: none, huber,
+        pseudo_huber, cauchy, tukey.  The setting stays with the context and applies from the next run on."""
+        p = abi.default_robust_params(bbox=bbox, e3d=e3d, grav=grav, odom=odom)
+        _check(load().esl_lm_set_robust(self._h, C.byref(p)), "esl_lm_set_robust")
+
+    def edge_chi2(self, edge_class):
+        """esl_edge_chi2: (raw chi2, robust weight rho1) of every edge of one class ("bbox", "e3d", "grav", "odom" or its number) at the
+        resident states, in caller order (upload order, then append order)."""
+        cls = abi.EDGE_CLASSES[edge_class] if isinstance(edge_class, str) else int(edge_class)
+        n = self._edge_counts[cls]
+        chi, w = np.zeros(n), np.zeros(n)
+        _check(load().esl_edge_chi2(self._h, C.c_int32(cls), chi.ctypes.data_as(_dp), w.ctypes.data_as(_dp), C.c_int64(n)),
+               "esl_edge_chi2")
+        return chi, w
 
     def lm_download(self, which, count):
         out = np.zeros(int(count))
