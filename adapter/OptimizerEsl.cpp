@@ -188,6 +188,8 @@ void Optimizer::GlobalObjectGraphOptimization(std::vector<Frame*>& pFrames, Map*
   };
   robust_key("2D", ESL_EDGE_BBOX);
   robust_key("3DEllipsoid", ESL_EDGE_E3D);
+  const bool localize = Config::Get<int>("Optimizer.Localization") == 1;
+  const std::vector<uint8_t> obj_fixed(localize ? (size_t)g.n_objs : 0, 1);
   esl_lm_report rep;
   int n_down = -1;   // bbox edges with weight < 1 after the optimisation (only counted with a 2D kernel set)
   {
@@ -198,7 +200,12 @@ void Optimizer::GlobalObjectGraphOptimization(std::vector<Frame*>& pFrames, Map*
       std::cerr << "esl_lm_set_robust: " << esl_last_error() << std::endl;
       return;
     }
-    if (esl_optimize(ctx, &g, f.cams.data(), f.objs.data(), &p, &rep) != ESL_OK) {
+    // Optimizer.Localization = 1: vEllipsoid->setFixed(true) on every ellipsoid (the reference hard-wires false, Optimizer.cpp:178).
+    // With Optimizer.SLAMMode = 1 this is a pose-only refinement of the trajectory against the map; the ellipsoids are written
+    // back unchanged.  A missing key reads 0: the shipped behaviour.
+    const int rc_opt = localize ? esl_optimize_fixed(ctx, &g, obj_fixed.data(), f.cams.data(), f.objs.data(), &p, &rep)
+                                : esl_optimize(ctx, &g, f.cams.data(), f.objs.data(), &p, &rep);
+    if (rc_opt != ESL_OK) {
       std::cerr << "esl_optimize: " << esl_last_error() << std::endl;  // the reference never throws here
       return;
     }

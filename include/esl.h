@@ -47,7 +47,8 @@ extern "C" {
                              * 5: esl_lm_params::e3d_half_turn (1 = the yaw-hypothesis minimum exactly as Ellipsoid.cpp:92-117 writes it),
                              *    esl_plane_params::max_curvature (PCL's maximum_curvature_ model test; min_inliers is a strict >);
                              *    additive part of 5: robust kernels per edge class (esl_robust_params, esl_lm_set_robust, esl_edge_chi2) --
-                             *    detect them by the symbol */
+                             *    detect them by the symbol; likewise fixed ellipsoids (esl_graph_upload_fixed, esl_optimize_fixed,
+                             *    esl_graph_obj_fixed) with ESL_SOLVER_CAMERA_CHAIN */
 #define ESL_MAX_TRACE 32
 
 typedef enum {
@@ -129,7 +130,15 @@ typedef enum {
    * separator cameras' rows: C4 3.3e12 flops; esl_lm_solver_stats reports the shape).  Needs every odometry edge to join two free
    * cameras that are neighbours in free-camera order, and either one GPU or the replicated-graph communicator
    * (esl_comm_set_replicated); ESL_ERR_INVALID otherwise. */
-  ESL_SOLVER_REDUCED_ELLIPSOID = 2
+  ESL_SOLVER_REDUCED_ELLIPSOID = 2,
+  /* The camera chain alone (additive part of ABI 5, with esl_graph_upload_fixed): no active edge joins a free camera to a free
+   * ellipsoid (W is structurally empty -- localisation against a fixed map), and the odometry edges satisfy the chain condition
+   * ESL_SOLVER_REDUCED_ELLIPSOID already requires.  (Hcc + lambda I + odometry blocks) x_c = b_c is then block tridiagonal (block
+   * diagonal without odometry) and is solved as such, by cyclic reduction over 6 x 6 blocks -- no dense matrix is formed; free
+   * ellipsoids, which can then only hang on fixed cameras, keep their 9 x 9 solves.  ESL_ERR_INVALID when requested on a graph that
+   * does not qualify or on a context with a communicator.  ESL_SOLVER_AUTO picks it when it applies AND the graph was uploaded
+   * with at least one obj_fixed flag set; requested explicitly it runs on any qualifying graph. */
+  ESL_SOLVER_CAMERA_CHAIN = 3
 } esl_linear_solver;
 
 typedef enum {
@@ -222,6 +231,27 @@ int esl_optimize(esl_ctx* ctx, const esl_graph* g, double* cams_io /* n_cams x 7
 
 /* ---- resident / step API (graph + states stay in HBM; used by bench and by the sharded driver) --*/
 int esl_graph_upload(esl_ctx* ctx, const esl_graph* g);
+/* ---- fixed ellipsoids (g2o's setFixed on a VertexEllipsoid, Optimizer.cpp:178; additive part of ABI 5: detect by the symbol) -----
+ * esl_graph_upload with per-ellipsoid flags (n_objs bytes, any non-zero value = fixed; NULL or all zeros = esl_graph_upload).  With
+ * obj_fixed[o] set: (1) the state of ellipsoid o never changes -- esl_states_download returns it bit for bit as uploaded; (2) an
+ * edge all of whose vertices are fixed is INACTIVE (sparse_optimizer.cpp allVerticesFixed): a bbox or 3-D edge between o and a fixed
+ * camera and every gravity prior on o are not linearised and are part of no chi2, of lambda_0 and of n_bbox_valid / n_bbox_dropped
+ * (which count the active bbox edges); with all cameras fixed o drops out entirely, and a run without any active edge ends with
+ * stop_reason 3; (3) an edge between o and a FREE camera is active and camera-only: its chi2 counts (through the robust kernel of
+ * its class), its Jacobian is taken wrt the camera alone (numeric or analytic per jacobian_mode), it adds Jc^T Omega Jc to H_cc and
+ * -Jc^T Omega r to b_c; the NaN pre-check and the visibility test apply to it.  Everything else is untouched.
+ * All ellipsoids fixed + free cameras = pose-only optimisation against a finished map (localisation); see ESL_SOLVER_CAMERA_CHAIN.
+ * A plain esl_graph_upload clears the flags; they survive esl_states_upload, snapshot / restore and esl_ctx_trim.  The step API and
+ * esl_lm_download work on a flagged graph (H_oo, b_o, x_o of a fixed ellipsoid read as zeros, H_cc / b_c include the camera-only
+ * edges); esl_lm_download(which = 9) returns ESL_ERR_STATE on a flagged graph.  esl_edge_chi2 keeps reporting EVERY edge of the
+ * caller's graph in caller order: camera-only edges with their raw chi2 and rho1, inactive edges with their raw chi2 at the resident
+ * states and weight 0.  ESL_ERR_STATE: esl_graph_append on a graph with a flag set; a flag set on a context with a communicator. */
+int esl_graph_upload_fixed(esl_ctx* ctx, const esl_graph* g, const uint8_t* obj_fixed);
+/* one-shot: esl_optimize with the flags */
+int esl_optimize_fixed(esl_ctx* ctx, const esl_graph* g, const uint8_t* obj_fixed, double* cams_io, double* objs_io,
+                       const esl_lm_params* p, esl_lm_report* out);
+/* the flags of the resident graph (count = n_objs bytes out, 0 / 1; all zero after a plain esl_graph_upload) */
+int esl_graph_obj_fixed(esl_ctx* ctx, uint8_t* flags_out, int32_t count);
 int esl_states_upload(esl_ctx* ctx, const double* cams, const double* objs);
 int esl_states_download(esl_ctx* ctx, double* cams, double* objs);
 int esl_optimize_resident(esl_ctx* ctx, const esl_lm_params* p, esl_lm_report* out);
@@ -292,8 +322,8 @@ int esl_lm_reduced_residual(esl_ctx* ctx, double* rel_residual_out);
 int esl_lm_try_step(esl_ctx* ctx, double lambda, esl_lm_partials* out);
 /* accept != 0: discard backup; accept == 0: restore states from backup */
 int esl_lm_commit(esl_ctx* ctx, int accept);
-/* which esl_linear_solver the last SLAM-mode trial step of this context ran with (ESL_SOLVER_REDUCED_CAMERA or
- * ESL_SOLVER_REDUCED_ELLIPSOID: what ESL_SOLVER_AUTO resolved to); 0 before any SLAM-mode step */
+/* which esl_linear_solver the last SLAM-mode trial step of this context ran with (ESL_SOLVER_REDUCED_CAMERA,
+ * ESL_SOLVER_REDUCED_ELLIPSOID or ESL_SOLVER_CAMERA_CHAIN: what ESL_SOLVER_AUTO resolved to); 0 before any SLAM-mode step */
 int esl_lm_solver_used(esl_ctx* ctx, int32_t* solver_out);
 /* shape of the camera-first elimination of the resident graph as the last trial step ran it (zeros when it did not):
  * stats[0] form of X: 0 dense rows, 1 sparse with stored per-segment products, 2 sparse, blocks of T straight from the slabs;

@@ -111,7 +111,7 @@ def default_plane_params(**kw):
     return p
 
 
-SOLVER_AUTO, SOLVER_REDUCED_CAMERA, SOLVER_REDUCED_ELLIPSOID = 0, 1, 2   # esl_linear_solver (include/esl.h)
+SOLVER_AUTO, SOLVER_REDUCED_CAMERA, SOLVER_REDUCED_ELLIPSOID, SOLVER_CAMERA_CHAIN = 0, 1, 2, 3   # esl_linear_solver (include/esl.h)
 
 ROBUST_KINDS = {"none": 0, "huber": 1, "pseudo_huber": 2, "cauchy": 3, "tukey": 4}   # esl_robust_kind (include/esl.h)
 EDGE_CLASSES = {"bbox": 0, "e3d": 1, "grav": 2, "odom": 3}                         # esl_edge_class

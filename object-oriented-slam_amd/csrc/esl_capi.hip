@@ -20,6 +20,7 @@
 #include "esl_kernels_map.hpp"
 #include "esl_kernels_chunk.hpp"
 #include "esl_slam.hpp"
+#include "esl_fixed.hpp"
 
 namespace esl {
 static thread_local std::string g_err;
@@ -275,6 +276,8 @@ int esl_ctx_destroy(esl_ctx* c) {
   if (c->append_dev) (void)hipFree(c->append_dev);
   if (c->slam_tab_dev) (void)hipFree(c->slam_tab_dev);
   if (c->eq_buf) (void)hipFree(c->eq_buf);
+  if (c->fx_blob) (void)hipFree(c->fx_blob);
+  if (c->chain_ws) (void)hipFree(c->chain_ws);
   fit_release(c);
   plane_release(c);
   for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
@@ -375,8 +378,23 @@ static void csr_by_key(const int32_t* key, int n, int n_keys, std::vector<int>& 
   csr_by_key(key, n, n_keys, start.data(), perm.data(), pos);
 }
 
+// the flags of esl_graph_upload_fixed go away with the graph they belong to (the blob stays: grow-only)
+static void fx_clear(esl_ctx* c) {
+  c->fx_on = false;
+  c->fx_flags.clear(); c->fx_bb_map.clear(); c->fx_e3_map.clear(); c->fx_grav_obj.clear();
+  c->fx = AnchGraph{};
+  c->fx_A = c->fx_chi = nullptr;
+}
+// extra_touched (n_cams flags or null): cameras that have an active edge outside g -- the anchored edges of esl_graph_upload_fixed
+static int graph_upload_impl(esl_ctx* c, const esl_graph* g, const uint8_t* extra_touched);
 int esl_graph_upload(esl_ctx* c, const esl_graph* g) {
   if (!c) return ESL_ERR_INVALID;
+  const int rc = validate_graph(g);
+  if (rc) return rc;
+  fx_clear(c);
+  return graph_upload_impl(c, g, nullptr);
+}
+static int graph_upload_impl(esl_ctx* c, const esl_graph* g, const uint8_t* extra_touched) {
   const bool host_timing = std::getenv("ESL_UPLOAD_HOST_TIMING") != nullptr;   // diagnostic: where the host call's time goes
   auto now_us = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double ht[16]; int nht = 0;
@@ -519,6 +537,8 @@ int esl_graph_upload(esl_ctx* c, const esl_graph* g) {
     for (int i = 0; i < g->n_e3d; ++i) touched[g->e3d_cam[i]] = 1;
     for (int i = 0; i < g->n_odom; ++i)
       if (!(fixed[g->odom_i[i]] && fixed[g->odom_j[i]])) { touched[g->odom_i[i]] = 1; touched[g->odom_j[i]] = 1; }
+    if (extra_touched)
+      for (int i = 0; i < F; ++i) if (extra_touched[i]) touched[i] = 1;
     for (int i = 0; i < F; ++i)
       if (!fixed[i] && touched[i]) slot[i] = nf++;
     d.n_free_cams = nf;
@@ -569,6 +589,116 @@ int esl_graph_upload(esl_ctx* c, const esl_graph* g) {
     std::fprintf(stderr, "  (validate, sort, gather, camera lists, chunks, cameras, commit, wait)\n");
   }
   c->graph_loaded = true;
+  return ESL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// esl_graph_upload_fixed: g2o's setFixed on ellipsoid vertices.  The caller's edges are split on the host: edges of free
+// ellipsoids form an ordinary graph (same ellipsoid numbering; a fixed ellipsoid is an ellipsoid without edges, its state is
+// copied through by every kernel that writes trial states), anchored edges (fixed ellipsoid, free camera) and inactive edges
+// (fixed ellipsoid, fixed camera; every gravity prior of a fixed ellipsoid) go into the arrays of esl_fixed.hpp.
+// ---------------------------------------------------------------------------------------------------
+int esl_graph_upload_fixed(esl_ctx* c, const esl_graph* g, const uint8_t* obj_fixed) {
+  if (!c) return ESL_ERR_INVALID;
+  int rc = validate_graph(g);
+  if (rc) return rc;
+  bool any = false;
+  if (obj_fixed) for (int o = 0; o < g->n_objs; ++o) any = any || obj_fixed[o] != 0;
+  if (!any) return esl_graph_upload(c, g);
+  if (c->comm) { set_error("esl_graph_upload_fixed: fixed ellipsoids are not supported on a context with a communicator"); return ESL_ERR_STATE; }
+  ESL_HIP_TRY(hipSetDevice(c->device));
+  const int N = g->n_objs, F = g->n_cams;
+  std::vector<uint8_t> fixed((size_t)N);
+  for (int o = 0; o < N; ++o) fixed[o] = obj_fixed[o] ? 1 : 0;
+  auto cam_free = [&](int i) { return g->cam_fixed && !g->cam_fixed[i]; };
+  // (a) the graph of the free ellipsoids, caller order kept
+  std::vector<int32_t> s_bc, s_bo, s_ec, s_eo, s_go;
+  std::vector<double> s_bm, s_bw, s_em, s_ew;
+  std::vector<int> bb_map((size_t)g->n_bbox), e3_map((size_t)g->n_e3d);
+  std::vector<int> an_bb, in_bb, an_e3, in_e3;   // caller indices of (b) and (c)
+  std::vector<uint8_t> touched((size_t)F, 0);
+  for (int i = 0; i < g->n_bbox; ++i) {
+    if (!fixed[g->bbox_obj[i]]) {
+      bb_map[i] = (int)s_bc.size();
+      s_bc.push_back(g->bbox_cam[i]); s_bo.push_back(g->bbox_obj[i]); s_bw.push_back(g->bbox_weight[i]);
+      s_bm.insert(s_bm.end(), g->bbox_meas + (size_t)4 * i, g->bbox_meas + (size_t)4 * i + 4);
+    } else if (cam_free(g->bbox_cam[i])) { an_bb.push_back(i); touched[g->bbox_cam[i]] = 1; }
+    else in_bb.push_back(i);
+  }
+  for (int i = 0; i < g->n_e3d; ++i) {
+    if (!fixed[g->e3d_obj[i]]) {
+      e3_map[i] = (int)s_ec.size();
+      s_ec.push_back(g->e3d_cam[i]); s_eo.push_back(g->e3d_obj[i]); s_ew.push_back(g->e3d_weight[i]);
+      s_em.insert(s_em.end(), g->e3d_meas + (size_t)10 * i, g->e3d_meas + (size_t)10 * i + 10);
+    } else if (cam_free(g->e3d_cam[i])) { an_e3.push_back(i); touched[g->e3d_cam[i]] = 1; }
+    else in_e3.push_back(i);
+  }
+  for (int i = 0; i < g->n_grav; ++i) if (!fixed[g->grav_obj[i]]) s_go.push_back(g->grav_obj[i]);
+  esl_graph sub = *g;
+  sub.n_bbox = (int32_t)s_bc.size(); sub.bbox_cam = s_bc.data(); sub.bbox_obj = s_bo.data(); sub.bbox_meas = s_bm.data(); sub.bbox_weight = s_bw.data();
+  sub.n_e3d = (int32_t)s_ec.size(); sub.e3d_cam = s_ec.data(); sub.e3d_obj = s_eo.data(); sub.e3d_meas = s_em.data(); sub.e3d_weight = s_ew.data();
+  sub.n_grav = (int32_t)s_go.size(); sub.grav_obj = s_go.data();
+  fx_clear(c);
+  if ((rc = graph_upload_impl(c, &sub, touched.data()))) return rc;
+  // (b) sorted by camera (= by camera slot: slots ascend with the camera index), stable; (c) behind them
+  auto by_cam = [&](std::vector<int>& v, const int32_t* cam) { std::stable_sort(v.begin(), v.end(), [&](int x, int y) { return cam[x] < cam[y]; }); };
+  by_cam(an_bb, g->bbox_cam); by_cam(an_e3, g->e3d_cam);
+  const int nf = c->g.n_free_cams;
+  const size_t nab = an_bb.size(), nae = an_e3.size(), nb = nab + in_bb.size(), ne = nae + in_e3.size();
+  // one blob: index arrays, measurements, flags, the per-slot lists, then the records
+  auto al = [](size_t x) { return (x + 255) / 256 * 256; };
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = al(off + std::max<size_t>(bytes, 8)); return o; };
+  const size_t o_bc = take(nb * 4), o_bo = take(nb * 4), o_bm = take(nb * 32), o_bw = take(nb * 8), o_bv = take(nb);
+  const size_t o_ec = take(ne * 4), o_eo = take(ne * 4), o_em = take(ne * 80), o_ew = take(ne * 8);
+  const size_t o_bs = take(((size_t)nf + 1) * 4), o_es = take(((size_t)nf + 1) * 4);
+  const size_t up_end = off;
+  const size_t o_A = take((nab + nae) * kARec * 8), o_chi = take((nab + nae) * 8);
+  if (off > c->fx_blob_cap) {
+    if (c->fx_blob) { (void)hipFree(c->fx_blob); c->fx_blob = nullptr; c->fx_blob_cap = 0; }
+    ESL_HIP_TRY(hipMalloc((void**)&c->fx_blob, off + off / 8));
+    c->fx_blob_cap = off + off / 8;
+  }
+  std::vector<char> h(up_end, 0);
+  int* bc_ = (int*)(h.data() + o_bc); int* bo_ = (int*)(h.data() + o_bo); double* bm_ = (double*)(h.data() + o_bm); double* bw_ = (double*)(h.data() + o_bw);
+  int* ec_ = (int*)(h.data() + o_ec); int* eo_ = (int*)(h.data() + o_eo); double* em_ = (double*)(h.data() + o_em); double* ew_ = (double*)(h.data() + o_ew);
+  int* bs_ = (int*)(h.data() + o_bs); int* es_ = (int*)(h.data() + o_es);
+  std::memset(h.data() + o_bv, 1, nb);
+  for (size_t k = 0; k < nb; ++k) {
+    const int i = k < nab ? an_bb[k] : in_bb[k - nab];
+    bc_[k] = g->bbox_cam[i]; bo_[k] = g->bbox_obj[i]; bw_[k] = g->bbox_weight[i];
+    std::memcpy(bm_ + 4 * k, g->bbox_meas + (size_t)4 * i, 4 * sizeof(double));
+    bb_map[i] = -((int)k + 1);
+    if (k < nab) ++bs_[c->h_cam_slot[bc_[k]] + 1];
+  }
+  for (size_t k = 0; k < ne; ++k) {
+    const int i = k < nae ? an_e3[k] : in_e3[k - nae];
+    ec_[k] = g->e3d_cam[i]; eo_[k] = g->e3d_obj[i]; ew_[k] = g->e3d_weight[i];
+    std::memcpy(em_ + 10 * k, g->e3d_meas + (size_t)10 * i, 10 * sizeof(double));
+    e3_map[i] = -((int)k + 1);
+    if (k < nae) ++es_[c->h_cam_slot[ec_[k]] + 1];
+  }
+  for (int sl = 0; sl < nf; ++sl) { bs_[sl + 1] += bs_[sl]; es_[sl + 1] += es_[sl]; }
+  ESL_HIP_TRY(hipMemcpy(c->fx_blob, h.data(), up_end, hipMemcpyHostToDevice));
+  AnchGraph& a = c->fx;
+  char* d = c->fx_blob;
+  a.n_bb = (int)nab; a.n_e3 = (int)nae; a.n_bb_all = (int)nb; a.n_e3_all = (int)ne;
+  a.bb_cam = (int*)(d + o_bc); a.bb_obj = (int*)(d + o_bo); a.bb_meas = (double*)(d + o_bm); a.bb_w = (double*)(d + o_bw); a.bb_valid = (unsigned char*)(d + o_bv);
+  a.e3_cam = (int*)(d + o_ec); a.e3_obj = (int*)(d + o_eo); a.e3_meas = (double*)(d + o_em); a.e3_w = (double*)(d + o_ew);
+  a.bb_start = (int*)(d + o_bs); a.e3_start = (int*)(d + o_es);
+  c->fx_A = (double*)(d + o_A); c->fx_chi = (double*)(d + o_chi);
+  c->fx_flags = fixed;
+  c->fx_bb_map = bb_map; c->fx_e3_map = e3_map;
+  c->fx_grav_obj.assign(g->grav_obj, g->grav_obj + g->n_grav);
+  c->fx_on = true;
+  return ESL_OK;
+}
+
+int esl_graph_obj_fixed(esl_ctx* c, uint8_t* flags_out, int32_t count) {
+  if (!c || !flags_out) return ESL_ERR_INVALID;
+  if (!c->graph_loaded) { set_error("esl_graph_obj_fixed: no graph loaded"); return ESL_ERR_STATE; }
+  if (count != c->g.n_objs) { set_error("esl_graph_obj_fixed: count is not the graph's ellipsoid count"); return ESL_ERR_INVALID; }
+  for (int o = 0; o < count; ++o) flags_out[o] = c->fx_on ? c->fx_flags[(size_t)o] : 0;
   return ESL_OK;
 }
 
@@ -852,6 +982,7 @@ int esl_graph_sizes(esl_ctx* c, int32_t* n_cams, int32_t* n_objs, int32_t* n_bbo
 }
 
 int esl_graph_append(esl_ctx* c, const esl_graph_delta* dl) {
+  if (c && c->fx_on) { set_error("esl_graph_append: the resident graph has fixed ellipsoids (esl_graph_upload_fixed); upload the extended graph instead"); return ESL_ERR_STATE; }
   if (!c || !dl) return ESL_ERR_INVALID;
   if (!c->graph_loaded || !c->states_loaded) { set_error("esl_graph_append: upload a graph and its states first"); return ESL_ERR_STATE; }
   if (c->comm) { set_error("esl_graph_append: one GPU only (no communicator)"); return ESL_ERR_STATE; }
@@ -1248,6 +1379,22 @@ int esl_lm_begin(esl_ctx* c, const esl_lm_params* p, int32_t* n_valid, int32_t* 
     ESL_HIP_TRY(hipMemsetAsync(c->chol_info + 2, 0, sizeof(int), c->stream));
     ESL_HIP_TRY(hipStreamSynchronize(c->stream));
   }
+  if (c->fx_on && c->fx.n_bb) {   // the anchored bbox edges are active edges: same pre-check, same counters
+    int adrop = 0;
+    if (p->drop_nan_bbox || c->g.check_vis) {
+      int* cnt = c->chol_info + 3;
+      ESL_HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(int), c->stream));
+      hipLaunchKernelGGL(k_anch_validate, dim3((c->fx.n_bb + 255) / 256), dim3(256), 0, c->stream, c->g, c->fx, c->cams, c->objs, cnt);
+      ESL_HIP_TRY(hipGetLastError());
+      ESL_HIP_TRY(hipMemcpyAsync(&adrop, cnt, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      ESL_HIP_TRY(hipStreamSynchronize(c->stream));
+    } else {
+      ESL_HIP_TRY(hipMemsetAsync(c->fx.bb_valid, 1, (size_t)c->fx.n_bb, c->stream));
+    }
+    if (n_valid) *n_valid = c->g.n_bbox_edges + c->fx.n_bb - dropped - adrop;
+    if (n_dropped) *n_dropped = dropped + adrop;
+    return ESL_OK;
+  }
   if (n_valid) *n_valid = c->g.n_bbox_edges - dropped;
   if (n_dropped) *n_dropped = dropped;
   return ESL_OK;
@@ -1456,7 +1603,8 @@ static int optimize_mapping_device(esl_ctx* c, const esl_lm_params* p, esl_lm_re
 
 int esl_optimize_resident(esl_ctx* c, const esl_lm_params* p, esl_lm_report* out) {
   if (!c || !p || !out) return ESL_ERR_INVALID;
-  if (p->linear_solver != ESL_SOLVER_AUTO && p->linear_solver != ESL_SOLVER_REDUCED_CAMERA && p->linear_solver != ESL_SOLVER_REDUCED_ELLIPSOID) {
+  if (p->linear_solver != ESL_SOLVER_AUTO && p->linear_solver != ESL_SOLVER_REDUCED_CAMERA && p->linear_solver != ESL_SOLVER_REDUCED_ELLIPSOID &&
+      p->linear_solver != ESL_SOLVER_CAMERA_CHAIN) {
     set_error("esl_lm_params::linear_solver: unknown solver"); return ESL_ERR_INVALID;
   }
   if (p->bbox_residual != ESL_BBOX_REPROJECTION && p->bbox_residual != ESL_BBOX_TANGENCY) { set_error("esl_lm_params::bbox_residual: unknown mode"); return ESL_ERR_INVALID; }
@@ -1474,7 +1622,7 @@ int esl_optimize_resident(esl_ctx* c, const esl_lm_params* p, esl_lm_report* out
   out->n_bbox_valid = nv;
   out->n_bbox_dropped = nd;
   const DevGraph& g = c->g;
-  const bool any_edge = (nv > 0) || g.n_e3d > 0 || (g.n_odom > 0 && g.n_free_cams > 0);
+  const bool any_edge = (nv > 0) || g.n_e3d > 0 || (g.n_odom > 0 && g.n_free_cams > 0) || (c->fx_on && c->fx.n_e3 > 0);
   bool any_grav = false;
   if (!any_edge) {  // gravity edges alone also make a graph
     std::vector<int> cnt((size_t)std::max(g.n_objs, 1));
@@ -1549,6 +1697,16 @@ int esl_optimize(esl_ctx* c, const esl_graph* g, double* cams_io, double* objs_i
   return esl_states_download(c, cams_io, objs_io);
 }
 
+int esl_optimize_fixed(esl_ctx* c, const esl_graph* g, const uint8_t* obj_fixed, double* cams_io, double* objs_io, const esl_lm_params* p,
+                       esl_lm_report* out) {
+  if (!c || !g || !p || !out) return ESL_ERR_INVALID;
+  int rc;
+  if ((rc = esl_graph_upload_fixed(c, g, obj_fixed))) return rc;
+  if ((rc = esl_states_upload(c, cams_io, objs_io))) return rc;
+  if ((rc = esl_optimize_resident(c, p, out))) return rc;
+  return esl_states_download(c, cams_io, objs_io);
+}
+
 int esl_states_snapshot(esl_ctx* c) {
   if (!c || !c->states_loaded) { set_error("esl_states_snapshot: no states"); return ESL_ERR_STATE; }
   ESL_HIP_TRY(hipSetDevice(c->device));
@@ -1608,9 +1766,56 @@ int esl_lm_set_robust(esl_ctx* c, const esl_robust_params* p) {
   return ESL_OK;
 }
 
+static int edge_chi2_plain(esl_ctx* c, int32_t edge_class, double* chi2, double* weight, int64_t count);
+// flagged graph: the free ellipsoids' edges from the ordinary path, the fixed ellipsoids' from k_anch_edge_chi2, merged in caller order
+static int edge_chi2_fixed(esl_ctx* c, int32_t edge_class, double* chi2, double* weight, int64_t count) {
+  const bool grav = edge_class == ESL_EDGE_GRAVITY;
+  const std::vector<int>& map = edge_class == ESL_EDGE_BBOX ? c->fx_bb_map : c->fx_e3_map;
+  const int64_t n_caller = grav ? (int64_t)c->fx_grav_obj.size() : (int64_t)map.size();
+  if (count != n_caller) { set_error("esl_edge_chi2: count is not the class's edge count"); return ESL_ERR_INVALID; }
+  if (count == 0) return ESL_OK;
+  const size_t n_sub = grav ? c->h_grav_obj.size() : edge_class == ESL_EDGE_BBOX ? c->h_bb_slot_of.size() : c->h_e3_slot_of.size();
+  std::vector<double> sc(n_sub), sw(n_sub);
+  int rc = edge_chi2_plain(c, edge_class, sc.data(), sw.data(), (int64_t)n_sub);
+  if (rc) return rc;
+  DevGraph g = c->g;
+  for (int k = 0; k < ESL_EDGE_CLASSES; ++k) { g.rk_kind[k] = c->robust.kind[k]; g.rk_delta[k] = c->robust.kind[k] ? c->robust.delta[k] : 1.0; }
+  const int n_x = grav ? g.n_objs : edge_class == ESL_EDGE_BBOX ? c->fx.n_bb_all : c->fx.n_e3_all;
+  std::vector<double> h((size_t)n_x * 2);
+  if (n_x) {
+    double* d = nullptr;
+    ESL_HIP_TRY(hipMalloc((void**)&d, (size_t)n_x * 2 * sizeof(double)));
+    hipLaunchKernelGGL(k_anch_edge_chi2, dim3((n_x + 255) / 256), dim3(256), 0, c->stream, g, c->fx, (int)edge_class, c->cams, c->objs, d, d + n_x);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    if (e != hipSuccess) { set_error(std::string("esl_edge_chi2: ") + hipGetErrorString(e)); return ESL_ERR_HIP; }
+  }
+  size_t j = 0;
+  for (int64_t i = 0; i < count; ++i) {
+    double cv, wv;
+    if (grav) {
+      const int o = c->fx_grav_obj[(size_t)i];
+      if (c->fx_flags[(size_t)o]) { cv = h[(size_t)o]; wv = 0; }
+      else { cv = sc[j]; wv = sw[j]; ++j; }
+    } else {
+      const int m = map[(size_t)i];
+      if (m >= 0) { cv = sc[(size_t)m]; wv = sw[(size_t)m]; }
+      else { cv = h[(size_t)(-m - 1)]; wv = h[(size_t)n_x + (size_t)(-m - 1)]; }
+    }
+    if (chi2) chi2[i] = cv;
+    if (weight) weight[i] = wv;
+  }
+  return ESL_OK;
+}
 int esl_edge_chi2(esl_ctx* c, int32_t edge_class, double* chi2, double* weight, int64_t count) {
   if (!c || edge_class < 0 || edge_class >= ESL_EDGE_CLASSES || count < 0) return ESL_ERR_INVALID;
   if (!c->graph_loaded || !c->states_loaded) { set_error("esl_edge_chi2: upload graph and states first"); return ESL_ERR_STATE; }
+  if (c->fx_on && edge_class != ESL_EDGE_ODOM) { ESL_HIP_TRY(hipSetDevice(c->device)); return edge_chi2_fixed(c, edge_class, chi2, weight, count); }
+  return edge_chi2_plain(c, edge_class, chi2, weight, count);
+}
+static int edge_chi2_plain(esl_ctx* c, int32_t edge_class, double* chi2, double* weight, int64_t count) {
   DevGraph g = c->g;   // the context's robust setting (the one its runs apply), residual settings of the last run
   for (int k = 0; k < ESL_EDGE_CLASSES; ++k) { g.rk_kind[k] = c->robust.kind[k]; g.rk_delta[k] = c->robust.kind[k] ? c->robust.delta[k] : 1.0; }
   const std::vector<int>* slot_of = edge_class == ESL_EDGE_BBOX ? &c->h_bb_slot_of : edge_class == ESL_EDGE_E3D ? &c->h_e3_slot_of
@@ -1658,7 +1863,9 @@ int esl_lm_download(esl_ctx* c, int32_t which, double* dst, int64_t count) {
     case 6: src = c->S; n = c->S_lda * c->S_n; break;
     case 7: src = c->objs_trial; n = (int64_t)g.n_objs * 10; break;
     case 8: src = c->cams_trial; n = (int64_t)g.n_cams * 7; break;
-    case 9: src = c->lm.slam ? c->Wbb : nullptr; n = ((int64_t)g.n_bbox + g.n_e3d) * 54; break;
+    case 9:
+      if (c->fx_on) { set_error("esl_lm_download: the W records are not available on a graph with fixed ellipsoids"); return ESL_ERR_STATE; }
+      src = c->lm.slam ? c->Wbb : nullptr; n = ((int64_t)g.n_bbox + g.n_e3d) * 54; break;
     default: set_error("esl_lm_download: unknown array"); return ESL_ERR_INVALID;
   }
   if (!src || count < n) { set_error("esl_lm_download: array not available or buffer too small"); return ESL_ERR_INVALID; }

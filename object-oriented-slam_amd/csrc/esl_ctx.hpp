@@ -67,6 +67,15 @@ struct DevGraph {
   int shard_rank = 0;
 };
 
+// edges of FIXED ellipsoids (esl_graph_upload_fixed; kernels: esl_fixed.hpp)
+struct AnchGraph {
+  int n_bb = 0, n_e3 = 0;           // anchored edges: [0, n_bb) / [0, n_e3), sorted by camera slot (stable)
+  int n_bb_all = 0, n_e3_all = 0;   // + the inactive edges behind them
+  int* bb_cam = nullptr; int* bb_obj = nullptr; double* bb_meas = nullptr; double* bb_w = nullptr; unsigned char* bb_valid = nullptr;
+  int* e3_cam = nullptr; int* e3_obj = nullptr; double* e3_meas = nullptr; double* e3_w = nullptr;
+  int* bb_start = nullptr; int* e3_start = nullptr;   // n_free_cams + 1 each: the anchored edges of every camera slot
+};
+
 // robust kernel of edge class `cls` on an edge's raw chi2: chi <- rho0(chi), w <- rho1(chi) w (g2o robustInformation).  The compile-time
 // switch keeps the default instantiations exactly what they were (a run-time flag costs registers and occupancy: esl_kernels_chunk.hpp).
 template <bool ROBUST>
@@ -283,7 +292,20 @@ struct esl_ctx {
   int *cf_rank = nullptr, *cf_unrank = nullptr, *cf_kfirst = nullptr;
   double* cf_xo_t = nullptr;
   double cf_upd_flops = 0;
-  int lm_solver_used = 0;   // esl_linear_solver the last trial step ran with (1 reduced camera system, 2 reduced ellipsoid system)
+  int lm_solver_used = 0;   // esl_linear_solver the last trial step ran with (1 reduced camera system, 2 reduced ellipsoid system, 3 camera chain)
+  // fixed ellipsoids (esl_graph_upload_fixed, esl_fixed.hpp).  fx_on: the resident graph was uploaded with at least one flag set;
+  // everything below is empty / unused otherwise and no kernel of esl_fixed.hpp runs
+  bool fx_on = false;
+  std::vector<uint8_t> fx_flags;            // n_objs flags (0 / 1) of the resident graph
+  esl::AnchGraph fx;                        // device arrays of the anchored + inactive edges (interior pointers of fx_blob)
+  char* fx_blob = nullptr; size_t fx_blob_cap = 0;   // grow-only
+  double* fx_A = nullptr; double* fx_chi = nullptr;  // per anchored edge: the 27-double camera record, chi2
+  // caller order -> where the edge went: >= 0: index in the caller order of the free-ellipsoid graph (h_bb_slot_of ...), < 0: -(k + 1),
+  // k = index in the arrays of fx
+  std::vector<int> fx_bb_map, fx_e3_map;
+  std::vector<int> fx_grav_obj;             // the caller's gravity edges (all of them; h_grav_obj holds those of free ellipsoids)
+  bool chain_ok = false;                    // the odometry edges between free cameras join neighbours only (slam_alloc)
+  double* chain_ws = nullptr; size_t chain_ws_cap = 0;   // ESL_SOLVER_CAMERA_CHAIN: D, L, rhs (two sets) + the blocks' inverses; grow-only
   // per-context runtime of the dense solver (esl_chol.hpp CholRuntime: look-ahead stream + events on THIS device, one-time
   // kernel attributes of this device) and of the Schur kernel; created on first use, released with the context
   void* chol_rt = nullptr;

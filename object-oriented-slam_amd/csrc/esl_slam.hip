@@ -12,6 +12,7 @@
 
 #include "esl_cf.hpp"
 #include "esl_chol.hpp"
+#include "esl_fixed.hpp"
 #include "esl_kernels_slam.hpp"
 
 namespace esl {
@@ -98,7 +99,7 @@ void slam_forget(esl_ctx* c) {
   c->cf_od_start = c->cf_od_edge = nullptr;
   c->S = c->Linv_ws = nullptr;
   cf_forget(c);
-  c->cf_chain_ok = false; c->cf_unavailable = false;
+  c->cf_chain_ok = false; c->cf_unavailable = false; c->chain_ok = false;
   c->h_ue_start.clear(); c->h_ue_id.clear(); c->h_ue_slot.clear();
   c->h_cu_start = c->h_cu_obj = c->h_cu_id = nullptr;
 }
@@ -172,6 +173,7 @@ int slam_alloc(esl_ctx* c) {
     for (auto& p : pe) ode[(size_t)cur[p.first]++] = p.second;   // (edges of one pair stay in ascending e)
   }
   c->cf_chain_ok = chain && nf > 0 && N > 0;
+  c->chain_ok = chain && nf > 0;
   const double t1 = timing ? now_us() : 0;
   // layout: uploads first, then the work buffers
   const size_t EU = (size_t)g.n_bbox + g.n_e3d;
@@ -270,8 +272,12 @@ static bool cf_dist(const esl_ctx* c) {
   return 9L * c->g.n_objs >= 8192;
 }
 // esl_lm_params::linear_solver -> the form this trial runs with; < 0: the request cannot be served
+// ESL_SOLVER_CAMERA_CHAIN: W is structurally empty (no edge of a free ellipsoid at a free camera) and the odometry edges chain
+static bool chain_applicable(const esl_ctx* c) { return c->chain_ok && c->g.n_ue == 0 && !c->comm; }
 static int slam_pick_solver(const esl_ctx* c) {
   const int want = c->lm.p.linear_solver;
+  if (want == ESL_SOLVER_CAMERA_CHAIN) return chain_applicable(c) ? ESL_SOLVER_CAMERA_CHAIN : -2;
+  if (want == ESL_SOLVER_AUTO && c->fx_on && chain_applicable(c)) return ESL_SOLVER_CAMERA_CHAIN;   // (only graphs uploaded with a flag set)
   if (want == ESL_SOLVER_REDUCED_CAMERA) return ESL_SOLVER_REDUCED_CAMERA;
   if (want == ESL_SOLVER_REDUCED_ELLIPSOID) return cf_applicable(c) ? ESL_SOLVER_REDUCED_ELLIPSOID : -1;
   if (!cf_applicable(c) || c->cf_unavailable) return ESL_SOLVER_REDUCED_CAMERA;
@@ -808,6 +814,22 @@ int slam_linearize(esl_ctx* c) {
     }
     hipLaunchKernelGGL(k_slam_cam_gather, dim3((F + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kWave * kWavesPerBlock), 0, c->stream, g, c->Abb, c->Aod,
                        c->Hcc, c->bc, c->cam_part);
+    if (c->fx_on && c->fx.n_bb + c->fx.n_e3 > 0) {   // anchored edges (fixed ellipsoid, free camera): camera records, then their per-camera sums
+      const AnchGraph& a = c->fx;
+      robust_dispatch(c->robust_on, [&](auto robust) {
+        constexpr bool R = decltype(robust)::value;
+        const dim3 gb((a.n_bb + 63) / 64), ge((a.n_e3 + 63) / 64);
+        if (an) {
+          if (a.n_bb) hipLaunchKernelGGL((k_anch_linearize<ESL_JAC_ANALYTIC, 0, R>), gb, dim3(64), 0, c->stream, g, a, c->cams, c->objs, delta, c->fx_A, c->fx_chi);
+          if (a.n_e3) hipLaunchKernelGGL((k_anch_linearize<ESL_JAC_ANALYTIC, 1, R>), ge, dim3(64), 0, c->stream, g, a, c->cams, c->objs, delta, c->fx_A, c->fx_chi);
+        } else {
+          if (a.n_bb) hipLaunchKernelGGL((k_anch_linearize<ESL_JAC_NUMERIC, 0, R>), gb, dim3(64), 0, c->stream, g, a, c->cams, c->objs, delta, c->fx_A, c->fx_chi);
+          if (a.n_e3) hipLaunchKernelGGL((k_anch_linearize<ESL_JAC_NUMERIC, 1, R>), ge, dim3(64), 0, c->stream, g, a, c->cams, c->objs, delta, c->fx_A, c->fx_chi);
+        }
+      });
+      hipLaunchKernelGGL(k_anch_gather, dim3((F + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kWave * kWavesPerBlock), 0, c->stream, g, a, c->fx_A, c->fx_chi,
+                         c->Hcc, c->bc, c->cam_part);
+    }
     if (c->comm && !c->comm_replicated) {   // camera blocks of all shards: every rank ends up with the TOTAL Hcc, b_c (3.4 MB at 10k cameras)
       int rc2 = comm_allreduce_sum(c, c->Hcc, (size_t)g.n_free_cams * 36);
       if (!rc2) rc2 = comm_allreduce_sum(c, c->bc, (size_t)g.n_free_cams * 6);
@@ -873,11 +895,78 @@ int slam_build_reduced(esl_ctx* c, double lambda, bool full_sum, void** dev_ptr,
   return ESL_OK;
 }
 
+// chi2 of the anchored edges at the trial cameras (after the camera update of either form, before reduce_all)
+static void anch_trial_chi2(esl_ctx* c) {
+  if (!c->fx_on || c->fx.n_bb + c->fx.n_e3 == 0) return;
+  robust_dispatch(c->robust_on, [&](auto robust) {
+    hipLaunchKernelGGL(k_anch_chi2<decltype(robust)::value>, dim3((c->g.n_cams + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kWave * kWavesPerBlock), 0, c->stream,
+                       c->g, c->fx, c->cams_trial, c->objs_trial, c->cam_part);
+  });
+}
+
+// One LM trial of ESL_SOLVER_CAMERA_CHAIN (esl_fixed.hpp): the block-tridiagonal camera system by cyclic reduction, the free
+// ellipsoids -- which hang on fixed cameras only -- by their own 9 x 9 solves.  Nothing of arena_solve / arena_S is touched.
+static int slam_try_step_chain(esl_ctx* c, double lambda) {
+  const DevGraph& g = c->g;
+  const int N = g.n_objs, F = g.n_cams, nf = g.n_free_cams;
+  const size_t need = (size_t)nf * 192;
+  if (need > c->chain_ws_cap) {
+    if (c->chain_ws) { ESL_HIP_TRY(hipStreamSynchronize(c->stream)); (void)hipFree(c->chain_ws); c->chain_ws = nullptr; c->chain_ws_cap = 0; }
+    ESL_HIP_TRY(hipMalloc((void**)&c->chain_ws, need * sizeof(double)));
+    c->chain_ws_cap = need;
+  }
+  double* D[2] = {c->chain_ws, c->chain_ws + (size_t)nf * 36};
+  double* L[2] = {c->chain_ws + (size_t)nf * 72, c->chain_ws + (size_t)nf * 108};
+  double* Di = c->chain_ws + (size_t)nf * 144;
+  double* R[2] = {c->chain_ws + (size_t)nf * 180, c->chain_ws + (size_t)nf * 186};
+  {
+    ProfScope ps(c, 3);
+    ESL_HIP_TRY(hipMemsetAsync(c->chol_info, 0, sizeof(int), c->stream));
+    hipLaunchKernelGGL(k_chain_init, dim3((unsigned)(((long)nf * 36 + 255) / 256)), dim3(256), 0, c->stream, nf, c->Hcc, c->bc, c->Aod, c->cf_od_start, c->cf_od_edge,
+                       lambda, D[0], L[0], R[0]);
+    int cur = 0;
+    // (rows couple only when an odometry edge joins two free cameras; every such edge joins neighbours: chain_ok)
+    bool coupled = false;
+    for (size_t e = 0; e < c->h_od_i.size() && !coupled; ++e) coupled = c->h_cam_slot[c->h_od_i[e]] >= 0 && c->h_cam_slot[c->h_od_j[e]] >= 0;
+    if (coupled)
+      for (int d = 1; d < nf; d *= 2) {
+        hipLaunchKernelGGL(k_chain_inv, dim3((unsigned)(((long)nf * 6 + 255) / 256)), dim3(256), 0, c->stream, nf, D[cur], Di, c->chol_info);
+        hipLaunchKernelGGL(k_chain_step, dim3((unsigned)nf), dim3(64), 0, c->stream, nf, d, D[cur], L[cur], R[cur], Di, D[cur ^ 1], L[cur ^ 1], R[cur ^ 1]);
+        cur ^= 1;
+      }
+    hipLaunchKernelGGL(k_chain_solve, dim3((unsigned)((nf + 63) / 64)), dim3(64), 0, c->stream, nf, D[cur], R[cur], c->xc, c->chol_info);
+    ESL_HIP_TRY(hipGetLastError());
+  }
+  {
+    ProfScope ps(c, 1);
+    const dim3 grid((N + kWavesPerBlock - 1) / kWavesPerBlock), block(kWave * kWavesPerBlock);
+    if (N > 0) {   // x_o = (Hoo + lambda I)^-1 b_o: the ellipsoids' lists of free-camera edges are empty
+      hipLaunchKernelGGL(k_slam_prepare, grid, block, 0, c->stream, g, lambda, c->Hoo, c->bo, c->Wbb, c->Yb, c->Dinv, c->obj_part, c->Tb, c->Wt);
+      hipLaunchKernelGGL(k_slam_backsub, grid, block, 0, c->stream, g, lambda, c->objs, c->bo, c->Wbb, c->Dinv, c->xc, c->xo, c->objs_trial, c->obj_part);
+    }
+    hipLaunchKernelGGL(k_slam_cam_update, dim3((F + 127) / 128), dim3(128), 0, c->stream, g, lambda, c->cams, c->xc, c->bc, c->cams_trial, c->cam_part);
+    const int nb_co = (N + kWavesPerBlock - 1) / kWavesPerBlock, nb_od = (g.n_odom + kWave * kWavesPerBlock - 1) / (kWave * kWavesPerBlock);
+    if (nb_co + nb_od > 0)
+      robust_dispatch(c->robust_on, [&](auto robust) {
+        hipLaunchKernelGGL(k_slam_chi2_all<decltype(robust)::value>, dim3((unsigned)(nb_co + nb_od)), dim3(kWave * kWavesPerBlock), 0, c->stream, g, nb_co,
+                           c->cams_trial, c->objs_trial, c->obj_part, c->od_part);
+      });
+    anch_trial_chi2(c);
+    ESL_HIP_TRY(hipGetLastError());
+  }
+  return ESL_OK;
+}
+
 int slam_try_step(esl_ctx* c, double lambda) {
   c->parts_fresh = false;
   const DevGraph& g = c->g;
   const int N = g.n_objs, F = g.n_cams;
   int solver = slam_pick_solver(c);
+  if (solver == -2) {
+    set_error("ESL_SOLVER_CAMERA_CHAIN needs a graph without an active edge between a free camera and a free ellipsoid, odometry edges "
+              "that join neighbouring free cameras only, and no communicator");
+    return ESL_ERR_INVALID;
+  }
   if (solver < 0) {
     set_error("ESL_SOLVER_REDUCED_ELLIPSOID needs odometry edges that join neighbouring free cameras only and, across GPUs, the "
               "replicated-graph communicator (esl_comm_set_replicated); a single GPU always qualifies");
@@ -891,8 +980,12 @@ int slam_try_step(esl_ctx* c, double lambda) {
     solver = ESL_SOLVER_REDUCED_CAMERA;
   }
   c->lm_solver_used = solver;
-  if (solver == ESL_SOLVER_REDUCED_ELLIPSOID) {
+  if (solver == ESL_SOLVER_CAMERA_CHAIN) {
+    if ((rc = slam_try_step_chain(c, lambda))) return rc;
+  } else if (solver == ESL_SOLVER_REDUCED_ELLIPSOID) {
     if ((rc = slam_try_step_cf(c, lambda))) return rc;
+    anch_trial_chi2(c);
+    ESL_HIP_TRY(hipGetLastError());
   } else {
   if ((rc = slam_build_reduced(c, lambda, false, nullptr, nullptr))) return rc;
   {
@@ -920,6 +1013,7 @@ int slam_try_step(esl_ctx* c, double lambda) {
         hipLaunchKernelGGL(k_slam_chi2_all<decltype(robust)::value>, dim3((unsigned)(nb_co + nb_od)), dim3(kWave * kWavesPerBlock), 0, c->stream, g, nb_co,
                            c->cams_trial, c->objs_trial, c->obj_part, c->od_part);
       });
+    anch_trial_chi2(c);
   }
   ESL_HIP_TRY(hipGetLastError());
   }

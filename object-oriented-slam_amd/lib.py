@@ -20,7 +20,7 @@ _lib = None
 
 EXPORTS = [
     "esl_abi_version", "esl_last_error", "esl_device_count", "esl_ctx_create", "esl_ctx_destroy",
-    "esl_ctx_synchronize", "esl_ctx_trim", "esl_lm_params_default", "esl_optimize", "esl_graph_upload", "esl_graph_append", "esl_graph_sizes", "esl_states_upload",
+    "esl_ctx_synchronize", "esl_ctx_trim", "esl_lm_params_default", "esl_optimize", "esl_optimize_fixed", "esl_graph_upload", "esl_graph_upload_fixed", "esl_graph_obj_fixed", "esl_graph_append", "esl_graph_sizes", "esl_states_upload",
     "esl_states_download", "esl_optimize_resident", "esl_states_snapshot", "esl_states_restore", "esl_profile_enable", "esl_profile_get", "esl_lm_begin", "esl_lm_linearize", "esl_lm_reduced_system", "esl_lm_reduced_residual",
     "esl_lm_try_step", "esl_lm_commit", "esl_lm_solver_used", "esl_lm_solver_stats", "esl_lm_download", "esl_lm_set_robust", "esl_edge_chi2", "esl_comm_unique_id", "esl_comm_init", "esl_comm_init_host", "esl_comm_set_replicated", "esl_comm_destroy", "esl_partition_objects", "esl_fit_params_default", "esl_fit_frame", "esl_fit_frame_debug", "esl_fit_frame_ex", "esl_selftest_cholesky", "esl_debug_chol_plan",
     "esl_init_quadric", "esl_init_from_qstar", "esl_init_plane_error", "esl_plane_params_default", "esl_extract_ground_plane", "esl_extract_planes",
@@ -66,6 +66,16 @@ def device_count():
 _dp = C.POINTER(C.c_double)
 
 
+def _fixed_flags(obj_fixed, n_objs):
+    """obj_fixed (None or n_objs flags) as a contiguous uint8 array, or None"""
+    if obj_fixed is None:
+        return None
+    f = np.ascontiguousarray(np.asarray(obj_fixed) != 0, dtype=np.uint8).reshape(-1)
+    if f.size != n_objs:
+        raise ValueError(f"obj_fixed has {f.size} entries, the graph {n_objs} ellipsoids")
+    return f
+
+
 def _edge_counts(graph):
     return [len(graph.bbox_cam), len(graph.e3d_cam), len(graph.grav_obj), len(graph.odom_i)]
 
@@ -93,23 +103,42 @@ class Context:
             pass
 
     # ---- one shot -----------------------------------------------------------------------------
-    def optimize(self, graph, cams, objs, params=None):
+    def optimize(self, graph, cams, objs, params=None, obj_fixed=None):
+        """esl_optimize; obj_fixed (n_objs flags): esl_optimize_fixed -- those ellipsoids stay exactly as given (all of them fixed and
+        free cameras: pose-only optimisation against the map)."""
         p = params if params is not None else abi.default_lm_params()
         g = graph.c_struct()
         cams = np.array(cams, dtype=np.float64, order="C").reshape(-1, 7).copy()
         objs = np.array(objs, dtype=np.float64, order="C").reshape(-1, 10).copy()
         rep = abi.EslLmReport()
         self._edge_counts = _edge_counts(graph)
+        fx = _fixed_flags(obj_fixed, graph.n_objs)
+        if fx is not None:
+            _check(load().esl_optimize_fixed(self._h, C.byref(g), fx.ctypes.data_as(C.POINTER(C.c_uint8)), cams.ctypes.data_as(_dp),
+                                             objs.ctypes.data_as(_dp), C.byref(p), C.byref(rep)), "esl_optimize_fixed")
+            return cams, objs, rep.as_dict()
         _check(load().esl_optimize(self._h, C.byref(g), cams.ctypes.data_as(_dp), objs.ctypes.data_as(_dp),
                                    C.byref(p), C.byref(rep)), "esl_optimize")
         return cams, objs, rep.as_dict()
 
     # ---- resident / step API --------------------------------------------------------------------
-    def upload_graph(self, graph):
-        self._graph = graph
+    def upload_graph(self, graph, obj_fixed=None):
+        """esl_graph_upload; obj_fixed (n_objs flags): esl_graph_upload_fixed."""
         g = graph.c_struct()
-        _check(load().esl_graph_upload(self._h, C.byref(g)), "esl_graph_upload")
+        fx = _fixed_flags(obj_fixed, graph.n_objs)
+        if fx is not None:
+            _check(load().esl_graph_upload_fixed(self._h, C.byref(g), fx.ctypes.data_as(C.POINTER(C.c_uint8))), "esl_graph_upload_fixed")
+        else:
+            _check(load().esl_graph_upload(self._h, C.byref(g)), "esl_graph_upload")
+        self._graph = graph
         self._edge_counts = _edge_counts(graph)
+
+    def graph_obj_fixed(self):
+        """esl_graph_obj_fixed: the fixed flags of the resident graph's ellipsoids (all zero after a plain upload)."""
+        n = self.graph_sizes()["n_objs"]
+        f = np.zeros(max(n, 1), dtype=np.uint8)
+        _check(load().esl_graph_obj_fixed(self._h, f.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_int32(n)), "esl_graph_obj_fixed")
+        return f[:n]
 
     def append_graph(self, new_cams=(), new_objs=(), bbox=None, e3d=None, grav_obj=(), new_cam_fixed=None, odom=None):
         """esl_graph_append: bbox = (cam, obj, meas (n,4), weight), e3d = (cam, obj, meas (n,10), weight); indices in the extended
@@ -195,7 +224,8 @@ class Context:
         _check(load().esl_lm_commit(self._h, C.c_int(1 if accept else 0)), "esl_lm_commit")
 
     def lm_solver_used(self):
-        """esl_linear_solver of the last SLAM-mode trial step: 1 reduced camera system, 2 reduced ellipsoid system (cameras first)."""
+        """esl_linear_solver of the last SLAM-mode trial step: 1 reduced camera system, 2 reduced ellipsoid system (cameras first), 3 the camera chain
+        alone (no free camera sees a free ellipsoid)."""
         v = C.c_int32(0)
         _check(load().esl_lm_solver_used(self._h, C.byref(v)), "esl_lm_solver_used")
         return v.value
