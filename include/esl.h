@@ -138,7 +138,17 @@ typedef enum {
    * ellipsoids, which can then only hang on fixed cameras, keep their 9 x 9 solves.  ESL_ERR_INVALID when requested on a graph that
    * does not qualify or on a context with a communicator.  ESL_SOLVER_AUTO picks it when it applies AND the graph was uploaded
    * with at least one obj_fixed flag set; requested explicitly it runs on any qualifying graph. */
-  ESL_SOLVER_CAMERA_CHAIN = 3
+  ESL_SOLVER_CAMERA_CHAIN = 3,
+  /* Matrix-free preconditioned conjugate gradient on the reduced camera system (additive part of ABI 5, with esl_lm_set_pcg: detect
+   * by the symbol; g2o's LinearSolverPCG, solvers/pcg/linear_solver_pcg.hpp, on the Schur complement).  S x_c = b_s is solved from
+   * x_0 = 0 with the 6 x 6 diagonal blocks of S as the preconditioner and S never formed: one iteration is two passes over the
+   * per-edge W blocks of the linearisation, so a trial costs O(edges) time and memory -- no dense matrix, any odometry topology
+   * (loop closures included), robust kernels and fixed ellipsoids as in the other forms.  The iteration stops at the first k with
+   * |r_k| <= rel_tol |b_s| (esl_pcg_params); a non-positive pivot in a preconditioner block or in an ellipsoid block, or no
+   * convergence within max_iters, is reported exactly as a non-positive pivot of the dense factorisation is (solve_ok = 0: the LM
+   * rejects the trial and raises lambda -- g2o's reaction to a failed _solver->solve).  Bit-reproducible from run to run.
+   * ESL_SOLVER_AUTO never picks it.  One GPU: ESL_ERR_INVALID on a context with a communicator. */
+  ESL_SOLVER_PCG = 4
 } esl_linear_solver;
 
 typedef enum {
@@ -219,6 +229,25 @@ typedef struct {
  * its start (esl_optimize, esl_optimize_resident, esl_lm_begin).  p = NULL: every class ESL_ROBUST_NONE (the default).
  * ESL_ERR_INVALID for a kind out of range or a bad delta.  Sharded runs: every rank must set the same values. */
 int esl_lm_set_robust(esl_ctx* ctx, const esl_robust_params* p);
+/* ---- ESL_SOLVER_PCG (additive part of ABI 5) -------------------------------------------------------------------------
+ * The setting belongs to the context exactly like esl_lm_set_robust: it survives esl_graph_upload, esl_graph_append and
+ * esl_ctx_trim and is read when a run starts (esl_optimize, esl_optimize_resident, esl_lm_begin).  p = NULL restores the defaults.
+ * ESL_ERR_INVALID for max_iters < 1, check_every < 1, or a rel_tol that is not finite or <= 0. */
+typedef struct {
+  int32_t max_iters;     /* 1000: iterations after which the solve counts as failed */
+  int32_t check_every;   /* 8: the host looks at the device's done flag once per this many iterations (the iterations, alpha, beta
+                          * and the stop test run on the device; launches behind a finished solve do nothing, so x_c, the iteration
+                          * count and the residual do not depend on this value) */
+  double rel_tol;        /* 1e-10: stop at |r_k|_2 <= rel_tol |b_s|_2 */
+} esl_pcg_params;        /* 16 bytes */
+void esl_pcg_params_default(esl_pcg_params* p);
+int esl_lm_set_pcg(esl_ctx* ctx, const esl_pcg_params* p);
+/* stats[0] iterations of the last PCG solve, [1] |r|_2 / |b_s|_2 at its exit (from the recurrence), [2] converged (0 / 1),
+ * [3] PCG solves since esl_lm_begin / the start of the optimize call, [4] iterations summed over those solves, [5] max_iters and
+ * [6] rel_tol in force, [7] 0.  All zeros before any PCG trial of this context. */
+#define ESL_PCG_STATS 8
+int esl_lm_pcg_stats(esl_ctx* ctx, double stats[ESL_PCG_STATS]);
+
 /* Every edge of one class at the states the context holds (e.g. after an optimize call): chi2[i] = raw chi2 e, weight[i] = rho1(e)
  * as the solver applies it, in CALLER order (upload order, then append order).  Bbox edges dropped by the NaN pre-check or the
  * visibility test report weight 0; a class without a kernel reports weight 1.  Gravity edges report the value of their
@@ -323,7 +352,8 @@ int esl_lm_try_step(esl_ctx* ctx, double lambda, esl_lm_partials* out);
 /* accept != 0: discard backup; accept == 0: restore states from backup */
 int esl_lm_commit(esl_ctx* ctx, int accept);
 /* which esl_linear_solver the last SLAM-mode trial step of this context ran with (ESL_SOLVER_REDUCED_CAMERA,
- * ESL_SOLVER_REDUCED_ELLIPSOID or ESL_SOLVER_CAMERA_CHAIN: what ESL_SOLVER_AUTO resolved to); 0 before any SLAM-mode step */
+ * ESL_SOLVER_REDUCED_ELLIPSOID or ESL_SOLVER_CAMERA_CHAIN: what ESL_SOLVER_AUTO resolved to; ESL_SOLVER_PCG when it was requested);
+ * 0 before any SLAM-mode step */
 int esl_lm_solver_used(esl_ctx* ctx, int32_t* solver_out);
 /* shape of the camera-first elimination of the resident graph as the last trial step ran it (zeros when it did not):
  * stats[0] form of X: 0 dense rows, 1 sparse with stored per-segment products, 2 sparse, blocks of T straight from the slabs;
@@ -341,6 +371,8 @@ int esl_lm_solver_stats(esl_ctx* ctx, double stats[ESL_SOLVER_STATS]);
  *        8 trial cameras (n_cams x 7), 9 (SLAM mode) the per-edge camera-ellipsoid blocks W = Jc^T Omega Jo as [54][n_bbox + n_e3d]:
  *        entry (a, b) of edge u at [(a * 9 + b) * (n_bbox + n_e3d) + u], u = position of the edge after the stable sort by
  *        ellipsoid (bbox edges first, 3-D edges from n_bbox on); zero for edges of fixed cameras.
+ *        10 the 6 x 6 diagonal blocks of S (n_free_cams x 36, row-major) exactly as the preconditioner of the last ESL_SOLVER_PCG
+ *        trial used them, before inversion; ESL_ERR_STATE when the last trial ran another solver.
  *        count = number of doubles the caller's buffer holds. */
 int esl_lm_download(esl_ctx* ctx, int32_t which, double* dst, int64_t count);
 

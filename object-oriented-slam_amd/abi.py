@@ -111,7 +111,17 @@ def default_plane_params(**kw):
     return p
 
 
-SOLVER_AUTO, SOLVER_REDUCED_CAMERA, SOLVER_REDUCED_ELLIPSOID, SOLVER_CAMERA_CHAIN = 0, 1, 2, 3   # esl_linear_solver (include/esl.h)
+SOLVER_AUTO, SOLVER_REDUCED_CAMERA, SOLVER_REDUCED_ELLIPSOID, SOLVER_CAMERA_CHAIN, SOLVER_PCG = 0, 1, 2, 3, 4   # esl_linear_solver (include/esl.h)
+
+
+class EslPcgParams(C.Structure):
+    """esl_pcg_params: settings of ESL_SOLVER_PCG (esl_lm_set_pcg)."""
+    _fields_ = [("max_iters", C.c_int32), ("check_every", C.c_int32), ("rel_tol", C.c_double)]
+
+
+def default_pcg_params():
+    """esl_pcg_params_default: 1000 iterations, a host look at the done flag every 8, rel_tol 1e-10."""
+    return EslPcgParams(max_iters=1000, check_every=8, rel_tol=1e-10)
 
 ROBUST_KINDS = {"none": 0, "huber": 1, "pseudo_huber": 2, "cauchy": 3, "tukey": 4}   # esl_robust_kind (include/esl.h)
 EDGE_CLASSES = {"bbox": 0, "e3d": 1, "grav": 2, "odom": 3}                         # esl_edge_class

@@ -1345,6 +1345,8 @@ static int lm_begin_enqueue(esl_ctx* c, const esl_lm_params* p, bool validate_in
   c->g.bbox_mode = p->bbox_residual == ESL_BBOX_TANGENCY ? 1 : 0;
   c->g.yt.as_written = p->e3d_half_turn ? 1 : 0;
   robust_to_graph(c);
+  c->pcg_run = c->pcg;   // (esl_lm_set_pcg: read when a run starts)
+  c->pcg_reset = true;
   c->lm.slam = c->g.n_free_cams > 0;
   c->lm.have_trial = false;
   int* cnt = c->chol_info + 2;
@@ -1604,7 +1606,7 @@ static int optimize_mapping_device(esl_ctx* c, const esl_lm_params* p, esl_lm_re
 int esl_optimize_resident(esl_ctx* c, const esl_lm_params* p, esl_lm_report* out) {
   if (!c || !p || !out) return ESL_ERR_INVALID;
   if (p->linear_solver != ESL_SOLVER_AUTO && p->linear_solver != ESL_SOLVER_REDUCED_CAMERA && p->linear_solver != ESL_SOLVER_REDUCED_ELLIPSOID &&
-      p->linear_solver != ESL_SOLVER_CAMERA_CHAIN) {
+      p->linear_solver != ESL_SOLVER_CAMERA_CHAIN && p->linear_solver != ESL_SOLVER_PCG) {
     set_error("esl_lm_params::linear_solver: unknown solver"); return ESL_ERR_INVALID;
   }
   if (p->bbox_residual != ESL_BBOX_REPROJECTION && p->bbox_residual != ESL_BBOX_TANGENCY) { set_error("esl_lm_params::bbox_residual: unknown mode"); return ESL_ERR_INVALID; }
@@ -1766,6 +1768,26 @@ int esl_lm_set_robust(esl_ctx* c, const esl_robust_params* p) {
   return ESL_OK;
 }
 
+void esl_pcg_params_default(esl_pcg_params* p) {
+  p->max_iters = 1000;
+  p->check_every = 8;
+  p->rel_tol = 1e-10;
+}
+
+int esl_lm_set_pcg(esl_ctx* c, const esl_pcg_params* p) {
+  if (!c) return ESL_ERR_INVALID;
+  esl_pcg_params r;
+  esl_pcg_params_default(&r);
+  if (p) {
+    if (p->max_iters < 1) { set_error("esl_lm_set_pcg: max_iters must be >= 1"); return ESL_ERR_INVALID; }
+    if (p->check_every < 1) { set_error("esl_lm_set_pcg: check_every must be >= 1"); return ESL_ERR_INVALID; }
+    if (!(std::isfinite(p->rel_tol) && p->rel_tol > 0)) { set_error("esl_lm_set_pcg: rel_tol must be finite and > 0"); return ESL_ERR_INVALID; }
+    r = *p;
+  }
+  c->pcg = r;
+  return ESL_OK;
+}
+
 static int edge_chi2_plain(esl_ctx* c, int32_t edge_class, double* chi2, double* weight, int64_t count);
 // flagged graph: the free ellipsoids' edges from the ordinary path, the fixed ellipsoids' from k_anch_edge_chi2, merged in caller order
 static int edge_chi2_fixed(esl_ctx* c, int32_t edge_class, double* chi2, double* weight, int64_t count) {
@@ -1866,6 +1888,9 @@ int esl_lm_download(esl_ctx* c, int32_t which, double* dst, int64_t count) {
     case 9:
       if (c->fx_on) { set_error("esl_lm_download: the W records are not available on a graph with fixed ellipsoids"); return ESL_ERR_STATE; }
       src = c->lm.slam ? c->Wbb : nullptr; n = ((int64_t)g.n_bbox + g.n_e3d) * 54; break;
+    case 10:
+      if (c->lm_solver_used != ESL_SOLVER_PCG || !c->pcg_M) { set_error("esl_lm_download: the last trial step did not run ESL_SOLVER_PCG"); return ESL_ERR_STATE; }
+      src = c->pcg_M; n = (int64_t)g.n_free_cams * 36; break;
     default: set_error("esl_lm_download: unknown array"); return ESL_ERR_INVALID;
   }
   if (!src || count < n) { set_error("esl_lm_download: array not available or buffer too small"); return ESL_ERR_INVALID; }

@@ -306,6 +306,16 @@ struct esl_ctx {
   std::vector<int> fx_grav_obj;             // the caller's gravity edges (all of them; h_grav_obj holds those of free ellipsoids)
   bool chain_ok = false;                    // the odometry edges between free cameras join neighbours only (slam_alloc)
   double* chain_ws = nullptr; size_t chain_ws_cap = 0;   // ESL_SOLVER_CAMERA_CHAIN: D, L, rhs (two sets) + the blocks' inverses; grow-only
+  // ESL_SOLVER_PCG (esl_pcg.hpp).  pcg: esl_lm_set_pcg, read when a run starts (pcg_run); pcg_ws: state block, M, M^-1, b_s, r, z, p (two),
+  // q, D^-1 b_o, the edges' products, the partials -- O(edges + cameras), grow-only, freed by slam_release; pcg_M: the diagonal blocks of S
+  // of the last PCG trial (interior pointer, null when the last trial ran another solver); pcg_host: pinned, the done flag's landing place
+  esl_pcg_params pcg = {1000, 8, 1e-10};
+  esl_pcg_params pcg_run = {1000, 8, 1e-10};
+  double* pcg_ws = nullptr; size_t pcg_ws_cap = 0;
+  double* pcg_st = nullptr; double* pcg_M = nullptr;
+  double* pcg_host = nullptr;
+  bool pcg_ran = false;            // a PCG trial has run on this context (esl_lm_pcg_stats reports zeros before)
+  bool pcg_reset = true;           // the per-run counters restart with the next PCG trial (esl_lm_begin)
   // per-context runtime of the dense solver (esl_chol.hpp CholRuntime: look-ahead stream + events on THIS device, one-time
   // kernel attributes of this device) and of the Schur kernel; created on first use, released with the context
   void* chol_rt = nullptr;

@@ -14,6 +14,7 @@
 #include "esl_chol.hpp"
 #include "esl_fixed.hpp"
 #include "esl_kernels_slam.hpp"
+#include "esl_pcg.hpp"
 
 namespace esl {
 
@@ -98,6 +99,7 @@ void slam_forget(esl_ctx* c) {
   c->Hcc = c->bc = c->xc = c->Wbb = c->Abb = c->Aod = c->Dinv = c->Yb = c->Wt = c->Tb = c->cam_part = c->od_part = c->z_ws = nullptr;
   c->cf_od_start = c->cf_od_edge = nullptr;
   c->S = c->Linv_ws = nullptr;
+  c->pcg_M = nullptr;   // (sized by the graph that goes away: esl_lm_download(10) needs a PCG trial on the new one)
   cf_forget(c);
   c->cf_chain_ok = false; c->cf_unavailable = false; c->chain_ok = false;
   c->h_ue_start.clear(); c->h_ue_id.clear(); c->h_ue_slot.clear();
@@ -109,7 +111,12 @@ static void blob_release(BlobArena& a) {
   if (a.ev) (void)hipEventDestroy(a.ev);
   a = BlobArena{};
 }
-void slam_release(esl_ctx* c) { slam_forget(c); blob_release(c->arena_slam); blob_release(c->arena_solve); blob_release(c->arena_S); }
+static void pcg_release(esl_ctx* c) {
+  if (c->pcg_ws) (void)hipFree(c->pcg_ws);
+  if (c->pcg_host) (void)hipHostFree(c->pcg_host);
+  c->pcg_ws = c->pcg_st = c->pcg_M = c->pcg_host = nullptr; c->pcg_ws_cap = 0; c->pcg_ran = false;
+}
+void slam_release(esl_ctx* c) { slam_forget(c); blob_release(c->arena_slam); blob_release(c->arena_solve); blob_release(c->arena_S); pcg_release(c); }
 // esl_ctx_trim: drop the solver blobs (tens of GB at BASELINE configs[3]); the next trial step that needs one builds it again.
 // keep_lists: the resident graph has free cameras, so arena_slam (its lists, W, Y ...) is still in use.
 void slam_trim(esl_ctx* c, bool keep_lists) {
@@ -276,6 +283,7 @@ static bool cf_dist(const esl_ctx* c) {
 static bool chain_applicable(const esl_ctx* c) { return c->chain_ok && c->g.n_ue == 0 && !c->comm; }
 static int slam_pick_solver(const esl_ctx* c) {
   const int want = c->lm.p.linear_solver;
+  if (want == ESL_SOLVER_PCG) return c->comm ? -3 : ESL_SOLVER_PCG;
   if (want == ESL_SOLVER_CAMERA_CHAIN) return chain_applicable(c) ? ESL_SOLVER_CAMERA_CHAIN : -2;
   if (want == ESL_SOLVER_AUTO && c->fx_on && chain_applicable(c)) return ESL_SOLVER_CAMERA_CHAIN;   // (only graphs uploaded with a flag set)
   if (want == ESL_SOLVER_REDUCED_CAMERA) return ESL_SOLVER_REDUCED_CAMERA;
@@ -957,6 +965,74 @@ static int slam_try_step_chain(esl_ctx* c, double lambda) {
   return ESL_OK;
 }
 
+// ESL_SOLVER_PCG (esl_pcg.hpp): x_c of the reduced camera system by preconditioned conjugate gradients, S never formed.  Leaves Dinv
+// and x_c where k_slam_backsub expects them and the verdict in bit 0 of the solver's flag word.  Touches none of arena_S / arena_solve.
+static int slam_pcg_solve(esl_ctx* c, double lambda) {
+  const DevGraph& g = c->g;
+  const int N = g.n_objs, F = g.n_cams, nf = g.n_free_cams;
+  const size_t EU = (size_t)g.n_bbox + g.n_e3d, n = (size_t)nf * 6;
+  const int nb_obj = std::max(1, (N + kWavesPerBlock - 1) / kWavesPerBlock), nb_cam = (F + kWavesPerBlock - 1) / kWavesPerBlock;
+  const int nb_upd = (nf + kPcgBlock - 1) / kPcgBlock;
+  // layout of the workspace (doubles)
+  size_t off = 0;
+  auto take = [&](size_t cnt) { const size_t at = off; off += (cnt + 31) / 32 * 32; return at; };
+  const size_t o_st = take(kPcgState), o_M = take((size_t)nf * 36), o_Mi = take((size_t)nf * 36), o_bs = take(n), o_r = take(n), o_z = take(n),
+               o_p0 = take(n), o_p1 = take(n), o_q = take(n), o_dbo = take((size_t)N * 9), o_E = take(EU * 6), o_pq = take((size_t)nb_cam),
+               o_rz = take(2 * (size_t)nb_upd), o_rr = take(2 * (size_t)nb_upd);
+  if (off > c->pcg_ws_cap) {
+    if (c->pcg_ws) { ESL_HIP_TRY(hipStreamSynchronize(c->stream)); (void)hipFree(c->pcg_ws); c->pcg_ws = nullptr; c->pcg_ws_cap = 0; }
+    const size_t want = off + off / 8;
+    ESL_HIP_TRY(hipMalloc((void**)&c->pcg_ws, want * sizeof(double)));
+    c->pcg_ws_cap = want;
+    c->pcg_reset = true;   // (the counters lived in the old block)
+  }
+  if (!c->pcg_host) ESL_HIP_TRY(hipHostMalloc((void**)&c->pcg_host, 16 * sizeof(double), hipHostMallocDefault));
+  double* ws = c->pcg_ws;
+  double* st = ws + o_st;
+  double* pbuf[2] = {ws + o_p0, ws + o_p1};
+  c->pcg_st = st; c->pcg_M = ws + o_M;
+  const esl_pcg_params pp = c->pcg_run;
+  const double tol2 = pp.rel_tol * pp.rel_tol;
+  const dim3 block(kWave * kWavesPerBlock);
+  {
+    ProfScope ps(c, 2);
+    ESL_HIP_TRY(hipMemsetAsync(c->chol_info, 0, sizeof(int), c->stream));
+    ESL_HIP_TRY(hipMemsetAsync(st, 0, kPcgSolves * sizeof(double), c->stream));
+    ESL_HIP_TRY(hipMemsetAsync(pbuf[0], 0, std::max<size_t>(n, 1) * sizeof(double), c->stream));
+    if (N > 0)
+      hipLaunchKernelGGL(k_pcg_setup_obj, dim3((unsigned)((N + kWavesPerBlock - 1) / kWavesPerBlock)), block, 0, c->stream, g, lambda, c->Hoo, c->bo, c->Dinv,
+                         ws + o_dbo, c->obj_part, c->chol_info);
+    hipLaunchKernelGGL(k_pcg_setup_cam, dim3((unsigned)nb_cam), block, 0, c->stream, g, lambda, c->Hcc, c->bc, c->Wbb, c->Dinv, ws + o_dbo, ws + o_M, ws + o_Mi,
+                       ws + o_bs, c->chol_info);
+    hipLaunchKernelGGL(k_pcg_update, dim3((unsigned)nb_upd), dim3(kPcgBlock), 0, c->stream, nf, -1, st, c->chol_info, ws + o_pq, nb_cam, ws + o_Mi, ws + o_bs,
+                       pbuf[0], ws + o_q, c->xc, ws + o_r, ws + o_z, ws + o_rz, ws + o_rr, nb_upd);
+    ESL_HIP_TRY(hipGetLastError());
+  }
+  {
+    ProfScope ps(c, 3);
+    int k = 0;
+    while (k < pp.max_iters) {
+      hipLaunchKernelGGL(k_pcg_obj, dim3((unsigned)nb_obj), block, 0, c->stream, g, k, tol2, st, ws + o_rz, ws + o_rr, nb_upd, c->Wbb, c->Dinv, ws + o_z,
+                         pbuf[k & 1], ws + o_E);
+      hipLaunchKernelGGL(k_pcg_cam, dim3((unsigned)nb_cam), block, 0, c->stream, g, k, lambda, st, c->Hcc, c->Aod, ws + o_E, ws + o_z, pbuf[k & 1],
+                         pbuf[(k + 1) & 1], ws + o_q, ws + o_pq);
+      hipLaunchKernelGGL(k_pcg_update, dim3((unsigned)nb_upd), dim3(kPcgBlock), 0, c->stream, nf, k, st, c->chol_info, ws + o_pq, nb_cam, ws + o_Mi, ws + o_bs,
+                         pbuf[(k + 1) & 1], ws + o_q, c->xc, ws + o_r, ws + o_z, ws + o_rz, ws + o_rr, nb_upd);
+      ++k;
+      if (k % pp.check_every == 0 && k < pp.max_iters) {   // the host's look at the done flag
+        ESL_HIP_TRY(hipMemcpyAsync(c->pcg_host, st + kPcgDone, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        ESL_HIP_TRY(hipStreamSynchronize(c->stream));
+        if (c->pcg_host[0] != 0) break;
+      }
+    }
+    hipLaunchKernelGGL(k_pcg_finish, dim3(1), dim3(kPcgBlock), 0, c->stream, k, tol2, st, ws + o_rr, nb_upd, c->chol_info, c->pcg_reset ? 1 : 0);
+    ESL_HIP_TRY(hipGetLastError());
+  }
+  c->pcg_reset = false;
+  c->pcg_ran = true;
+  return ESL_OK;
+}
+
 int slam_try_step(esl_ctx* c, double lambda) {
   c->parts_fresh = false;
   const DevGraph& g = c->g;
@@ -965,6 +1041,10 @@ int slam_try_step(esl_ctx* c, double lambda) {
   if (solver == -2) {
     set_error("ESL_SOLVER_CAMERA_CHAIN needs a graph without an active edge between a free camera and a free ellipsoid, odometry edges "
               "that join neighbouring free cameras only, and no communicator");
+    return ESL_ERR_INVALID;
+  }
+  if (solver == -3) {
+    set_error("ESL_SOLVER_PCG runs on one GPU: this context has a communicator (multi-GPU PCG is not implemented)");
     return ESL_ERR_INVALID;
   }
   if (solver < 0) {
@@ -980,6 +1060,7 @@ int slam_try_step(esl_ctx* c, double lambda) {
     solver = ESL_SOLVER_REDUCED_CAMERA;
   }
   c->lm_solver_used = solver;
+  if (solver != ESL_SOLVER_PCG) c->pcg_M = nullptr;   // (esl_lm_download(10): the blocks of the LAST trial's preconditioner only)
   if (solver == ESL_SOLVER_CAMERA_CHAIN) {
     if ((rc = slam_try_step_chain(c, lambda))) return rc;
   } else if (solver == ESL_SOLVER_REDUCED_ELLIPSOID) {
@@ -987,8 +1068,10 @@ int slam_try_step(esl_ctx* c, double lambda) {
     anch_trial_chi2(c);
     ESL_HIP_TRY(hipGetLastError());
   } else {
-  if ((rc = slam_build_reduced(c, lambda, false, nullptr, nullptr))) return rc;
-  {
+  if (solver == ESL_SOLVER_PCG) {
+    if ((rc = slam_pcg_solve(c, lambda))) return rc;
+  } else {
+    if ((rc = slam_build_reduced(c, lambda, false, nullptr, nullptr))) return rc;
     ProfScope ps(c, 3);
     ESL_HIP_TRY(hipMemsetAsync(c->chol_info, 0, sizeof(int), c->stream));
     if (c->comm && slam_dist_chol(c)) {
@@ -1293,6 +1376,21 @@ extern "C" int esl_lm_solver_stats(esl_ctx* c, double* st) {
   st[7] = (double)(c->cf_sparse ? c->cf_kpad_s : c->cf_kpad);
   st[8] = c->cf_tperm ? c->cf_upd_flops : 0.0;   // (0: the whole lower triangle times K)
   st[9] = c->cf_tperm ? 1.0 : 0.0;
+  return ESL_OK;
+}
+extern "C" int esl_lm_pcg_stats(esl_ctx* c, double* st) {
+  if (!c || !st) return ESL_ERR_INVALID;
+  for (int k = 0; k < ESL_PCG_STATS; ++k) st[k] = 0;
+  if (!c->pcg_ran || !c->pcg_st) return ESL_OK;
+  ESL_HIP_TRY(hipSetDevice(c->device));
+  double h[esl::kPcgState];
+  ESL_HIP_TRY(hipMemcpyAsync(h, c->pcg_st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  ESL_HIP_TRY(hipStreamSynchronize(c->stream));
+  st[0] = h[esl::kPcgIters];
+  st[1] = h[esl::kPcgBb] > 0 ? std::sqrt(h[esl::kPcgRr] / h[esl::kPcgBb]) : 0.0;
+  st[2] = h[esl::kPcgConv];
+  if (!c->pcg_reset) { st[3] = h[esl::kPcgSolves]; st[4] = h[esl::kPcgIterSum]; }
+  st[5] = c->pcg_run.max_iters; st[6] = c->pcg_run.rel_tol;
   return ESL_OK;
 }
 extern "C" int esl_lm_solver_used(esl_ctx* c, int32_t* solver_out) {

@@ -22,7 +22,7 @@ EXPORTS = [
     "esl_abi_version", "esl_last_error", "esl_device_count", "esl_ctx_create", "esl_ctx_destroy",
     "esl_ctx_synchronize", "esl_ctx_trim", "esl_lm_params_default", "esl_optimize", "esl_optimize_fixed", "esl_graph_upload", "esl_graph_upload_fixed", "esl_graph_obj_fixed", "esl_graph_append", "esl_graph_sizes", "esl_states_upload",
     "esl_states_download", "esl_optimize_resident", "esl_states_snapshot", "esl_states_restore", "esl_profile_enable", "esl_profile_get", "esl_lm_begin", "esl_lm_linearize", "esl_lm_reduced_system", "esl_lm_reduced_residual",
-    "esl_lm_try_step", "esl_lm_commit", "esl_lm_solver_used", "esl_lm_solver_stats", "esl_lm_download", "esl_lm_set_robust", "esl_edge_chi2", "esl_comm_unique_id", "esl_comm_init", "esl_comm_init_host", "esl_comm_set_replicated", "esl_comm_destroy", "esl_partition_objects", "esl_fit_params_default", "esl_fit_frame", "esl_fit_frame_debug", "esl_fit_frame_ex", "esl_selftest_cholesky", "esl_debug_chol_plan",
+    "esl_lm_try_step", "esl_lm_commit", "esl_lm_solver_used", "esl_lm_solver_stats", "esl_lm_download", "esl_lm_set_robust", "esl_edge_chi2", "esl_pcg_params_default", "esl_lm_set_pcg", "esl_lm_pcg_stats", "esl_comm_unique_id", "esl_comm_init", "esl_comm_init_host", "esl_comm_set_replicated", "esl_comm_destroy", "esl_partition_objects", "esl_fit_params_default", "esl_fit_frame", "esl_fit_frame_debug", "esl_fit_frame_ex", "esl_selftest_cholesky", "esl_debug_chol_plan",
     "esl_init_quadric", "esl_init_from_qstar", "esl_init_plane_error", "esl_plane_params_default", "esl_extract_ground_plane", "esl_extract_planes",
 ]
 
@@ -225,7 +225,7 @@ class Context:
 
     def lm_solver_used(self):
         """esl_linear_solver of the last SLAM-mode trial step: 1 reduced camera system, 2 reduced ellipsoid system (cameras first), 3 the camera chain
-        alone (no free camera sees a free ellipsoid)."""
+        alone (no free camera sees a free ellipsoid), 4 matrix-free PCG on the reduced camera system."""
         v = C.c_int32(0)
         _check(load().esl_lm_solver_used(self._h, C.byref(v)), "esl_lm_solver_used")
         return v.value
@@ -255,6 +255,25 @@ class Context:
         pseudo_huber, cauchy, tukey.  The setting stays with the context and applies from the next run on."""
         p = abi.default_robust_params(bbox=bbox, e3d=e3d, grav=grav, odom=odom)
         _check(load().esl_lm_set_robust(self._h, C.byref(p)), "esl_lm_set_robust")
+
+    def set_pcg(self, max_iters=None, check_every=None, rel_tol=None):
+        """esl_lm_set_pcg: the settings of ESL_SOLVER_PCG (None: the default -- 1000 iterations, a host look every 8, rel_tol 1e-10).  The
+        setting stays with the context and applies from the next run on."""
+        p = abi.default_pcg_params()
+        if max_iters is not None:
+            p.max_iters = int(max_iters)
+        if check_every is not None:
+            p.check_every = int(check_every)
+        if rel_tol is not None:
+            p.rel_tol = float(rel_tol)
+        _check(load().esl_lm_set_pcg(self._h, C.byref(p)), "esl_lm_set_pcg")
+
+    def lm_pcg_stats(self):
+        """esl_lm_pcg_stats: the last PCG solve and the sums over this run's solves (all zeros before any PCG trial)."""
+        st = (C.c_double * 8)()   # ESL_PCG_STATS
+        _check(load().esl_lm_pcg_stats(self._h, st), "esl_lm_pcg_stats")
+        names = ["iterations", "rel_residual", "converged", "solves", "iterations_total", "max_iters", "rel_tol", "reserved"]
+        return {n: float(st[i]) for i, n in enumerate(names)}
 
     def edge_chi2(self, edge_class):
         """esl_edge_chi2: (raw chi2, robust weight rho1) of every edge of one class ("bbox", "e3d", "grav", "odom" or its number) at the
