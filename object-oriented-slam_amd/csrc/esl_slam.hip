@@ -633,9 +633,9 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
     // serial order.
     static const bool overlap_on = !(std::getenv("ESL_CF_OVERLAP") && std::getenv("ESL_CF_OVERLAP")[0] == '0');
     const int Ks_ = (int)c->cf_kpad_s;
+    ESL_HIP_TRY(chol_set_attributes(rt));   // (fills rt.sw)
     const bool overlap = overlap_on && c->cf_sparse && c->cf_sp_form == 1 && !dist && Ks_ > 0 &&
-                         chol_update_v_applies(ldt, (long)n_o + 1, 0, (long)n_o, true, ldx) && rt.cf_overlap_init() == hipSuccess;
-    ESL_HIP_TRY(chol_set_attributes(rt));
+                         chol_update_v_applies(rt.sw, ldt, (long)n_o + 1, 0, (long)n_o, true, ldx) && rt.cf_overlap_init() == hipSuccess;
     auto launch_products = [&](hipStream_t st2) {
       hipLaunchKernelGGL(k_cf_seg_syrk, dim3((unsigned)c->cf_n_twork), dim3(256), 0, st2, c->cf_twork, c->cf_seg_start, c->cf_seg_first, c->cf_xoff,
                          c->cf_xld, c->cf_Xc, c->cf_boff, c->cf_P);
@@ -664,7 +664,7 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
       ESL_HIP_TRY(hipEventRecord(rt.cf_ev_p, rt.cf_side));
       {
         ProfScope pk(c, 7);   // the rank-K update (assign form), with the products running beside it
-        chol_launch_update(c->cf_T, ldt, (long)n_o + 1, c->stream, 0, Ks_, 0, (long)n_o, c->cf_Xs, ldx, nullptr, c->cf_kfirst, true);
+        chol_launch_update(rt.sw, c->cf_T, ldt, (long)n_o + 1, c->stream, 0, Ks_, 0, (long)n_o, c->cf_Xs, ldx, nullptr, c->cf_kfirst, true);
       }
       ESL_HIP_TRY(hipStreamWaitEvent(c->stream, rt.cf_ev_p, 0));
       {
@@ -688,10 +688,10 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
       if (dist) {
         for (int op = c->comm_rank; op < n_outer; op += c->comm_ranks) {
           const long c_begin = (long)op * Wp * kNB, c_end = std::min<long>((long)(op + 1) * Wp * kNB, (long)n_o);
-          chol_launch_update(c->cf_T, ldt, (long)n_o + 1, c->stream, 0, K, c_begin, c_end, Xf, ldx, nullptr, c->cf_sparse ? c->cf_kfirst : nullptr);
+          chol_launch_update(rt.sw, c->cf_T, ldt, (long)n_o + 1, c->stream, 0, K, c_begin, c_end, Xf, ldx, nullptr, c->cf_sparse ? c->cf_kfirst : nullptr);
         }
       } else if (K > 0) {
-        chol_launch_update(c->cf_T, ldt, (long)n_o + 1, c->stream, 0, K, 0, (long)n_o, Xf, ldx, c->cf_part, c->cf_sparse ? c->cf_kfirst : nullptr);
+        chol_launch_update(rt.sw, c->cf_T, ldt, (long)n_o + 1, c->stream, 0, K, 0, (long)n_o, Xf, ldx, c->cf_part, c->cf_sparse ? c->cf_kfirst : nullptr);
       }
     }
     }
@@ -1128,9 +1128,9 @@ int slam_try_step(esl_ctx* c, double lambda) {
     // waits, and the context keeps that form from then on.  Not in a multi-rank run: the other ranks would not redo
     // their collectives.
     CholRuntime& rt = chol_rt(c);
-    const bool can_retry = !(c->comm && c->comm_ranks > 1) && !(rt.sw_persistent == 0 && rt.sw_backsub == 1);
+    const bool can_retry = !(c->comm && c->comm_ranks > 1) && !(rt.sw.persistent == 0 && rt.sw.backsub_launches);
     if (!can_retry) { set_error("dense solver: a device-side hand-off timed out (k_chol_backsub / persistent panel kernel)"); return ESL_ERR_HIP; }
-    rt.sw_persistent = 0; rt.sw_backsub = 1; rt.fallbacks += 1;
+    rt.sw.persistent = 0; rt.sw.backsub_launches = true; rt.fallbacks += 1;
     fprintf(stderr, "[libesl_hip] a device-side hand-off of the dense solver timed out; this context now uses the launch-per-step form\n");
     ESL_HIP_TRY(hipMemsetAsync(c->chol_info, 0, sizeof(int), c->stream));
     c->parts_fresh = false;
@@ -1272,7 +1272,7 @@ extern "C" int esl_selftest_cholesky(esl_ctx* c, int32_t n, double* ms_out, doub
   ST_TRY(hipEventRecord(e0, c->stream));
   ST_TRY(chol_factor_solve(M, lda, n, Linv, z, x, info, c->stream, chol_rt(c)));
   ST_TRY(hipEventRecord(e1, c->stream));
-  if (std::getenv("ESL_CHOL_DEBUG")) {   // a stream created and destroyed while the factorisation runs: the disturbance that made the
+  if (chol_rt(c).sw.debug) {             // a stream created and destroyed while the factorisation runs: the disturbance that made the
     hipStream_t w2 = nullptr;             // scheduler time-slice the first (two-kernel) persistent form
     if (hipStreamCreateWithFlags(&w2, hipStreamNonBlocking) == hipSuccess) (void)hipStreamDestroy(w2);
   }
@@ -1285,74 +1285,7 @@ extern "C" int esl_selftest_cholesky(esl_ctx* c, int32_t n, double* ms_out, doub
   float ms = 0;
   ST_TRY(hipEventElapsedTime(&ms, e0, e1));
 #undef ST_TRY
-  if (std::getenv("ESL_CHOL_TIMING")) {
-    std::vector<long long> ps((size_t)kPwGrid * 5, 0);
-    if (hipMemcpyFromSymbol(ps.data(), HIP_SYMBOL(g_chol_stats), ps.size() * sizeof(long long)) == hipSuccess && ps[2] > 0) {
-      // persistent kernel, last launch: workgroup 0 = the chain of diagonal blocks, the others pull tasks off the list
-      long long t_first = ps[3], t_last = ps[4];
-      double w_wait = 0, w_body = 0, w_tasks = 0, w_span = 0, w_wait_max = 0, w_end_min = 1e300, w_end_max = 0; int nw = 0;
-      for (int b = 1; b < kPwGrid; ++b) {
-        const long long* q = &ps[(size_t)b * 5];
-        if (q[4] == 0) continue;
-        t_first = std::min(t_first, q[3]); t_last = std::max(t_last, q[4]);
-      }
-      for (int b = 1; b < kPwGrid; ++b) {
-        const long long* q = &ps[(size_t)b * 5];
-        if (q[4] == 0) continue;
-        ++nw; w_wait += (double)q[0]; w_body += (double)q[1]; w_tasks += (double)q[2]; w_span += (double)(q[4] - q[3]);
-        w_wait_max = std::max(w_wait_max, (double)q[0]);
-        w_end_min = std::min(w_end_min, (double)(q[4] - t_first)); w_end_max = std::max(w_end_max, (double)(q[4] - t_first));
-      }
-      fprintf(stderr, "[k_chol_persist, last launch] span %.2f ms | chain: %lld blocks, waiting %.2f ms, factoring %.2f ms | %d workers: mean waiting %.2f ms (max %.2f), "
-                      "in task bodies %.2f ms, %.0f tasks each, alive %.2f ms, first / last exit at %.2f / %.2f ms\n",
-              (double)(t_last - t_first) * 1e-5, ps[2], (double)ps[0] * 1e-5, (double)ps[1] * 1e-5, nw, nw ? w_wait / nw * 1e-5 : 0.0, w_wait_max * 1e-5,
-              nw ? w_body / nw * 1e-5 : 0.0, nw ? w_tasks / nw : 0.0, nw ? w_span / nw * 1e-5 : 0.0, w_end_min * 1e-5, w_end_max * 1e-5);
-    }
-    {
-      std::vector<long long> cl(2048, 0);
-      const int npl = std::min(1024, (n + kNB - 1) / kNB);
-      if (ps[2] > 0 && hipMemcpyFromSymbol(cl.data(), HIP_SYMBOL(g_chol_chain_log), cl.size() * sizeof(long long)) == hipSuccess && npl > 8) {
-        // the chain's timeline, averaged over eighths of the panels: factor time and the gap between one factor published and the next tile final
-        long long ft[4] = {0, 0, 0, 0};
-        if (hipMemcpyFromSymbol(ft, HIP_SYMBOL(g_chol_fuse_ticks), sizeof(ft)) == hipSuccess && (ft[1] | ft[2]))
-          fprintf(stderr, "[k_chol_persist chain, fused stage, us per panel] waits %.1f  rows under the block %.1f  next block's update %.1f  drain %.1f\n",
-                  (double)ft[0] * 0.01 / npl, (double)ft[1] * 0.01 / npl, (double)ft[2] * 0.01 / npl, (double)ft[3] * 0.01 / npl);
-        fprintf(stderr, "[k_chol_persist chain, us per panel by eighth of the matrix: potrf / gap to the next block]");
-        for (int e = 0; e < 8; ++e) {
-          const int k0 = e * npl / 8, k1 = std::min(npl - 1, (e + 1) * npl / 8);
-          double f = 0, g = 0; int c = 0;
-          for (int k = k0; k < k1; ++k) { f += (double)(cl[2 * k + 1] - cl[2 * k]); g += (double)(cl[2 * k + 2] - cl[2 * k + 1]); ++c; }
-          if (c) fprintf(stderr, " %.0f/%.0f", f / c * 0.01, g / c * 0.01);
-        }
-        fprintf(stderr, "\n");
-        {   // the same over the last three eighths (where the chain sets the pace), by the panel's position in its outer panel
-          const int Wp = chol_outer_panels(n);
-          std::vector<double> f(Wp, 0), g(Wp, 0); std::vector<int> cn(Wp, 0);
-          for (int k = 5 * npl / 8; k < npl - 1; ++k) { f[k % Wp] += (double)(cl[2 * k + 1] - cl[2 * k]); g[k % Wp] += (double)(cl[2 * k + 2] - cl[2 * k + 1]); ++cn[k % Wp]; }
-          fprintf(stderr, "[k_chol_persist chain, last 3/8 of the panels, us by k mod W: potrf / gap]");
-          for (int q = 0; q < Wp; ++q) if (cn[q]) fprintf(stderr, " %.0f/%.0f", f[q] / cn[q] * 0.01, g[q] / cn[q] * 0.01);
-          fprintf(stderr, "\n");
-        }
-      }
-    }
-    {
-      long long uc[4] = {0, 0, 0, 0};
-      if (hipMemcpyFromSymbol(uc, HIP_SYMBOL(g_upd_clk), sizeof(uc)) == hipSuccess && uc[1] > 0)
-        fprintf(stderr, "[k_chol_update_lds, one %lld-row tile of the last launch, K = %lld] %.1f us at a shader clock of %.0f MHz -> MFMA peak at that clock %.1f TFLOP/s\n",
-                uc[3], uc[2], (double)uc[1] * 0.01, (double)uc[0] / (double)uc[1] * 100.0, 78.6 * ((double)uc[0] / (double)uc[1] * 100.0) / 2400.0);
-    }
-    long long clk[16];
-    if (hipMemcpyFromSymbol(clk, HIP_SYMBOL(g_potrf_clk), sizeof(clk)) == hipSuccess) {
-      static const char* names[9] = {"load", "rank-4 steps", "-", "-", "-", "store L", "-", "inverse", "store Linv"};
-      fprintf(stderr, "[k_chol_potrf2, last launch, us into the rank-4 loop at step 1 / 8 / 16 / 24: %.1f %.1f %.1f %.1f]\n", (double)(clk[10] - clk[1]) * 0.01,
-              (double)(clk[11] - clk[1]) * 0.01, (double)(clk[12] - clk[1]) * 0.01, (double)(clk[13] - clk[1]) * 0.01);
-      fprintf(stderr, "[k_chol_potrf2, last launch, triangular inverse: levels 4 + 8 %.1f us, level 16 %.1f us, levels 32 + 64 %.1f us]\n", (double)(clk[14] - clk[7]) * 0.01,
-              (double)(clk[15] - clk[14]) * 0.01, (double)(clk[8] - clk[15]) * 0.01);
-      fprintf(stderr, "[k_chol_potrf2, last launch, us]");
-      for (int k = 0; k < 9; ++k) fprintf(stderr, " %s=%.1f", names[k], (double)(clk[k + 1] - clk[k]) * 0.01);
-      fprintf(stderr, "\n");
-    }
-  }
+  if (chol_rt(c).sw.timing) chol_print_timing(n);
   *ms_out = ms;
   *rel_residual_out = h2[1] > 0 ? std::sqrt(h2[0] / h2[1]) : 0.0;
   if (hinfo & 2) { set_error("self test: a device-side hand-off of the dense solver timed out"); rc = ESL_ERR_HIP; }
@@ -1405,7 +1338,7 @@ extern "C" int esl_debug_chol_plan(int32_t n, int32_t W, int32_t filler, int32_t
                                    int32_t* ns_out /* np x nR */, int64_t cap_ns, int32_t meta_out[5] /* np, n_outer, nR, n_tasks, W */) {
   if (n < 1 || W < 1 || !meta_out) return ESL_ERR_INVALID;
   esl::CholPlan pl;
-  esl::chol_plan_build(n, W, filler, pl, esl::chol_fuse_default(), esl::chol_merge_default(n), esl::chol_strip_merge_default(), std::min(esl::chol_special_default(), (int)W));
+  esl::chol_plan_from_switches(esl::chol_switches_from_env(), n, W, filler, pl);   // (a fresh read per call: the tests change the plan switches between calls)
   meta_out[0] = pl.np; meta_out[1] = pl.n_outer; meta_out[2] = pl.nR; meta_out[3] = (int32_t)pl.tasks.size(); meta_out[4] = pl.W;
   if (tasks_out) {
     if ((int64_t)pl.tasks.size() > cap_tasks) return ESL_ERR_INVALID;

@@ -116,7 +116,7 @@ static __global__ __launch_bounds__(256, 2) void k_update_v4(double* __restrict_
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
 int main(int argc, char** argv) {
   const long n = argc > 1 ? atol(argv[1]) : 18000, K = argc > 2 ? atol(argv[2]) : 3744;
-  const int stair = argc > 3 ? atoi(argv[3]) : 0, sb = argc > 4 ? atoi(argv[4]) : 0;
+  const int stair = argc > 3 ? atoi(argv[3]) : 0;   // (argv[4]: unused, once the retired tile order)
   const long rows = n + 1, lda = (rows + 127) / 128 * 128, ldx = lda;
   std::vector<double> hX((size_t)ldx * K), hM((size_t)lda * n);
   unsigned long long s = 12345;
@@ -138,8 +138,8 @@ int main(int argc, char** argv) {
                        stair ? dkf : nullptr);
   };
   auto run_new = [&](double* M) {
-    const long ntI = (rows + 127) / 128, ntJ = (n + 127) / 128, nblk = chol_v_grid(ntI, sb);
-    hipLaunchKernelGGL(k_chol_update_v, dim3((unsigned)nblk), dim3(256), kCholLdsV, st, M, lda, rows, n, 0, (int)K, 0L, (int)ntJ, 0, dX, ldx, stair ? dkf : nullptr, sb);
+    const long ntI = (rows + 127) / 128, ntJ = (n + 127) / 128, nblk = chol_v_grid(ntI);
+    hipLaunchKernelGGL(k_chol_update_v, dim3((unsigned)nblk), dim3(256), kCholLdsV, st, M, lda, rows, n, 0, (int)K, 0L, (int)ntJ, 0, dX, ldx, stair ? dkf : nullptr);
   };
   const int v4 = argc > 5 ? atoi(argv[5]) : 0;   // 41: two fragment sets, 42: one
   auto run_v4 = [&](double* M) {
@@ -158,7 +158,7 @@ int main(int argc, char** argv) {
       float ms; CK(hipEventElapsedTime(&ms, e0, e1)); best = std::min(best, ms);
     }
     const double fl = (double)K * rows * n;   // lower triangle, 2 flops per term
-    printf("%s  n=%ld K=%ld stair=%d sb=%d  %8.3f ms  %6.2f TF (full-triangle flops) = %.3f of 78.6\n", which ? (v4 == 41 ? "v4 (j two ahead)" : v4 == 42 ? "v4, 1 frag set  " : "v(128x128 x2/CU)") : "lds(256x128)    ", n, K, stair, which ? sb : 0, best, fl / best / 1e9,
+    printf("%s  n=%ld K=%ld stair=%d  %8.3f ms  %6.2f TF (full-triangle flops) = %.3f of 78.6\n", which ? (v4 == 41 ? "v4 (j two ahead)" : v4 == 42 ? "v4, 1 frag set  " : "v(128x128 x2/CU)") : "lds(256x128)    ", n, K, stair, best, fl / best / 1e9,
            fl / best / 1e9 / 78.6);
   }
   std::vector<double> r1(hM.size()), r2(hM.size());

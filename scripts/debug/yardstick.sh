@@ -9,7 +9,6 @@ scripts/debug/bin/tile_probe_v
 echo; echo "== C -= X^T X, n = 18,000, K = 3,744: k_chol_update_lds<256,128> against k_chol_update_v on the same data, bit for bit  [scripts/debug/upd_v_probe.hip]"
 echo "-- dense X"; scripts/debug/bin/upd_v_probe 18000 3744 0 0
 echo "-- X with a staircase of leading zero rows (12 % of the products skipped, as esl_cf.hpp's)"; scripts/debug/bin/upd_v_probe 18000 3744 1 0
-echo "-- tile order by 8 x 8 blocks per XCD"; scripts/debug/bin/upd_v_probe 18000 3744 0 8 | grep "^v("
 echo "-- n = 16,384, K = 512 (a trailing update of the factorisation)"; scripts/debug/bin/upd_v_probe 16384 512 0 0
 echo; echo "== PMC passes over the dense-X run (per dispatch, medians)  [scripts/debug/pmc_probe.sh]"
 bash scripts/debug/pmc_probe.sh gpurun_out/pmc_y scripts/debug/bin/upd_v_probe 18000 3744 0 0 > /dev/null 2>&1

@@ -260,6 +260,23 @@ def test_persistent_cholesky_without_the_fused_chain(pkg, monkeypatch, n):
     assert res < 1e-13
 
 
+def test_back_substitution_launch_form(pkg, monkeypatch):
+    """ESL_CHOL_BACKSUB_LAUNCHES=1: the launch-per-panel back-substitution (k_chol_backdot + k_chol_backsolve per panel, last panel first)
+    -- the A/B form of k_chol_backsub and the fallback for an odd leading dimension or an unaligned base.  130: two panels, the second
+    ragged (ESL_CHOL_SMALL=0, or k_chol_small would substitute by itself); 257: three panels, the last of one row; 777: seven panels.
+    Same generated systems and the same bound as test_dense_cholesky_selftest_residual."""
+    monkeypatch.setenv("ESL_CHOL_BACKSUB_LAUNCHES", "1")
+    monkeypatch.setenv("ESL_CHOL_SMALL", "0")
+    cx = pkg.Context(0)
+    try:
+        out = [(n,) + tuple(cx.selftest_cholesky(n)) for n in (130, 257, 777)]
+    finally:
+        cx.close()
+    print("launch-per-panel back-substitution: (n, ms, residual)", out)
+    for n, ms, res in out:
+        assert res < 1e-12, (n, res)
+
+
 def test_slam_runs_are_bitwise_reproducible(pkg, ctx):
     """SLAM mode has no order-dependent reduction left (round 1's Schur complement scattered into S with fp64 atomics): the
     same graph twice gives the same bits, trace and states."""
