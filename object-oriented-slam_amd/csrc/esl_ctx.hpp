@@ -67,6 +67,9 @@ struct DevGraph {
   int shard_rank = 0;
 };
 
+// doubles in the camera-side record of one edge: A = Jc^T w Jc (21 packed) and g = -Jc^T w r (6)
+constexpr int kARec = 27;
+
 // edges of FIXED ellipsoids (esl_graph_upload_fixed; kernels: esl_fixed.hpp)
 struct AnchGraph {
   int n_bb = 0, n_e3 = 0;           // anchored edges: [0, n_bb) / [0, n_e3), sorted by camera slot (stable)
@@ -104,7 +107,7 @@ inline void robust_dispatch(bool on, F&& f) {
   else f(std::false_type{});
 }
 
-struct ChunkTableFwd;
+struct HostImage;   // esl_graph.hip
 struct LmState {
   bool begun = false;
   esl_lm_params p;
@@ -192,7 +195,6 @@ struct esl_ctx {
   size_t prof_used = 0;
   int64_t prof_count[ESL_PROF_KINDS] = {0};
   double prof_ms[ESL_PROF_KINDS] = {0};
-  size_t cap_cams = 0, cap_objs = 0;
   // host copies kept from upload (edge -> camera after sorting by ellipsoid)
   std::vector<int> h_bb_cam, h_bb_obj, h_e3_cam, h_e3_obj, h_cam_slot, h_od_i, h_od_j;
   // chunked mapping-mode pipeline (esl_kernels_chunk.hpp)
@@ -208,10 +210,10 @@ struct esl_ctx {
   double* blk_chi = nullptr;     // per-workgroup chi2 of the last linearisation
   unsigned int* tickets = nullptr;  // 2 arrival counters
   double* dev_scal = nullptr;    // {chi2_lin, max_diag}
-  void* append_img = nullptr;    // host image of the appendable layout (esl_graph_append, esl_capi.hip)
+  esl::HostImage* append_img = nullptr;   // host image of the appendable layout (esl_graph_append, esl_graph.hip)
   char* append_dev = nullptr; size_t append_dev_cap = 0;   // device scratch of an append's staged blob
-  char* slam_tab_dev = nullptr; size_t slam_tab_cap = 0;   // SLAM-mode append: the camera-side tables + odometry arrays, rebuilt per append (esl_capi.hip)
-  // grow-only arenas behind esl_graph_upload (esl_capi.hip)
+  char* slam_tab_dev = nullptr; size_t slam_tab_cap = 0;   // SLAM-mode append: the camera-side tables + odometry arrays, rebuilt per append (esl_graph.hip)
+  // grow-only arenas behind esl_graph_upload (esl_graph.hip)
   char* arena_graph = nullptr; size_t arena_graph_cap = 0;
   char* arena_work = nullptr;  size_t arena_work_cap = 0;
   char* stage_host = nullptr;  size_t stage_host_cap = 0;   // pinned staging blob

@@ -1,6 +1,6 @@
 // esl_fixed.hpp — fixed ellipsoid vertices (g2o's setFixed on a VertexEllipsoid) and the camera-chain solver.
 //
-// esl_graph_upload_fixed splits the caller's edges on the host (esl_capi.hip):
+// esl_graph_upload_fixed splits the caller's edges on the host (esl_graph.hip):
 //   (a) edges of FREE ellipsoids       -> the ordinary device graph, untouched kernels (a fixed ellipsoid is an ellipsoid without edges)
 //   (b) ANCHORED edges                 -> fixed ellipsoid, free camera: camera-only edges, the arrays below, sorted by camera slot
 //   (c) INACTIVE edges                 -> fixed ellipsoid, fixed camera (g2o's allVerticesFixed): kept behind (b) for esl_edge_chi2 only

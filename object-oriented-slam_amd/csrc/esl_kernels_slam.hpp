@@ -65,9 +65,8 @@ __device__ __forceinline__ void numeric_jac_cam6_loop(const SE3& T, double delta
 }
 
 // per-edge camera-side products: W = Jc^T w Jo written SoA (index k * EU + u); the camera terms A = Jc^T w Jc (21 packed) and
-// g = -Jc^T w r (6) as a per-edge record ([u][27]: the camera gather reads a record as one coalesced row, lane = entry); Y and the
+// g = -Jc^T w r (6) as a per-edge record ([u][kARec], esl_ctx.hpp: the camera gather reads a record as one coalesced row, lane = entry); Y and the
 // pull kernel's copy of W are per-edge records ([u][54])
-constexpr int kARec = 27;
 template <int D>
 __device__ __forceinline__ void store_cam_terms(const double* Jc, const double* Jo, const double* r, double w,
                                                 double* __restrict__ W, double* __restrict__ A, long EU, long u) {

@@ -92,7 +92,7 @@ double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::
 }  // namespace
 
 static void cf_forget(esl_ctx* c);
-// the graph goes away: every interior pointer is forgotten, the arenas stay (esl_capi.hip free_graph)
+// the graph goes away: every interior pointer is forgotten, the arenas stay (esl_graph.hip free_graph)
 void slam_forget(esl_ctx* c) {
   DevGraph& g = c->g;
   g.ue_start = g.ue_id = g.ue_slot = g.cu_start = g.cu_obj = g.cu_id = nullptr;

@@ -9,6 +9,6 @@ make -s
 while [ $# -ge 2 ]; do
   name=$1; flags=$2; shift 2
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -munsafe-fp-atomics $flags -c esl_capi.hip -o variants/$name.capi.o
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o variants/$name.so variants/$name.capi.o esl_slam.o esl_fit.o esl_init.o esl_comm.o esl_plane.o -ldl
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o variants/$name.so variants/$name.capi.o esl_graph.o esl_slam.o esl_fit.o esl_init.o esl_comm.o esl_plane.o -ldl
   echo "built variants/$name.so ($flags)"
 done

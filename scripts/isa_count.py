@@ -69,6 +69,7 @@ def main():
     tag = sys.argv[1] if len(sys.argv) > 1 else "r2"
     res = {}
     res.update(count(assemble("esl_capi.hip", ["-DESL_ISA_PROBE"])))
+    res.update(count(assemble("esl_graph.hip")))
     res.update(count(assemble("esl_slam.hip")))
     res.update(count(assemble("esl_fit.hip", ["-ffp-contract=off"])))
     res.update(count(assemble("esl_init.hip")))

@@ -553,3 +553,83 @@ def test_e3d_half_turn_switch_is_inert_away_from_half_turns_and_validated(pkg, c
         chi.append(ctx.lm_linearize().chi2)
     print("half-turn fixture, chi2 of the one 3-D edge: guarded %.6g, as written %r" % (chi[0], chi[1]))
     assert chi[0] == pytest.approx(sub.e3d_weight[0] * 1.8779e-2 ** 2, rel=2e-3)
+
+
+def chunk_boundary_graph(pkg):
+    """3 ellipsoids with 0 / 64 / 65 bbox and 0 / 32 / 33 3-D edges (no chunk, exactly one full chunk, a full chunk + one edge), 6
+    cameras (camera 0 fixed), odometry between neighbours; the observations of make_graph's 6-camera scene repeated with fresh noise,
+    in shuffled caller order.  Arrival: the edges of camera 5 last (part 2), the others split in halves (parts 0 and 1).
+    Returns (graph in arrival order, cams, objs, part of every bbox edge, part of every 3-D edge)."""
+    g0, c, o, _ = pkg.synth.make_graph(6, 3, 10 ** 6, seed=3, slam=True, frac_3d=1.0)   # ellipsoids 1 and 2 are seen by all six cameras
+    rng = np.random.default_rng(17)
+
+    def edges(cam, obj, meas, w, counts, noise):
+        pick = np.concatenate([np.flatnonzero(obj == k)[np.arange(n) % max(1, int((obj == k).sum()))] for k, n in enumerate(counts)]).astype(int)
+        pick = pick[rng.permutation(len(pick))]
+        part = np.where(cam[pick] == 5, 2, 0)
+        rest = np.flatnonzero(part == 0)
+        part[rest[len(rest) // 2:]] = 1
+        pick, part = pick[np.argsort(part, kind="stable")], np.sort(part)
+        return cam[pick], obj[pick], meas[pick] + noise * rng.standard_normal(meas[pick].shape), w[pick], part
+    *bb, pb = edges(g0.bbox_cam, g0.bbox_obj, g0.bbox_meas.reshape(-1, 4), g0.bbox_weight, (0, 64, 65), 0.5)
+    q_still = np.array([1, 1, 1, 0, 0, 0, 0, 1, 1, 1]) * 0.005    # centre and half axes move, the quaternion stays a unit one
+    *e3, pe = edges(g0.e3d_cam, g0.e3d_obj, g0.e3d_meas.reshape(-1, 10), g0.e3d_weight, (0, 32, 33), q_still)
+    g = pkg.Graph(g0.K, 6, 3, g0.cam_fixed, *bb, *e3, g0.grav_obj, g0.grav_normal, g0.grav_weight, g0.odom_i, g0.odom_j, g0.odom_meas.reshape(-1, 7))
+    assert list(np.bincount(g.bbox_obj, minlength=3)) == [0, 64, 65] and list(np.bincount(g.e3d_obj, minlength=3)) == [0, 32, 33]
+    return g, c, o, pb, pe
+
+
+def test_upload_append_and_flagged_upload_lay_out_the_same_graph(pkg, ctx):
+    """One ellipsoid with more than 64 bbox and more than 32 3-D edges (and one with exactly 64 / 32, one with none) through the three
+    paths that lay a graph out (csrc/esl_graph.hip, rules: esl_graph_layout.hpp): (a) esl_graph_upload of the whole graph, (b) upload
+    of the first half + two appends -- the first forces a re-layout, the second (a new free camera, its odometry edge, its edges; the
+    big ellipsoid crosses its chunk boundaries here) goes into the slack --, (c) esl_graph_upload_fixed with no flag set.  Same
+    chunks, same order inside every ellipsoid and every camera -> the per-edge chi2 of every class (caller order) and one LM run
+    are BITWISE equal.  Then (c) with the 65 / 33-edge ellipsoid fixed against the numpy reference of tests/test_gpu_fixed.py at
+    that file's tolerances."""
+    from tests import fixed_ref as fr
+    from tests.test_gpu_fixed import assert_fixed_untouched, assert_matches_ref
+    g, c, o, pb, pe = chunk_boundary_graph(pkg)
+    p = pkg.default_lm_params(jacobian_mode=1, max_iters=3)
+    bbox = lambda m: (g.bbox_cam[m], g.bbox_obj[m], g.bbox_meas.reshape(-1, 4)[m], g.bbox_weight[m])
+    e3d = lambda m: (g.e3d_cam[m], g.e3d_obj[m], g.e3d_meas.reshape(-1, 10)[m], g.e3d_weight[m])
+    odom = lambda m: (g.odom_i[m], g.odom_j[m], g.odom_meas.reshape(-1, 7)[m])
+
+    def measure():
+        ctx.upload_states(c, o)
+        chi = {k: ctx.edge_chi2(k) for k in ("bbox", "e3d", "grav", "odom")}
+        rep = ctx.optimize_resident(p)
+        return chi, rep, ctx.download_states()
+
+    def same(x, y, what):
+        for k in x[0]:
+            assert np.array_equal(x[0][k][0], y[0][k][0]) and np.array_equal(x[0][k][1], y[0][k][1]), "%s: chi2 / weight of the %s edges differ" % (what, k)
+        assert x[1] == y[1], (what, x[1], y[1])
+        assert np.array_equal(x[2][0], y[2][0]) and np.array_equal(x[2][1], y[2][1]), what
+    # (a)
+    ctx.upload_graph(g)
+    assert ctx.graph_sizes()["relayouts"] == 0
+    a = measure()
+    assert a[1]["iterations"] > 0 and a[1]["chi2_final"] < a[1]["chi2_initial"] and np.all(a[0]["bbox"][1] > 0)
+    # (b)
+    ctx.upload_graph(pkg.Graph(g.K, 5, 3, g.cam_fixed[:5], *bbox(pb == 0), *e3d(pe == 0), g.grav_obj, g.grav_normal, g.grav_weight, *odom(g.odom_j < 5)))
+    ctx.upload_states(c[:5], o)
+    ctx.append_graph(bbox=bbox(pb == 1), e3d=e3d(pe == 1))
+    assert ctx.graph_sizes()["relayouts"] == 1                       # the compact upload had no slack
+    assert (pb == 2).any() and (pe == 2).any()
+    ctx.append_graph(new_cams=c[5:6], new_cam_fixed=[0], bbox=bbox(pb == 2), e3d=e3d(pe == 2), odom=odom(g.odom_j == 5))
+    assert ctx.graph_sizes() == dict(n_cams=6, n_objs=3, n_bbox=129, n_e3d=65, relayouts=1)   # ... and this one fitted it
+    same(a, measure(), "upload + two appends")
+    # (c)
+    ctx.upload_graph(g, obj_fixed=np.zeros(3, np.uint8))
+    assert not ctx.graph_obj_fixed().any()
+    same(a, measure(), "flagged upload, no flag set")
+    # (c) with the big ellipsoid fixed
+    flags = np.array([0, 0, 1], np.uint8)
+    pf = pkg.default_lm_params(jacobian_mode=1, numeric_delta=1e-6)
+    ref = fr.optimize(g, c, o, obj_fixed=flags, delta=1e-6)
+    cg, og, rg = ctx.optimize(g, c, o, pf, obj_fixed=flags)
+    assert list(ctx.graph_obj_fixed()) == [0, 0, 1]
+    assert_fixed_untouched(o, og, flags)
+    assert np.array_equal(cg[0], c[0])
+    assert_matches_ref(rg, cg, og, ref, flags)
