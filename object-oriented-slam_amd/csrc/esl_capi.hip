@@ -134,6 +134,7 @@ int esl_ctx_create(int device_id, esl_ctx** out) {
   ESL_HIP_TRY(hipSetDevice(device_id));
   esl_ctx* c = new esl_ctx();
   c->device = device_id;
+  { const char* ov = std::getenv("ESL_CF_OVERLAP"); c->sw_cf_overlap = (ov && ov[0] >= '0' && ov[0] <= '3') ? ov[0] - '0' : 1; }
   auto init = [&]() -> int {
     ESL_HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     ESL_HIP_TRY(hipHostMalloc((void**)&c->host_part, 16 * sizeof(double), hipHostMallocDefault));
@@ -163,6 +164,8 @@ int esl_ctx_create(int device_id, esl_ctx** out) {
 int esl_ctx_destroy(esl_ctx* c) {
   if (!c) return ESL_OK;
   (void)hipSetDevice(c->device);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);   // a trial may still be in flight (optimize_resident returns before the GPU is idle)
+  slam_sync_side(c);
   free_graph(c);
   slam_release(c);
   if (c->arena_graph) (void)hipFree(c->arena_graph);

@@ -231,16 +231,21 @@ static __global__ __launch_bounds__(64) void k_cf_factor_blocks(int nf, const do
 // thread = (list entry k, ellipsoid column b) or, behind those, one per free camera.  Records in LIST order ([k][b][a], a = camera
 // row): the forward substitution finds the record of entry k of column b without going through the edge id.  bbox edges dropped by
 // the NaN / visibility pre-check get V = 0 (the lists still hold them).
+// cls (with the nested dissection's stride): 0 = every entry; 1 = the entries of INTERIOR slots only, 2 = those of SEPARATOR slots
+// (slot % stride == stride - 1) only -- the interior entries need L_ii^-1 of the segments' chains alone, so esl_slam.hip launches
+// class 1 while the separators' own chain is still running and class 2 behind it.  Same arithmetic, same addresses: the two
+// launches together write what one launch of class 0 writes.
 __device__ __forceinline__ void cf_edge_scale_one(const DevGraph& g, int n_list, const int* __restrict__ oe_u, const int* __restrict__ oe_slot,
                                                   const double* __restrict__ W, const double* __restrict__ Linv,
                                                   const double* __restrict__ bc, double* __restrict__ V,
-                                                  double* __restrict__ vy, long t) {
+                                                  double* __restrict__ vy, long t, int cls = 0, int stride = 0) {
   const long EU = (long)g.n_bbox + g.n_e3d;
   if (t < (long)n_list * 9) {
     const long k = t / 9;
     const int b = (int)(t - k * 9);
-    const long u = oe_u[k];
     const int slot = oe_slot[k];
+    if (cls != 0 && (slot % stride == stride - 1) != (cls == 2)) return;
+    const long u = oe_u[k];
     const bool valid = !(u < g.n_bbox) || g.bb_valid[u];
     double w[6];
 #pragma unroll
@@ -256,6 +261,7 @@ __device__ __forceinline__ void cf_edge_scale_one(const DevGraph& g, int n_list,
   } else {
     const long s = t - (long)n_list * 9;
     if (s >= g.n_free_cams) return;
+    if (cls != 0 && (s % stride == stride - 1) != (cls == 2)) return;
     const double* Li = Linv + (size_t)s * 36;
     double w[6];
 #pragma unroll
@@ -272,8 +278,8 @@ __device__ __forceinline__ void cf_edge_scale_one(const DevGraph& g, int n_list,
 static __global__ __launch_bounds__(256) void k_cf_edge_scale(DevGraph g, int n_list, const int* __restrict__ oe_u, const int* __restrict__ oe_slot,
                                                               const double* __restrict__ W, const double* __restrict__ Linv,
                                                               const double* __restrict__ bc, double* __restrict__ V,
-                                                              double* __restrict__ vy) {
-  cf_edge_scale_one(g, n_list, oe_u, oe_slot, W, Linv, bc, V, vy, (long)blockIdx.x * 256 + threadIdx.x);
+                                                              double* __restrict__ vy, int cls, int stride) {
+  cf_edge_scale_one(g, n_list, oe_u, oe_slot, W, Linv, bc, V, vy, (long)blockIdx.x * 256 + threadIdx.x, cls, stride);
 }
 
 // ---- X = L^-1 [W | b_c]: one lane per column (9 per ellipsoid + the right-hand side), sequential over the cameras -----------

@@ -169,22 +169,28 @@ struct CholRuntime {
   // optional event bracket around the FACTORISATION alone (not the back-substitution): mark(user, 1) before, mark(user, 0) after
   void (*prof_mark)(void* user, int begin) = nullptr;
   void* prof_user = nullptr;
-  hipStream_t cf_side = nullptr;                            // camera-first elimination: the segments' products run here beside the rank-K update (esl_slam.hip)
-  hipEvent_t cf_ev_x = nullptr, cf_ev_p = nullptr;
+  // camera-first elimination (esl_slam.hip): the separators' chain runs here beside the interior rows' pipeline, then the segments'
+  // products beside the separators' forward recurrence and the rank-K update.  cf_ev_a: the separators' system is assembled (main
+  // stream); cf_ev_s: their chain's blocks are written (side); cf_ev_x: the slabs are complete (main); cf_ev_p: the products are (side)
+  hipStream_t cf_side = nullptr;
+  hipEvent_t cf_ev_x = nullptr, cf_ev_p = nullptr, cf_ev_a = nullptr, cf_ev_s = nullptr;
   hipError_t cf_overlap_init() {
-    if (cf_side) return hipSuccess;
+    if (cf_side && cf_ev_x && cf_ev_p && cf_ev_a && cf_ev_s) return hipSuccess;
+    if (cf_side) return hipErrorNotReady;   // (an earlier attempt failed half way: the serial order)
     // (a plain second stream.  Two full-size grids on two streams do not run side by side -- the second kernel's workgroups are placed
     //  when the first one's are all dispatched -- and with the side stream confined to every 2nd / 4th / 8th CU of every XCD
     //  (hipExtStreamCreateWithCUMask) the products simply ran later AND slower: the bracket around T's build 29.3 -> 32.9 / 40.7 / 57.2 ms.
     //  What the second stream does give: the products fill the update's last, partly empty round of tiles: 30.0 -> 29.3 ms.)
     hipError_t e = hipStreamCreateWithFlags(&cf_side, hipStreamNonBlocking); if (e != hipSuccess) return e;
-    e = hipEventCreateWithFlags(&cf_ev_x, hipEventDisableTiming); if (e != hipSuccess) return e;
-    return hipEventCreateWithFlags(&cf_ev_p, hipEventDisableTiming);
+    for (hipEvent_t* ev : {&cf_ev_x, &cf_ev_p, &cf_ev_a, &cf_ev_s}) {
+      e = hipEventCreateWithFlags(ev, hipEventDisableTiming); if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
   }
   void release() {
-    if (cf_side) { (void)hipStreamDestroy(cf_side); cf_side = nullptr; }
-    if (cf_ev_x) { (void)hipEventDestroy(cf_ev_x); cf_ev_x = nullptr; }
-    if (cf_ev_p) { (void)hipEventDestroy(cf_ev_p); cf_ev_p = nullptr; }
+    if (cf_side) { (void)hipStreamSynchronize(cf_side); (void)hipStreamDestroy(cf_side); cf_side = nullptr; }
+    for (hipEvent_t* ev : {&cf_ev_x, &cf_ev_p, &cf_ev_a, &cf_ev_s})
+      if (*ev) { (void)hipEventDestroy(*ev); *ev = nullptr; }
     if (bs_flags) { (void)hipFree(bs_flags); bs_flags = nullptr; bs_flags_cap = 0; }
     if (d_tasks) { (void)hipFree(d_tasks); d_tasks = nullptr; d_tasks_cap = 0; }
     if (d_ns) { (void)hipFree(d_ns); d_ns = nullptr; d_ns_cap = 0; }

@@ -120,6 +120,8 @@ void slam_release(esl_ctx* c) { slam_forget(c); blob_release(c->arena_slam); blo
 // esl_ctx_trim: drop the solver blobs (tens of GB at BASELINE configs[3]); the next trial step that needs one builds it again.
 // keep_lists: the resident graph has free cameras, so arena_slam (its lists, W, Y ...) is still in use.
 void slam_trim(esl_ctx* c, bool keep_lists) {
+  slam_sync_side(c);   // (every trial joins the side stream to the context's stream, which the callers have waited for: a host wait of its own
+                       //  before what it reads is freed)
   cf_forget(c);
   c->S = c->Linv_ws = nullptr;
   c->cf_unavailable = false;
@@ -578,21 +580,62 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
     const bool nd = st > 0 && ns > 0;
     const unsigned cg = (unsigned)((n_o + 1 + 63) / 64);
     const long nt = (long)c->cf_n_list * 9 + nf;
-    // V = Li W, vy = Li b_c; X dense: the same launch writes the whole of T (D's lower blocks, b_o's row, zeros) -- nothing reads T before
-    // the rank-K update further down
-    auto launch_edge_scale = [&]() {
+    // this rank's columns of T: everything, or with the replicated-graph communicator its outer panels (dealt cyclically, as the
+    // distributed factorisation below expects them)
+    const int Wp = chol_outer_panels(n_o), n_outer = ((n_o + kNB - 1) / kNB + Wp - 1) / Wp;
+    const bool dist = cf_dist(c);
+    const int Ks_ = (int)c->cf_kpad_s;
+    ESL_HIP_TRY(chol_set_attributes(rt));   // (fills rt.sw)
+    // The side-stream order (single rank, nested dissection, X kept sparse with stored products; ESL_CF_OVERLAP=0 when the context was
+    // created: everything below in stream order).  Two dependent chains meet only at k_cf_sep_rhs:
+    //   interior    k_cf_edge_scale (interior slots) -> k_cf_forward<2> -> the segments' products (k_cf_seg_syrk, k_cf_seg_rhs)
+    //   separators  k_cf_chain (one wave, n_sep steps) -> k_cf_factor_blocks -> V, vy of the separator slots -> [k_cf_forward<2>'s slabs
+    //               and sums] -> k_cf_sep_rhs -> k_cf_forward<1> (one wave per 64 columns) -> the rank-K update
+    // so (1) the separators' chain and its blocks run on rt.cf_side beside the interior pipeline -- enqueued FIRST: a small grid is
+    // resident at once and a full grid on the other stream fills the rest of the GPU (two full grids do not share it: esl_chol.hpp,
+    // cf_overlap_init) -- and (2) the products, which need the slabs alone, run on rt.cf_side beside k_cf_forward<1> and the update.
+    // No arithmetic and no address changes, so every array has the bits of the serial order.
+    // Across trials: the side chain of trial t + 1 writes cf_LfacS, cf_GS, cf_LiS, cf_MS, cf_NS and the separators' slots of cf_Linv,
+    // which trial t's k_cf_edge_scale (separator slots), k_cf_sep_rhs, k_cf_forward<1>, k_cf_tridiag_back and k_cf_back_prep read: all of
+    // them are on the main stream in front of trial t + 1's cf_ev_a, which the side chain waits for.  Trial t + 1's k_cf_forward<2>
+    // writes the slabs trial t's products read: the main stream has waited for trial t's cf_ev_p.  cf_ensure's relayout, esl_ctx_trim
+    // and everything else on the main stream are covered the same way, because every way out of this function leaves the side
+    // stream joined to the main one (CfSideJoin).
+    const bool side = c->sw_cf_overlap != 0 && nd && c->cf_sparse && c->cf_sp_form == 1 && !dist && Ks_ > 0 && rt.cf_overlap_init() == hipSuccess;
+    // with the update on its k_chol_update_v path (the one with an assign form) the products also run beside the UPDATE (round 6): it
+    // ASSIGNS T = -Xs^T Xs instead of updating what the gather wrote, and the gather, which then comes last, adds its D - sum to that --
+    // (D - sum) + (-acc) is the same double as (D - sum) - acc, so T has the same bits
+    const bool assign = side && chol_update_v_applies(rt.sw, ldt, (long)n_o + 1, 0, (long)n_o, true, ldx);
+    const bool side_chain = side && c->sw_cf_overlap != 3, early_products = side && c->sw_cf_overlap != 2;   // (each alone: A/B)
+    struct CfSideJoin {   // side-stream work not yet waited for by the main stream when the function is left (an ESL_HIP_TRY failure): joined here
+      CholRuntime& rt; hipStream_t main; bool armed;
+      hipError_t wait(hipEvent_t ev) { const hipError_t e = hipStreamWaitEvent(main, ev, 0); armed = e != hipSuccess; return e; }
+      ~CfSideJoin() {
+        if (!armed) return;
+        if (hipEventRecord(rt.cf_ev_p, rt.cf_side) != hipSuccess || hipStreamWaitEvent(main, rt.cf_ev_p, 0) != hipSuccess) (void)hipStreamSynchronize(rt.cf_side);
+      }
+    } join{rt, c->stream, false};
+    // V = Li W, vy = Li b_c (cls: esl_cf.hpp -- 0 all list entries, 1 / 2 those of interior / separator slots); X dense: the same launch
+    // writes the whole of T (D's lower blocks, b_o's row, zeros) -- nothing reads T before the rank-K update further down
+    auto launch_edge_scale = [&](int cls) {
       const int nb_es = (int)((nt + 255) / 256);
       if (!c->cf_sparse)
         hipLaunchKernelGGL(k_cf_edge_scale_T, dim3((unsigned)(nb_es + (int)((ldt * (long)n_o + 255) / 256))), dim3(256), 0, c->stream, g, nb_es, c->cf_n_list, c->cf_oe_u,
                            c->cf_oe_slot, c->Wbb, c->cf_Linv, c->bc, c->cf_V, c->cf_vy, c->Hoo, c->bo, lambda, c->cf_T, ldt, (long)n_o);
       else
         hipLaunchKernelGGL(k_cf_edge_scale, dim3((unsigned)nb_es), dim3(256), 0, c->stream, g, c->cf_n_list, c->cf_oe_u, c->cf_oe_slot, c->Wbb, c->cf_Linv, c->bc,
-                           c->cf_V, c->cf_vy);
+                           c->cf_V, c->cf_vy, cls, st);
+    };
+    auto launch_products = [&](hipStream_t st2) {
+      hipLaunchKernelGGL(k_cf_seg_syrk, dim3((unsigned)c->cf_n_twork), dim3(256), 0, st2, c->cf_twork, c->cf_seg_start, c->cf_seg_first, c->cf_xoff,
+                         c->cf_xld, c->cf_Xc, c->cf_boff, c->cf_P);
+      hipLaunchKernelGGL(k_cf_seg_rhs, dim3((unsigned)c->cf_n_fwork), dim3(64), 0, st2, c->cf_fwork, c->cf_seg_start, c->cf_xoff, c->cf_xld, c->cf_Xc,
+                         c->cf_roff, c->cf_Prhs);
     };
     if (!nd) {
       hipLaunchKernelGGL(k_cf_chain, dim3(1), dim3(64), 0, c->stream, nf, c->Hcc, c->cf_B, lambda, c->cf_Lfac, c->cf_G, c->chol_info, nf, nf);
       hipLaunchKernelGGL(k_cf_factor_blocks, dim3((unsigned)((nf + 63) / 64)), dim3(64), 0, c->stream, nf, c->cf_Lfac, c->cf_G, c->cf_Linv, c->cf_M, c->cf_N, 0);
-      launch_edge_scale();
+      launch_edge_scale(0);
       hipLaunchKernelGGL(k_cf_forward<0>, dim3(cg), dim3(64), 0, c->stream, nf, n_o, c->cf_n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V, c->cf_vy,
                          c->cf_M, c->cf_Xt, ldx, nf, nf, (const double*)nullptr, (double*)nullptr, 0, CfSegs{});
     } else {   // nested dissection (esl_cf.hpp): segments in parallel, then the separators' own short chain
@@ -601,10 +644,22 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
       if (nseg > 1) hipLaunchKernelGGL(k_cf_zt, dim3((unsigned)(nseg - 1)), dim3(64), 0, c->stream, nf, st, c->cf_Linv, c->cf_M, c->cf_B, c->cf_Zt);
       hipLaunchKernelGGL(k_cf_sep_assemble, dim3((unsigned)((ns * 36 + 255) / 256)), dim3(256), 0, c->stream, nf, st, ns, c->Hcc, lambda, c->cf_G, c->cf_Zt,
                          c->cf_Hs, c->cf_Bs);
-      hipLaunchKernelGGL(k_cf_chain, dim3(1), dim3(64), 0, c->stream, ns, c->cf_Hs, c->cf_Bs, 0.0, c->cf_LfacS, c->cf_GS, c->chol_info, ns, ns);
-      hipLaunchKernelGGL(k_cf_factor_blocks, dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, c->stream, ns, c->cf_LfacS, c->cf_GS, c->cf_LiS, c->cf_MS, c->cf_NS, 0,
-                         c->cf_Linv, st);   // (+ the separators' L_ii^-1 into the per-slot array: was k_cf_sep_scatter)
-      launch_edge_scale();
+      auto launch_sep_chain = [&](hipStream_t st2) {
+        hipLaunchKernelGGL(k_cf_chain, dim3(1), dim3(64), 0, st2, ns, c->cf_Hs, c->cf_Bs, 0.0, c->cf_LfacS, c->cf_GS, c->chol_info, ns, ns);
+        hipLaunchKernelGGL(k_cf_factor_blocks, dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, st2, ns, c->cf_LfacS, c->cf_GS, c->cf_LiS, c->cf_MS, c->cf_NS, 0,
+                           c->cf_Linv, st);   // (+ the separators' L_ii^-1 into the per-slot array: was k_cf_sep_scatter)
+      };
+      if (side_chain) {
+        ESL_HIP_TRY(hipEventRecord(rt.cf_ev_a, c->stream));
+        ESL_HIP_TRY(hipStreamWaitEvent(rt.cf_side, rt.cf_ev_a, 0));
+        join.armed = true;
+        launch_sep_chain(rt.cf_side);
+        ESL_HIP_TRY(hipEventRecord(rt.cf_ev_s, rt.cf_side));
+        launch_edge_scale(1);
+      } else {
+        launch_sep_chain(c->stream);
+        launch_edge_scale(0);
+      }
       if (!c->cf_sparse) {
         hipLaunchKernelGGL(k_cf_forward<0>, dim3(cg, (unsigned)nseg), dim3(64), 0, c->stream, nf, n_o, c->cf_n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V,
                            c->cf_vy, c->cf_M, c->cf_Xt, ldx, st, st - 1, (const double*)c->cf_Zt, c->cf_R, st, CfSegs{});
@@ -616,32 +671,25 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
         const CfSegs sg{c->cf_fwork, c->cf_seg_start, c->cf_seg_obj, c->cf_xoff, c->cf_xld, c->cf_rank, c->cf_unrank};
         hipLaunchKernelGGL(k_cf_forward<2>, dim3((unsigned)c->cf_n_fwork), dim3(64), 0, c->stream, nf, n_o, c->cf_n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V,
                            c->cf_vy, c->cf_M, c->cf_Xc, ldx, st, st - 1, (const double*)c->cf_Zt, c->cf_R, st, sg);
+        if (side_chain) {   // the separators' chain is needed from here on: their V and vy, then the right-hand sides
+          ESL_HIP_TRY(join.wait(rt.cf_ev_s));
+          launch_edge_scale(2);
+        }
         hipLaunchKernelGGL(k_cf_sep_rhs, dim3(cg, (unsigned)ns), dim3(64), 0, c->stream, nf, n_o, st, c->cf_n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V, c->cf_vy,
                            c->cf_G, c->cf_LiS, c->cf_Xc, ldx, c->cf_R, (const int*)c->cf_cmap, sg);
+        if (early_products) ESL_HIP_TRY(hipEventRecord(rt.cf_ev_x, c->stream));   // (the slabs were complete after k_cf_forward<2>; k_cf_sep_rhs only reads them)
         hipLaunchKernelGGL(k_cf_forward<1>, dim3(cg), dim3(64), 0, c->stream, ns, n_o, c->cf_n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V, c->cf_vy,
                            c->cf_MS, c->cf_Xs, ldx, ns, ns, (const double*)nullptr, c->cf_R, 0, CfSegs{});
+        if (side) {   // the products behind k_cf_forward<1>'s 282 waves (C4), beside them.  Measured at C4: the products start 1.4 ms
+                      // earlier, k_cf_forward<1> stretches from 0.61 to 1.08 ms beside them, the update starts 0.32 ms earlier
+          if (!early_products) ESL_HIP_TRY(hipEventRecord(rt.cf_ev_x, c->stream));
+          ESL_HIP_TRY(hipStreamWaitEvent(rt.cf_side, rt.cf_ev_x, 0));
+          join.armed = true;
+          launch_products(rt.cf_side);
+          ESL_HIP_TRY(hipEventRecord(rt.cf_ev_p, rt.cf_side));
+        }
       }
     }
-    // this rank's columns of T: everything, or with the replicated-graph communicator its outer panels (dealt cyclically, as the
-    // distributed factorisation below expects them)
-    const int Wp = chol_outer_panels(n_o), n_outer = ((n_o + kNB - 1) / kNB + Wp - 1) / Wp;
-    const bool dist = cf_dist(c);
-    // Round 6: the segments' products (HBM-bound: 16.7 GB written) run on a second stream BESIDE the separators' rank-K update
-    // (MFMA-bound): the update ASSIGNS T = -Xs^T Xs instead of updating what the gather wrote, and the gather, which now comes last,
-    // adds its D - sum to that -- (D - sum) + (-acc) is the same double as (D - sum) - acc, so T has the same bits.  Single rank, X
-    // kept sparse with stored products, the update on its k_chol_update_v path (the one with an assign form); ESL_CF_OVERLAP=0: the
-    // serial order.
-    static const bool overlap_on = !(std::getenv("ESL_CF_OVERLAP") && std::getenv("ESL_CF_OVERLAP")[0] == '0');
-    const int Ks_ = (int)c->cf_kpad_s;
-    ESL_HIP_TRY(chol_set_attributes(rt));   // (fills rt.sw)
-    const bool overlap = overlap_on && c->cf_sparse && c->cf_sp_form == 1 && !dist && Ks_ > 0 &&
-                         chol_update_v_applies(rt.sw, ldt, (long)n_o + 1, 0, (long)n_o, true, ldx) && rt.cf_overlap_init() == hipSuccess;
-    auto launch_products = [&](hipStream_t st2) {
-      hipLaunchKernelGGL(k_cf_seg_syrk, dim3((unsigned)c->cf_n_twork), dim3(256), 0, st2, c->cf_twork, c->cf_seg_start, c->cf_seg_first, c->cf_xoff,
-                         c->cf_xld, c->cf_Xc, c->cf_boff, c->cf_P);
-      hipLaunchKernelGGL(k_cf_seg_rhs, dim3((unsigned)c->cf_n_fwork), dim3(64), 0, st2, c->cf_fwork, c->cf_seg_start, c->cf_xoff, c->cf_xld, c->cf_Xc,
-                         c->cf_roff, c->cf_Prhs);
-    };
     auto launch_gather = [&](int accumulate) {
       for (int op = dist ? c->comm_rank : 0; op < (dist ? n_outer : 1); op += dist ? c->comm_ranks : 1) {
         const long c_begin = dist ? (long)op * Wp * kNB : 0, c_end = dist ? std::min<long>((long)(op + 1) * Wp * kNB, (long)n_o) : (long)n_o;
@@ -655,33 +703,7 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
                              lambda, c->cf_T, ldt, o2b, o2e, (const int*)c->cf_unrank);
       }
     };
-    if (overlap) {
-      // (the slabs Xc were complete after k_cf_forward<2>; the event is recorded here, behind the separators' short chain, which the
-      //  products do not need but which costs them 0.3 ms of head start at most)
-      ESL_HIP_TRY(hipEventRecord(rt.cf_ev_x, c->stream));
-      ESL_HIP_TRY(hipStreamWaitEvent(rt.cf_side, rt.cf_ev_x, 0));
-      launch_products(rt.cf_side);
-      ESL_HIP_TRY(hipEventRecord(rt.cf_ev_p, rt.cf_side));
-      {
-        ProfScope pk(c, 7);   // the rank-K update (assign form), with the products running beside it
-        chol_launch_update(rt.sw, c->cf_T, ldt, (long)n_o + 1, c->stream, 0, Ks_, 0, (long)n_o, c->cf_Xs, ldx, nullptr, c->cf_kfirst, true);
-      }
-      ESL_HIP_TRY(hipStreamWaitEvent(c->stream, rt.cf_ev_p, 0));
-      {
-        ProfScope pk(c, 8);   // (what is left of the products' path on this stream: the gather)
-        launch_gather(1);
-      }
-      ESL_HIP_TRY(hipGetLastError());
-    } else {
-    if (!c->cf_sparse) {   // (T was written whole by the edge-scale launch)
-    } else {   // T = D - (interior rows)^T (interior rows), block by block (every block on and below the diagonal is written)
-      ProfScope pk(c, 8);
-      if (c->cf_sp_form == 1)   // the segments' products (all of them on every rank: 3 % of a trial)
-        launch_products(c->stream);
-      launch_gather(0);
-    }
-    ESL_HIP_TRY(hipGetLastError());
-    {
+    auto launch_update = [&]() {   // T -= X^T X over the rows of X that are dense: all of them, or (X sparse) the separators'
       ProfScope pk(c, 7);   // the rank-K update alone (nested in class 2): the MFMA roofline kernel of this form
       const double* Xf = c->cf_sparse ? c->cf_Xs : c->cf_Xt;
       const int K = (int)(c->cf_sparse ? c->cf_kpad_s : c->cf_kpad);
@@ -693,7 +715,34 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
       } else if (K > 0) {
         chol_launch_update(rt.sw, c->cf_T, ldt, (long)n_o + 1, c->stream, 0, K, 0, (long)n_o, Xf, ldx, c->cf_part, c->cf_sparse ? c->cf_kfirst : nullptr);
       }
-    }
+    };
+    if (assign) {
+      {
+        ProfScope pk(c, 7);   // the rank-K update (assign form), with the products running beside it
+        chol_launch_update(rt.sw, c->cf_T, ldt, (long)n_o + 1, c->stream, 0, Ks_, 0, (long)n_o, c->cf_Xs, ldx, nullptr, c->cf_kfirst, true);
+      }
+      ESL_HIP_TRY(join.wait(rt.cf_ev_p));
+      {
+        ProfScope pk(c, 8);   // (what is left of the products' path on this stream: the gather)
+        launch_gather(1);
+      }
+    } else if (side) {   // (the update has no assign form at this size: the products ran beside k_cf_forward<1> alone)
+      ESL_HIP_TRY(join.wait(rt.cf_ev_p));
+      {
+        ProfScope pk(c, 8);
+        launch_gather(0);
+      }
+      ESL_HIP_TRY(hipGetLastError());
+      launch_update();
+    } else {
+      if (c->cf_sparse) {   // T = D - (interior rows)^T (interior rows), block by block (every block on and below the diagonal is written)
+        ProfScope pk(c, 8);   // (X dense: T was written whole by the edge-scale launch)
+        if (c->cf_sp_form == 1)   // the segments' products (all of them on every rank: 3 % of a trial)
+          launch_products(c->stream);
+        launch_gather(0);
+      }
+      ESL_HIP_TRY(hipGetLastError());
+      launch_update();
     }
     ESL_HIP_TRY(hipGetLastError());
   }
@@ -759,6 +808,9 @@ static CholRuntime& chol_rt(esl_ctx* c) {
     c->chol_rt = rt;
   }
   return *(CholRuntime*)c->chol_rt;
+}
+void slam_sync_side(esl_ctx* c) {
+  if (c->chol_rt && ((CholRuntime*)c->chol_rt)->cf_side) (void)hipStreamSynchronize(((CholRuntime*)c->chol_rt)->cf_side);
 }
 void slam_release_runtime(esl_ctx* c) {
   if (c->chol_prof_scope) { delete (ProfScope*)c->chol_prof_scope; c->chol_prof_scope = nullptr; }

@@ -14,4 +14,5 @@ int slam_linearize(esl_ctx* c);
 int slam_build_reduced(esl_ctx* c, double lambda, bool full_sum, void** dev_ptr, int64_t* n);
 int slam_try_step(esl_ctx* c, double lambda);
 void slam_release_runtime(esl_ctx* c);   // the context's CholRuntime (esl_ctx_destroy)
+void slam_sync_side(esl_ctx* c);         // host wait for the camera-first side stream (before anything it reads is freed)
 }  // namespace esl
