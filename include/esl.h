@@ -48,7 +48,8 @@ extern "C" {
                              *    esl_plane_params::max_curvature (PCL's maximum_curvature_ model test; min_inliers is a strict >);
                              *    additive part of 5: robust kernels per edge class (esl_robust_params, esl_lm_set_robust, esl_edge_chi2) --
                              *    detect them by the symbol; likewise fixed ellipsoids (esl_graph_upload_fixed, esl_optimize_fixed,
-                             *    esl_graph_obj_fixed) with ESL_SOLVER_CAMERA_CHAIN */
+                             *    esl_graph_obj_fixed) with ESL_SOLVER_CAMERA_CHAIN, and relocalisation against a fixed map
+                             *    (esl_reloc_set_map, esl_relocalize) */
 #define ESL_MAX_TRACE 32
 
 typedef enum {
@@ -521,6 +522,67 @@ int esl_init_from_qstar(esl_ctx* ctx, const double qstar[16], int32_t faithful, 
  * bbox tangent planes pi of (pi^T Q* pi)^2 for the given ellipsoid (10-vector, world frame). */
 int esl_init_plane_error(esl_ctx* ctx, const double* poses_Twc /* n x 7 */, const double* bboxes /* n x 4 */, int32_t n,
                          const double K[4], int32_t rows, int32_t cols, const double ellipsoid[10], double* error_out);
+
+/* ---- relocalisation: camera pose and detection -> map association with NO pose prior (additive part of ABI 5: detect by the symbol) ---
+ * esl_optimize_fixed refines a pose that is already inside the basin of its edges and needs the edge lists, i.e. which detection is
+ * which map ellipsoid.  esl_relocalize supplies both for one frame: from the frame's single-frame ellipsoids (esl_fit_frame's output,
+ * camera frame), the ground plane seen from the camera and a fixed map with its ground plane, by an exhaustive, deterministic
+ * hypothesise-and-score search on the device.  (The reference's only association, DataAssociationSolver, src/core/DataAssociation.cpp:
+ * 16-135, takes the nearest map centre within 1 m GIVEN the pose; step 6 below is that rule.)
+ *  1. Gravity frames.  A plane (n, d) is normalised by |n|; e_k = the coordinate axis with the smallest |n_k| (lowest k on ties),
+ *     u = normalise(e_k x n), v = n x u, G(x) = [u; v; n] x + (0, 0, d): third coordinate = height above ground.  Map centres give
+ *     p_m = G_w(C_m), detection centres q_d = G_c(c_d); the pose sought is x_w = G_w^-1(Z(yaw, t) G_c(x_c)), Z = rotation by yaw about
+ *     z + (tx, ty, 0).
+ *  2. Candidates: pairs (d, m) that pass the label, height and sorted-size gates of esl_reloc_params, in (d, m) lexicographic order;
+ *     P of them.
+ *  3. Hypotheses: candidate pairs i < j with different detections and different map objects, |q_dj - q_di|_xy >= min_baseline and
+ *     | |q_dj - q_di|_xy - |p_mj - p_mi|_xy | <= 2 center_tol.  yaw = atan2 of the map difference - atan2 of the detection difference,
+ *     t = midpoint(p) - R(yaw) midpoint(q).
+ *  4. Score: every detection takes its nearest candidate by planar distance after the motion and is an inlier when that distance is
+ *     <= center_tol; n = inliers, cost = sum of their squared distances.  Winner: max n, then min cost, then min key i P + j -- a total
+ *     order, so the result does not depend on the order the hypotheses are processed in; runs are bit-reproducible.
+ *  5. refine: closed-form 2-D rigid fit over the winner's inlier pairs (centred; yaw = atan2(sum cross, sum dot), t = mean p -
+ *     R mean q), rescored once and kept only when its (n, cost) is not worse.  Runs from 3 inliers on: two pairs already are their fit.
+ *  6. Association under the final pose: detections in index order, each takes its nearest UNCLAIMED candidate within center_tol.
+ *     n_inliers and cost of the result are those of this association.
+ * The defaults below are design choices, not values tuned on real data. */
+typedef struct {
+  double center_tol;      /* 0.25 m: planar distance below which a moved detection centre matches a map centre */
+  double height_tol;      /* 0.25 m: |height above ground of detection - of map object| for a candidate */
+  double size_ratio;      /* 1.5: candidate needs max_k |log(s_det[k] / s_map[k])| <= log(size_ratio), half-axes SORTED per ellipsoid; <= 1: no size gate */
+  double min_baseline;    /* 0.5 m: smallest planar distance between the two detections of a hypothesis */
+  int32_t min_inliers;    /* 3 */
+  int32_t max_candidates; /* 4096 (at most 1048576) */
+  int32_t match_labels;   /* 1: candidate needs equal labels; 0: labels ignored */
+  int32_t refine;         /* 1: closed-form planar re-fit over the winner's inliers */
+} esl_reloc_params;       /* 48 bytes */
+void esl_reloc_params_default(esl_reloc_params* p);
+
+/* The map: M x 10 world ellipsoids, M labels, the world ground plane.  objs == NULL: take the resident graph's current ellipsoid states
+ * device-to-device (M must equal its n_objs; ESL_ERR_STATE without a graph and states).  The map lives in grow-only device buffers of
+ * its own: it survives esl_graph_upload, esl_graph_append and esl_ctx_trim, and a later change of the resident states does not reach
+ * it.  ESL_ERR_INVALID: null or negative arguments, a plane normal shorter than 1e-12. */
+int esl_reloc_set_map(esl_ctx* ctx, const double* objs, const int32_t* labels, int32_t M, const double ground_world[4]);
+
+typedef struct {
+  int32_t status;         /* 0 found; 1 fewer than 2 candidates or no hypothesis passed the gates; 2 best hypothesis below min_inliers; 3 candidates > max_candidates, nothing scored */
+  int32_t n_candidates;
+  int64_t n_hypotheses;   /* pairs that passed every gate and were scored */
+  int64_t best_key;       /* i * P + j of the winner (candidate indices i < j), -1 when none */
+  int32_t n_inliers;      /* associated detections under the returned pose (status 2: the best hypothesis's inliers) */
+  int32_t refined;        /* 1 if the re-fit pose was kept */
+  double cost;            /* sum of squared planar distances of the associated detections (status 2: of the best hypothesis's inliers) */
+  double yaw, tx, ty;     /* the planar motion in the gravity frames, yaw in (-pi, pi]; zeros unless status 0 */
+  double Twc[7];          /* camera -> world, x y z qx qy qz qw, qw >= 0 */
+} esl_reloc_result;
+
+/* ESL_ERR_INVALID: null or negative arguments, a plane normal shorter than 1e-12, D > 64, non-finite tolerances, max_candidates above
+ * 1048576.  ESL_ERR_STATE: no esl_reloc_set_map before.  Statuses 1-3 are results, not errors: the call returns ESL_OK, Twc holds the
+ * identity (0 0 0 0 0 0 1) and assoc_out is -1 everywhere.  The call leaves the resident graph, its states and its solver blobs alone
+ * and runs on this context's GPU only (on a context with a communicator too: no collective is issued). */
+int esl_relocalize(esl_ctx* ctx, const double* det_objs /* D x 10, camera frame */, const int32_t* det_labels, int32_t D,
+                   const double ground_cam[4], const esl_reloc_params* p /* NULL = defaults */,
+                   esl_reloc_result* out, int32_t* assoc_out /* D: map index or -1; may be NULL */);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------*/
 /* Dense FP64-MFMA Cholesky factor + solve (the reduced-camera solver of SLAM mode) on a procedurally generated,

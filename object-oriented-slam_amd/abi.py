@@ -123,6 +123,36 @@ def default_pcg_params():
     """esl_pcg_params_default: 1000 iterations, a host look at the done flag every 8, rel_tol 1e-10."""
     return EslPcgParams(max_iters=1000, check_every=8, rel_tol=1e-10)
 
+
+class EslRelocParams(C.Structure):
+    """esl_reloc_params: gates and switches of esl_relocalize."""
+    _fields_ = [("center_tol", C.c_double), ("height_tol", C.c_double), ("size_ratio", C.c_double), ("min_baseline", C.c_double),
+                ("min_inliers", C.c_int32), ("max_candidates", C.c_int32), ("match_labels", C.c_int32), ("refine", C.c_int32)]
+
+
+class EslRelocResult(C.Structure):
+    """esl_reloc_result: what esl_relocalize found (status 0) or why it found nothing (1 - 3)."""
+    _fields_ = [("status", C.c_int32), ("n_candidates", C.c_int32), ("n_hypotheses", C.c_int64), ("best_key", C.c_int64),
+                ("n_inliers", C.c_int32), ("refined", C.c_int32), ("cost", C.c_double), ("yaw", C.c_double), ("tx", C.c_double),
+                ("ty", C.c_double), ("Twc", C.c_double * 7)]
+
+    def as_dict(self):
+        return dict(status=self.status, n_candidates=self.n_candidates, n_hypotheses=self.n_hypotheses, best_key=self.best_key,
+                    n_inliers=self.n_inliers, refined=self.refined, cost=self.cost, yaw=self.yaw, tx=self.tx, ty=self.ty,
+                    Twc=np.array(list(self.Twc)))
+
+
+def default_reloc_params(**kw):
+    """esl_reloc_params_default: design choices, not values tuned on real data (include/esl.h)."""
+    p = EslRelocParams(center_tol=0.25, height_tol=0.25, size_ratio=1.5, min_baseline=0.5, min_inliers=3, max_candidates=4096,
+                       match_labels=1, refine=1)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
 ROBUST_KINDS = {"none": 0, "huber": 1, "pseudo_huber": 2, "cauchy": 3, "tukey": 4}   # esl_robust_kind (include/esl.h)
 EDGE_CLASSES = {"bbox": 0, "e3d": 1, "grav": 2, "odom": 3}                         # esl_edge_class
 

@@ -24,6 +24,7 @@ EXPORTS = [
     "esl_states_download", "esl_optimize_resident", "esl_states_snapshot", "esl_states_restore", "esl_profile_enable", "esl_profile_get", "esl_lm_begin", "esl_lm_linearize", "esl_lm_reduced_system", "esl_lm_reduced_residual",
     "esl_lm_try_step", "esl_lm_commit", "esl_lm_solver_used", "esl_lm_solver_stats", "esl_lm_download", "esl_lm_set_robust", "esl_edge_chi2", "esl_pcg_params_default", "esl_lm_set_pcg", "esl_lm_pcg_stats", "esl_comm_unique_id", "esl_comm_init", "esl_comm_init_host", "esl_comm_set_replicated", "esl_comm_destroy", "esl_partition_objects", "esl_fit_params_default", "esl_fit_frame", "esl_fit_frame_debug", "esl_fit_frame_ex", "esl_selftest_cholesky", "esl_debug_chol_plan",
     "esl_init_quadric", "esl_init_from_qstar", "esl_init_plane_error", "esl_plane_params_default", "esl_extract_ground_plane", "esl_extract_planes",
+    "esl_reloc_params_default", "esl_reloc_set_map", "esl_relocalize",
 ]
 
 
@@ -417,6 +418,43 @@ class Context:
                                          labels.ctypes.data_as(C.POINTER(C.c_int32))), "esl_extract_planes")
         k = min(n.value, max_planes)
         return dict(n_planes=n.value, planes=planes[:k], sizes=sizes[:k], labels=labels)
+
+    def reloc_set_map(self, objs, labels, ground_world):
+        """esl_reloc_set_map: the fixed map esl_relocalize searches -- objs (M, 10) world ellipsoids, or None to take the resident
+        graph's current ellipsoid states on the device; labels (M,); the world ground plane (4,)."""
+        lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        gw = np.ascontiguousarray(ground_world, dtype=np.float64).reshape(4)
+        if objs is None:
+            op = _dp()
+        else:
+            objs = np.ascontiguousarray(objs, dtype=np.float64).reshape(-1, 10)
+            if len(objs) != len(lab):
+                raise ValueError(f"{len(objs)} ellipsoids, {len(lab)} labels")
+            op = objs.ctypes.data_as(_dp)
+        _check(load().esl_reloc_set_map(self._h, op, lab.ctypes.data_as(C.POINTER(C.c_int32)), C.c_int32(len(lab)),
+                                        gw.ctypes.data_as(_dp)), "esl_reloc_set_map")
+
+    def relocalize(self, det_objs, det_labels, ground_cam, params=None):
+        """esl_relocalize: camera pose and detection -> map association of one frame against the map of reloc_set_map, with no
+        pose prior.  det_objs (D, 10) single-frame ellipsoids in the camera frame (fit_frame's output), det_labels (D,), ground_cam
+        the ground plane in the camera frame.  Returns (dict of esl_reloc_result, assoc (D,) map index or -1); status 1 - 3 are
+        results, not errors."""
+        p = params if params is not None else abi.default_reloc_params()
+        det = np.ascontiguousarray(det_objs, dtype=np.float64).reshape(-1, 10)
+        lab = np.ascontiguousarray(det_labels, dtype=np.int32).reshape(-1)
+        if len(det) != len(lab):
+            raise ValueError(f"{len(det)} detections, {len(lab)} labels")
+        gc = np.ascontiguousarray(ground_cam, dtype=np.float64).reshape(4)
+        D = len(det)
+        assoc = np.full(max(D, 1), -1, dtype=np.int32)
+        res = abi.EslRelocResult()
+        t0 = time.perf_counter()
+        rc = load().esl_relocalize(self._h, det.ctypes.data_as(_dp) if D else _dp(),
+                                   lab.ctypes.data_as(C.POINTER(C.c_int32)) if D else C.POINTER(C.c_int32)(), C.c_int32(D),
+                                   gc.ctypes.data_as(_dp), C.byref(p), C.byref(res), assoc.ctypes.data_as(C.POINTER(C.c_int32)))
+        self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
+        _check(rc, "esl_relocalize")
+        return res.as_dict(), assoc[:D]
 
     def selftest_cholesky(self, n):
         """(ms, relative residual) of the dense FP64-MFMA Cholesky factor + solve on a generated SPD system."""
