@@ -49,7 +49,8 @@ extern "C" {
                              *    additive part of 5: robust kernels per edge class (esl_robust_params, esl_lm_set_robust, esl_edge_chi2) --
                              *    detect them by the symbol; likewise fixed ellipsoids (esl_graph_upload_fixed, esl_optimize_fixed,
                              *    esl_graph_obj_fixed) with ESL_SOLVER_CAMERA_CHAIN, and relocalisation against a fixed map
-                             *    (esl_reloc_set_map, esl_relocalize) */
+                             *    (esl_reloc_set_map, esl_relocalize), and 2-D data association against the projected map
+                             *    (esl_predict_boxes, esl_associate_boxes) */
 #define ESL_MAX_TRACE 32
 
 typedef enum {
@@ -583,6 +584,56 @@ typedef struct {
 int esl_relocalize(esl_ctx* ctx, const double* det_objs /* D x 10, camera frame */, const int32_t* det_labels, int32_t D,
                    const double ground_cam[4], const esl_reloc_params* p /* NULL = defaults */,
                    esl_reloc_result* out, int32_t* assoc_out /* D: map index or -1; may be NULL */);
+
+/* ---- 2-D data association: detection boxes against the projected map, GIVEN the poses (additive part of ABI 5: detect by the symbol) ---
+ * The reference's association (DataAssociationSolver::Solve, src/core/DataAssociation.cpp:16-135) is 3-D only; its mb3D == false branch
+ * is empty, so a detection without a depth ellipsoid gets -1 and its bbox edge is lost.  esl_associate_boxes fills that branch: it
+ * predicts the box of every map ellipsoid in every frame with the projection the bbox edge evaluates, and assigns detections to
+ * predictions by the reference's greedy rule (SolveCostMat, DataAssociation.cpp:90-135) with cost 1 - IoU.  Everything runs in FP64;
+ * every choice is a total order, so the result does not depend on the order in which threads meet the candidates, and runs are
+ * bit-reproducible.
+ *  1. Prediction of map object m in frame f.  Eligible iff the bbox edge's visibility predicate holds (checkVisibility, Optimizer.cpp:
+ *     35-81: centre in front of the camera, camera outside the ellipsoid, projected centre or a box corner inside the image), the box b
+ *     of the projected outline is finite, and the clipped box c = (max(b0, 0), max(b1, 0), min(b2, cols), min(b3, rows)) is at least
+ *     min_box_px wide AND high.  z_m = the camera-frame z of the centre.
+ *  2. Occlusion (occlusion != 0).  An eligible m is occluded iff ONE other eligible m' is nearer (z_m' < z_m, or z_m' == z_m and
+ *     m' < m) and covers it: area(c_m n c_m') >= occl_ratio * area(c_m).  An occluder may itself be occluded; there is no union of
+ *     occluders.  O(V^2) per frame over the V eligible predictions, exact.
+ *  3. Assignment.  The detections of a frame are taken in index order.  The candidates of a detection are the eligible, non-occluded,
+ *     unclaimed predictions, of equal label if match_labels.  It takes the candidate with the largest IoU(detection box as given, c_m),
+ *     ties to the lowest m; if that IoU is >= min_iou and > 0 the pair is assigned and m is claimed for the rest of the frame,
+ *     otherwise assoc = -1 and iou = 0.  A detection with a non-finite coordinate, x2 <= x1 or y2 <= y1 gets -1 and claims nothing. */
+typedef struct {
+  double min_iou;        /* 0.3: a detection is assigned only when its best IoU is >= this (and > 0) */
+  double occl_ratio;     /* 0.7: share of a prediction's clipped box one nearer prediction must cover to hide it */
+  double min_box_px;     /* 10: the clipped predicted box must be at least this wide AND this high */
+  int32_t match_labels;  /* 1: candidates need equal labels; 0: labels ignored */
+  int32_t occlusion;     /* 1: hidden predictions take no detection; 0: step 2 skipped */
+} esl_assoc_params;      /* 32 bytes */
+void esl_assoc_params_default(esl_assoc_params* p);
+
+/* One frame's predictions (steps 1 and 2), for inspection and tests.  boxes_out holds c for eligible objects and NaN otherwise,
+ * depth_out z_m or NaN, flags_out bit 0 eligible, bit 1 occluded.  objs == NULL: the resident graph's current ellipsoid states (M must
+ * equal its n_objs).  Errors as esl_associate_boxes. */
+int esl_predict_boxes(esl_ctx* ctx, const double Tcw[7], const double* objs /* M x 10 world, NULL = resident ellipsoid states */,
+                      int32_t M, const double K[4], int32_t rows, int32_t cols, const esl_assoc_params* p /* NULL = defaults */,
+                      double* boxes_out /* M x 4 */, double* depth_out /* M */, int32_t* flags_out /* M: bit 0 eligible, bit 1 occluded */);
+
+/* Many frames.  frame_stats_out holds per frame: eligible predictions, occluded ones, assigned detections, spilled (1 when the frame's
+ * eligible predictions did not fit the on-chip tile of 1,024 and went through global scratch; the result is the same bits).
+ * ESL_ERR_INVALID: null or negative arguments (labels are needed whenever their count is > 0), offsets that do not start at 0 or
+ * decrease, non-finite or negative min_iou / occl_ratio / min_box_px, rows or cols < 1, F or M differing from the resident graph when
+ * the NULL forms are used.  ESL_ERR_STATE: a NULL source without a resident graph and states.  F = 0, M = 0 and a frame without
+ * detections are valid; with M = 0 every detection gets -1.  The calls leave the resident graph, its states and its solver blobs alone,
+ * keep grow-only device buffers of their own (freed by esl_ctx_destroy), run on this context's GPU only and issue no collective.  With
+ * esl_profile_enable(ctx, 2) the kernel launches of a call are bracketed as kernel class 4. */
+int esl_associate_boxes(esl_ctx* ctx, const double* cams /* F x 7 Tcw, NULL = resident camera states (F must equal n_cams) */, int32_t F,
+                        const double* objs /* M x 10, NULL = resident (M must equal n_objs) */, const int32_t* obj_labels /* M */, int32_t M,
+                        const double K[4], int32_t rows, int32_t cols,
+                        const int32_t* det_offsets /* F + 1, CSR, non-decreasing, [0] = 0 */, const double* det_boxes /* n_det x 4: x1 y1 x2 y2 */,
+                        const int32_t* det_labels /* n_det */, const esl_assoc_params* p /* NULL = defaults */,
+                        int32_t* assoc_out /* n_det: map index or -1 */, double* iou_out /* n_det or NULL */,
+                        int32_t* frame_stats_out /* F x 4 or NULL: eligible, occluded, assigned, spilled */);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------*/
 /* Dense FP64-MFMA Cholesky factor + solve (the reduced-camera solver of SLAM mode) on a procedurally generated,

@@ -153,6 +153,22 @@ def default_reloc_params(**kw):
     return p
 
 
+class EslAssocParams(C.Structure):
+    """esl_assoc_params: gates and switches of esl_predict_boxes / esl_associate_boxes."""
+    _fields_ = [("min_iou", C.c_double), ("occl_ratio", C.c_double), ("min_box_px", C.c_double), ("match_labels", C.c_int32),
+                ("occlusion", C.c_int32)]
+
+
+def default_assoc_params(**kw):
+    """esl_assoc_params_default (include/esl.h)."""
+    p = EslAssocParams(min_iou=0.3, occl_ratio=0.7, min_box_px=10.0, match_labels=1, occlusion=1)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
 ROBUST_KINDS = {"none": 0, "huber": 1, "pseudo_huber": 2, "cauchy": 3, "tukey": 4}   # esl_robust_kind (include/esl.h)
 EDGE_CLASSES = {"bbox": 0, "e3d": 1, "grav": 2, "odom": 3}                         # esl_edge_class
 

@@ -25,6 +25,7 @@ EXPORTS = [
     "esl_lm_try_step", "esl_lm_commit", "esl_lm_solver_used", "esl_lm_solver_stats", "esl_lm_download", "esl_lm_set_robust", "esl_edge_chi2", "esl_pcg_params_default", "esl_lm_set_pcg", "esl_lm_pcg_stats", "esl_comm_unique_id", "esl_comm_init", "esl_comm_init_host", "esl_comm_set_replicated", "esl_comm_destroy", "esl_partition_objects", "esl_fit_params_default", "esl_fit_frame", "esl_fit_frame_debug", "esl_fit_frame_ex", "esl_selftest_cholesky", "esl_debug_chol_plan",
     "esl_init_quadric", "esl_init_from_qstar", "esl_init_plane_error", "esl_plane_params_default", "esl_extract_ground_plane", "esl_extract_planes",
     "esl_reloc_params_default", "esl_reloc_set_map", "esl_relocalize",
+    "esl_assoc_params_default", "esl_predict_boxes", "esl_associate_boxes",
 ]
 
 
@@ -455,6 +456,68 @@ class Context:
         self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
         _check(rc, "esl_relocalize")
         return res.as_dict(), assoc[:D]
+
+    def predict_boxes(self, Tcw, objs, K, rows, cols, params=None):
+        """esl_predict_boxes: the map's predicted boxes in one frame.  Tcw (7,), objs (M, 10) world ellipsoids or None for the resident
+        graph's current ellipsoid states.  Returns (boxes (M, 4) clipped, NaN where not eligible; depth (M,); flags (M,) bit 0 eligible,
+        bit 1 occluded)."""
+        p = params if params is not None else abi.default_assoc_params()
+        _ip = C.POINTER(C.c_int32)
+        Tcw = np.ascontiguousarray(Tcw, dtype=np.float64).reshape(7)
+        Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(4)
+        if objs is None:
+            M, op = self.graph_sizes()["n_objs"], _dp()
+        else:
+            objs = np.ascontiguousarray(objs, dtype=np.float64).reshape(-1, 10)
+            M, op = len(objs), (objs.ctypes.data_as(_dp) if len(objs) else _dp())
+        boxes = np.full((max(M, 1), 4), np.nan); depth = np.full(max(M, 1), np.nan); flags = np.zeros(max(M, 1), dtype=np.int32)
+        _check(load().esl_predict_boxes(self._h, Tcw.ctypes.data_as(_dp), op, C.c_int32(M), Kc.ctypes.data_as(_dp), C.c_int32(rows),
+                                        C.c_int32(cols), C.byref(p), boxes.ctypes.data_as(_dp), depth.ctypes.data_as(_dp),
+                                        flags.ctypes.data_as(_ip)), "esl_predict_boxes")
+        return boxes[:M], depth[:M], flags[:M]
+
+    def associate_boxes(self, cams, objs, obj_labels, K, rows, cols, det_offsets, det_boxes, det_labels, params=None):
+        """esl_associate_boxes: detection boxes -> map objects in many frames, given the poses.  cams (F, 7) Tcw and objs (M, 10), or
+        None for the resident graph's current states; obj_labels (M,); det_offsets (F + 1,) CSR; det_boxes (n_det, 4) x1 y1 x2 y2;
+        det_labels (n_det,).  Returns (assoc (n_det,) map index or -1, iou (n_det,), frame_stats (F, 4): eligible, occluded, assigned,
+        spilled)."""
+        p = params if params is not None else abi.default_assoc_params()
+        _ip = C.POINTER(C.c_int32)
+
+        def ptr(a, t):
+            return a.ctypes.data_as(t) if a.size else t()
+        Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(4)
+        off = np.ascontiguousarray(det_offsets, dtype=np.int32).reshape(-1)
+        db = np.ascontiguousarray(det_boxes, dtype=np.float64).reshape(-1, 4)
+        dl = np.ascontiguousarray(det_labels, dtype=np.int32).reshape(-1)
+        ol = np.ascontiguousarray(obj_labels, dtype=np.int32).reshape(-1)
+        if len(db) != len(dl):
+            raise ValueError(f"{len(db)} detection boxes, {len(dl)} labels")
+        if len(off) and off[-1] != len(db):
+            raise ValueError(f"det_offsets end at {off[-1]}, there are {len(db)} detection boxes")
+        if cams is None:
+            F, cp = len(off) - 1, _dp()
+        else:
+            cams = np.ascontiguousarray(cams, dtype=np.float64).reshape(-1, 7)
+            F, cp = len(cams), ptr(cams, _dp)
+            if len(off) != F + 1:
+                raise ValueError(f"{F} frames need {F + 1} offsets, got {len(off)}")
+        if objs is None:
+            M, op = len(ol), _dp()
+        else:
+            objs = np.ascontiguousarray(objs, dtype=np.float64).reshape(-1, 10)
+            M, op = len(objs), ptr(objs, _dp)
+            if len(ol) != M:
+                raise ValueError(f"{M} ellipsoids, {len(ol)} labels")
+        n = len(db)
+        assoc = np.full(max(n, 1), -1, dtype=np.int32); iou = np.zeros(max(n, 1)); stats = np.zeros((max(F, 1), 4), dtype=np.int32)
+        t0 = time.perf_counter()
+        rc = load().esl_associate_boxes(self._h, cp, C.c_int32(F), op, ptr(ol, _ip), C.c_int32(M), Kc.ctypes.data_as(_dp),
+                                        C.c_int32(rows), C.c_int32(cols), ptr(off, _ip), ptr(db, _dp), ptr(dl, _ip), C.byref(p),
+                                        assoc.ctypes.data_as(_ip), iou.ctypes.data_as(_dp), stats.ctypes.data_as(_ip))
+        self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
+        _check(rc, "esl_associate_boxes")
+        return assoc[:n], iou[:n], stats[:F]
 
     def selftest_cholesky(self, n):
         """(ms, relative residual) of the dense FP64-MFMA Cholesky factor + solve on a generated SPD system."""
