@@ -50,7 +50,8 @@ extern "C" {
                              *    detect them by the symbol; likewise fixed ellipsoids (esl_graph_upload_fixed, esl_optimize_fixed,
                              *    esl_graph_obj_fixed) with ESL_SOLVER_CAMERA_CHAIN, and relocalisation against a fixed map
                              *    (esl_reloc_set_map, esl_relocalize), and 2-D data association against the projected map
-                             *    (esl_predict_boxes, esl_associate_boxes) */
+                             *    (esl_predict_boxes, esl_associate_boxes), and the SVD initialisation of many ellipsoids in one call
+                             *    (esl_init_quadrics) */
 #define ESL_MAX_TRACE 32
 
 typedef enum {
@@ -523,6 +524,42 @@ int esl_init_from_qstar(esl_ctx* ctx, const double qstar[16], int32_t faithful, 
  * bbox tangent planes pi of (pi^T Q* pi)^2 for the given ellipsoid (10-vector, world frame). */
 int esl_init_plane_error(esl_ctx* ctx, const double* poses_Twc /* n x 7 */, const double* bboxes /* n x 4 */, int32_t n,
                          const double K[4], int32_t rows, int32_t cols, const double ellipsoid[10], double* error_out);
+
+/* ---- SVD quadric initialisation of many objects in one call (additive part of ABI 5: detect by the symbol) --------------------------
+ * Initializer::initializeQuadric for many objects at once (Tracking::JudgeInitialization's loop, Tracking.cpp:581-608): one launch,
+ * one wavefront per object, no allocation on a warm call.
+ * Input.  The observations are an edge list: entry i says that frame obs_cam[i] saw object obs_obj[i] in the box obs_boxes[4 i ..].
+ * esl_graph's bbox_cam / bbox_obj / bbox_meas can be passed as they are, and so can an assoc_out of esl_associate_boxes as obs_obj:
+ * entries with obs_obj < 0 are skipped.  The observations of object o are the entries with obs_obj == o in list order; the list need
+ * not be sorted.  Poses are Tcw (the graph's convention, NOT esl_init_quadric's Twc); the quaternion is normalised as the
+ * SE3Quat(Vector7d) constructor does.
+ * Per object the rules are esl_init_quadric's (Initializer.cpp:58-145): a detection with all four coordinates < 1 contributes
+ * nothing; a line is kept iff its coordinate is > 0 and < cols - 1 (rows - 1 for y); the null vector of the plane matrix comes from
+ * the one-sided Jacobi SVD on the matrix itself, signed so that Q*_33 > 0; faithful as in esl_init_from_qstar.
+ * stats_out[4 o ..] = status, observations (all list entries of the object), planes (kept lines), spilled:
+ *   status 0  initialised: every output written; plane_error_out[o] = quadricErrorWithPlanes (Initializer.cpp:271-284) of the
+ *             returned ellipsoid over the object's own planes
+ *   status 1  observations < min_observations (Tracking_MINIMUM_INITIALIZATION_FRAME, 15 in Config.cpp:29, or 0): every output of the
+ *             object is zero, planes is 0
+ *   status 2  otherwise, fewer than 9 planes: every output of the object is zero
+ *   status 3  the decomposition rejected Q*: ellipsoid zero, qstar_out holds the SVD's Q* (as the single call does), plane error zero
+ * The plane matrix of an object (320 bytes per observation) stays on chip up to T = 248 observations (objects of up to 96 use a
+ * smaller tile of their own, so that more of them are resident); a larger object keeps its rows in a global slab, spilled = 1: the
+ * same arithmetic through another pointer.  An object's outputs depend on its own observations alone, not on the rest of the batch.
+ * ESL_ERR_INVALID: null or negative arguments (obs_* are needed whenever n_obs > 0, ellipsoids_out whenever N > 0), a non-skipped
+ * entry with obs_cam outside [0, F) or obs_obj >= N, rows or cols < 1, n_obs >= 2^31, F differing from the resident graph's n_cams
+ * when cams == NULL.  ESL_ERR_STATE: cams == NULL without a resident graph and states.  N = 0 and n_obs = 0 are valid.  The call
+ * leaves the resident graph, its states and the solver blobs alone, keeps grow-only device buffers of its own (freed by
+ * esl_ctx_destroy), runs on this context's GPU only and issues no collective.  With esl_profile_enable(ctx, 2) its launches are
+ * bracketed as kernel class 4. */
+int esl_init_quadrics(esl_ctx* ctx,
+                      const double* cams /* F x 7 Tcw, NULL = resident camera states (F must equal n_cams) */, int32_t F,
+                      int32_t N /* objects */,
+                      const int32_t* obs_cam /* n_obs: frame index */, const int32_t* obs_obj /* n_obs: 0..N-1, < 0 = entry skipped */,
+                      const double* obs_boxes /* n_obs x 4: x1 y1 x2 y2 */, int64_t n_obs,
+                      const double K[4], int32_t rows, int32_t cols, int32_t faithful, int32_t min_observations,
+                      double* ellipsoids_out /* N x 10 */, double* qstar_out /* N x 16 or NULL */,
+                      double* plane_error_out /* N or NULL */, int32_t* stats_out /* N x 4 or NULL: status, observations, planes, spilled */);
 
 /* ---- relocalisation: camera pose and detection -> map association with NO pose prior (additive part of ABI 5: detect by the symbol) ---
  * esl_optimize_fixed refines a pose that is already inside the basin of its edges and needs the edge lists, i.e. which detection is

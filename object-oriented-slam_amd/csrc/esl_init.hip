@@ -6,9 +6,16 @@
 // The plane rows (<= 4 per observation, 10 monomials each) are staged in LDS; the null vector comes
 // from a one-sided (Hestenes) Jacobi SVD whose column dot-products are lane-strided sums finished with
 // a butterfly all-reduce; the 4x4 / 3x3 decompositions that follow are a few hundred flops on lane 0.
+//
+// esl_init_quadrics (second half of the file) is the same arithmetic for every object of an edge list in one call: its own kernel
+// beside k_init_quadric, which it leaves as it is.
+#include <algorithm>
 #include <cmath>
+#include <string>
+#include <vector>
 
 #include "esl_ctx.hpp"
+#include "esl_init_group.hpp"
 #include "esl_kernels_map.hpp"
 
 namespace esl {
@@ -294,6 +301,209 @@ __device__ void decompose_qstar(const double* Qs, int faithful, double* __restri
   out[26] = 1.0;
 }
 
+// ---- esl_init_quadrics: the same per-object arithmetic for many objects in one call -------------------------------------------------
+// One workgroup of one wavefront per object.  The host groups the observation list by object (esl_init_group.hpp) and sorts the
+// objects by falling observation count; an object's plane matrix (320 bytes per observation) lives
+//   - in LDS in a tile of kInitTileSmall observations  (k_init_quadrics<kInitTileSmall>: 31.8 KB, five workgroups per CU),
+//   - in LDS in a tile of kInitTile observations       (k_init_quadrics<kInitTile>: 80.4 KB, two workgroups per CU),
+//   - or in its rows of a global slab when it has more than kInitTile observations (stats[3] = 1; launched with the small tile, which
+//     it does not use, so that it does not take a large tile's place).
+// Which of the three holds depends on the object's own observation count alone, and the arithmetic is the same code over either
+// pointer, so an object's result does not depend on what else is in the batch.
+#ifndef ESL_INIT_TILE
+#define ESL_INIT_TILE 248
+#endif
+#ifndef ESL_INIT_TILE_SMALL
+#define ESL_INIT_TILE_SMALL 96
+#endif
+constexpr int kInitTile = ESL_INIT_TILE;              // T of include/esl.h: the most observations whose plane matrix stays on chip
+constexpr int kInitTileSmall = ESL_INIT_TILE_SMALL;
+static_assert(kInitTileSmall >= 1 && kInitTileSmall <= kInitTile, "the small tile is the first bin");
+static_assert((132 + (size_t)kInitTile * 40) * sizeof(double) <= 160 * 1024, "the tile has to fit a CU's LDS");
+
+struct InitBatchArgs {
+  const double* cams;                       // Tcw, 7 doubles per frame
+  const int* obs_cam; const double* obs_box; // the caller's list as given
+  const int* idx;                           // positions in the list, grouped by object
+  const InitObj* order;                     // the launch list: [first, first + count) of this launch
+  double K[4];
+  int rows, cols, faithful, min_obs;
+  double* slab;
+  double* ell; double* qstar; double* perr; int* stats;   // qstar, perr, stats may be null
+};
+
+// getPlanesHomo (Initializer.cpp:58-91) for the observations of one object: the kept lines' monomial rows to A, compacted in
+// observation order; returns the row count (wave-uniform).  The row arithmetic is k_init_quadric's, on Tcw as given.
+static __device__ int init_plane_rows(const InitBatchArgs& a, const InitObj& e, double* A) {
+  const int lane = threadIdx.x;
+  int m = 0;
+  for (int base = 0; base < e.n; base += 64) {
+    const int i = base + lane;
+    double rowsv[4][10];
+    int cnt = 0;
+    if (i < e.n) {
+      const int k = a.idx[e.first + i];
+      const double* d = a.obs_box + 4 * (size_t)k;
+      if (!(d[0] < 1 && d[1] < 1 && d[2] < 1 && d[3] < 1)) {
+        SE3 Tcw = se3_load(a.cams + 7 * (size_t)a.obs_cam[k]);
+        Tcw.r = q_normalize_pos(Tcw.r);  // SE3Quat(Vector7d) ctor normalises (se3quat.h:66-69)
+        const Mat3 R = q_to_R(Tcw.r);
+        double P[12];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const double c0 = c < 3 ? R.m[c] : Tcw.t[0], c1 = c < 3 ? R.m[3 + c] : Tcw.t[1], c2 = c < 3 ? R.m[6 + c] : Tcw.t[2];
+          P[c] = a.K[0] * c0 + a.K[2] * c2; P[4 + c] = a.K[1] * c1 + a.K[3] * c2; P[8 + c] = c2;
+        }
+        const double lines[4][3] = {{1, 0, -d[0]}, {0, 1, -d[1]}, {1, 0, -d[2]}, {0, 1, -d[3]}};
+        const bool keep[4] = {d[0] > 0 && d[0] < a.cols - 1, d[1] > 0 && d[1] < a.rows - 1, d[2] > 0 && d[2] < a.cols - 1,
+                              d[3] > 0 && d[3] < a.rows - 1};
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+          if (!keep[l]) continue;
+          double p[4];
+#pragma unroll
+          for (int c = 0; c < 4; ++c) p[c] = P[c] * lines[l][0] + P[4 + c] * lines[l][1] + P[8 + c] * lines[l][2];
+          double* v = rowsv[cnt++];
+          v[0] = p[0] * p[0]; v[1] = 2 * p[0] * p[1]; v[2] = 2 * p[0] * p[2]; v[3] = 2 * p[0] * p[3]; v[4] = p[1] * p[1];
+          v[5] = 2 * p[1] * p[2]; v[6] = 2 * p[1] * p[3]; v[7] = p[2] * p[2]; v[8] = 2 * p[2] * p[3]; v[9] = p[3] * p[3];
+        }
+      }
+    }
+    int incl = cnt;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int t = __shfl_up(incl, off, 64);
+      if (lane >= off) incl += t;
+    }
+    const int excl = incl - cnt;
+    for (int k = 0; k < cnt; ++k)
+      for (int c = 0; c < 10; ++c) A[(size_t)(m + excl + k) * 10 + c] = rowsv[k][c];
+    m += __shfl(incl, 63, 64);
+  }
+  return m;
+}
+
+// every output of an object that is not initialised (statuses 1 and 2) is zero
+static __device__ void init_reject(const InitBatchArgs& a, const InitObj& e, int status, int planes) {
+  const int lane = threadIdx.x;
+  if (lane < 10) a.ell[(size_t)e.obj * 10 + lane] = 0.0;
+  if (a.qstar && lane < 16) a.qstar[(size_t)e.obj * 16 + lane] = 0.0;
+  if (lane == 0) {
+    if (a.perr) a.perr[e.obj] = 0.0;
+    if (a.stats) { int* s = a.stats + (size_t)e.obj * 4; s[0] = status; s[1] = e.n; s[2] = planes; s[3] = (status == 2 && e.spill >= 0) ? 1 : 0; }
+  }
+}
+
+template <int TILE>
+static __global__ __launch_bounds__(64) void k_init_quadrics(InitBatchArgs a, int first) {
+  // V 10 x 10 | the result as k_init_quadric lays it out (28) + padding | the tile
+  __shared__ __attribute__((aligned(16))) double sm[132 + TILE * 40];
+  const InitObj e = a.order[first + blockIdx.x];
+  const int lane = threadIdx.x;
+  if (e.n < a.min_obs) { init_reject(a, e, 1, 0); return; }
+  double* V = sm;
+  double* res = sm + 100;
+  double* A = e.spill >= 0 ? a.slab + (size_t)e.spill * 40 : sm + 132;   // e.spill < 0 only when e.n <= TILE (the host's bins)
+  const int m = init_plane_rows(a, e, A);
+  for (int idx = lane; idx < 100; idx += 64) V[idx] = (idx / 10 == idx % 10) ? 1.0 : 0.0;
+  __syncthreads();
+  if (m < 9) { init_reject(a, e, 2, m); return; }   // at least 9 planes are needed (Initializer.cpp:38)
+  // one-sided Jacobi SVD on the columns of A, as in k_init_quadric
+  for (int sweep = 0; sweep < 60; ++sweep) {
+    int rotated = 0;
+    for (int p = 0; p < 10; ++p)
+      for (int q = p + 1; q < 10; ++q) {
+        double al = 0, be = 0, ga = 0;
+        for (int r = lane; r < m; r += 64) {
+          const double ap = A[(size_t)r * 10 + p], aq = A[(size_t)r * 10 + q];
+          al += ap * ap; be += aq * aq; ga += ap * aq;
+        }
+        al = wave_allsum(al); be = wave_allsum(be); ga = wave_allsum(ga);
+        if (fabs(ga) <= 1e-15 * sqrt(al * be) || ga == 0.0) continue;
+        rotated = 1;
+        const double zeta = (be - al) / (2 * ga);
+        const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1 + zeta * zeta));
+        const double cs = 1 / sqrt(1 + t * t), sn = cs * t;
+        for (int r = lane; r < m; r += 64) {
+          const double ap = A[(size_t)r * 10 + p], aq = A[(size_t)r * 10 + q];
+          A[(size_t)r * 10 + p] = cs * ap - sn * aq;
+          A[(size_t)r * 10 + q] = sn * ap + cs * aq;
+        }
+        if (lane < 10) {
+          const double vp = V[lane * 10 + p], vq = V[lane * 10 + q];
+          V[lane * 10 + p] = cs * vp - sn * vq;
+          V[lane * 10 + q] = sn * vp + cs * vq;
+        }
+        __syncthreads();
+      }
+    if (!rotated) break;
+  }
+  int best = 0;
+  double bn = -1;
+  for (int c = 0; c < 10; ++c) {
+    double s = 0;
+    for (int r = lane; r < m; r += 64) s += A[(size_t)r * 10 + c] * A[(size_t)r * 10 + c];
+    s = wave_allsum(s);
+    if (bn < 0 || s < bn) { bn = s; best = c; }
+  }
+  if (lane == 0) {
+    double q[10];
+    for (int r = 0; r < 10; ++r) q[r] = V[r * 10 + best];
+    if (q[9] < 0)
+      for (int r = 0; r < 10; ++r) q[r] = -q[r];  // sign convention: Q*_33 > 0
+    const double Qs[16] = {q[0], q[1], q[2], q[3], q[1], q[4], q[5], q[6], q[2], q[5], q[7], q[8], q[3], q[6], q[8], q[9]};
+    for (int i = 0; i < 16; ++i) res[10 + i] = Qs[i];
+    for (int i = 0; i < 10; ++i) res[i] = 0;
+    res[26] = 0; res[27] = 0;
+    decompose_qstar(Qs, a.faithful, res);
+  }
+  __syncthreads();
+  const bool ok = res[26] > 0.5;
+  if (lane < 10) a.ell[(size_t)e.obj * 10 + lane] = res[lane];
+  if (a.qstar && lane < 16) a.qstar[(size_t)e.obj * 16 + lane] = res[10 + lane];
+  if (lane == 0 && a.stats) { int* s = a.stats + (size_t)e.obj * 4; s[0] = ok ? 0 : 3; s[1] = e.n; s[2] = m; s[3] = e.spill >= 0 ? 1 : 0; }
+  if (!a.perr) return;
+  double err = 0;
+  if (ok) {
+    // quadricErrorWithPlanes of the ellipsoid just returned over this object's planes: the SVD rotated A away, so the rows are built
+    // again, then k_init_quadric's mode 2
+    (void)init_plane_rows(a, e, A);
+    __syncthreads();
+    SE3 T = se3_load(res);
+    const Mat3 R = q_to_R(T.r);
+    const double d[4] = {res[7] * res[7], res[8] * res[8], res[9] * res[9], -1.0};
+    double Z[16], Qs[16];   // Q* = Z diag(a^2, b^2, c^2, -1) Z^T (Ellipsoid.cpp:290-300)
+    for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) Z[i * 4 + j] = R.m[i * 3 + j]; Z[i * 4 + 3] = T.t[i]; Z[12 + i] = 0; }
+    Z[15] = 1;
+    for (int i = 0; i < 4; ++i)
+      for (int j = 0; j < 4; ++j) { double v = 0; for (int k = 0; k < 4; ++k) v += Z[i * 4 + k] * d[k] * Z[j * 4 + k]; Qs[i * 4 + j] = v; }
+    const double qh[10] = {Qs[0], Qs[1], Qs[2], Qs[3], Qs[5], Qs[6], Qs[7], Qs[10], Qs[11], Qs[15]};
+    for (int r = lane; r < m; r += 64) {
+      double v = 0;
+      for (int k = 0; k < 10; ++k) v += A[(size_t)r * 10 + k] * qh[k];
+      err += v * v;
+    }
+    err = wave_allsum(err);
+  }
+  if (lane == 0) a.perr[e.obj] = err;
+}
+
+struct InitBatchState {   // esl_ctx::init_batch
+  enum { B_CAMS, B_OCAM, B_BOX, B_IDX, B_ORDER, B_SLAB, B_ELL, B_QS, B_PERR, B_STATS, kBufs };
+  void* buf[kBufs] = {};
+  size_t cap[kBufs] = {};
+  std::vector<int32_t> offsets, idx;   // the host's grouping, kept for their capacity
+  std::vector<InitObj> order;
+};
+
+void init_batch_release(esl_ctx* c) {   // called by esl_ctx_destroy
+  InitBatchState* s = (InitBatchState*)c->init_batch;
+  if (!s) return;
+  for (void* p : s->buf) if (p) (void)hipFree(p);
+  delete s;
+  c->init_batch = nullptr;
+}
+
 }  // namespace esl
 
 using namespace esl;
@@ -375,5 +585,102 @@ extern "C" int esl_init_plane_error(esl_ctx* c, const double* poses_Twc, const d
   const int rc = init_launch(c, poses_Twc, bboxes, n, K, rows, cols, 1, 2, ellipsoid, 10, h);
   if (rc) return rc;
   *error_out = h[27];
+  return ESL_OK;
+}
+
+namespace {
+
+int init_batch_grow(esl_ctx* c, InitBatchState* s, int k, size_t bytes) {   // grow-only; contents are not kept
+  if (bytes <= s->cap[k] && s->buf[k]) return ESL_OK;
+  ESL_HIP_TRY(hipStreamSynchronize(c->stream));
+  if (s->buf[k]) (void)hipFree(s->buf[k]);
+  s->buf[k] = nullptr; s->cap[k] = 0;
+  ESL_HIP_TRY(hipMalloc(&s->buf[k], std::max<size_t>(bytes, 16)));
+  s->cap[k] = bytes;
+  return ESL_OK;
+}
+
+int init_batch_fail(const char* what, int rc) { set_error(std::string("esl_init_quadrics: ") + what); return rc; }
+
+}  // namespace
+
+extern "C" int esl_init_quadrics(esl_ctx* c, const double* cams, int32_t F, int32_t N, const int32_t* obs_cam, const int32_t* obs_obj,
+                                 const double* obs_boxes, int64_t n_obs, const double K[4], int32_t rows, int32_t cols, int32_t faithful,
+                                 int32_t min_observations, double* ellipsoids_out, double* qstar_out, double* plane_error_out,
+                                 int32_t* stats_out) {
+  if (!c || !K || F < 0 || N < 0 || n_obs < 0 || min_observations < 0) return init_batch_fail("bad argument (null pointer or negative count)", ESL_ERR_INVALID);
+  if (n_obs > INT32_MAX) return init_batch_fail("more than 2^31 - 1 observations", ESL_ERR_INVALID);
+  if (n_obs > 0 && (!obs_cam || !obs_obj || !obs_boxes)) return init_batch_fail("null observation array", ESL_ERR_INVALID);
+  if (N > 0 && !ellipsoids_out) return init_batch_fail("null ellipsoids_out", ESL_ERR_INVALID);
+  if (rows < 1 || cols < 1) return init_batch_fail("rows or cols < 1", ESL_ERR_INVALID);
+  if (!cams) {
+    if (!c->graph_loaded || !c->states_loaded) return init_batch_fail("cams == NULL needs a resident graph with states", ESL_ERR_STATE);
+    if (F != c->g.n_cams) return init_batch_fail("F differs from the resident graph's n_cams", ESL_ERR_INVALID);
+  }
+  if (!c->init_batch) c->init_batch = new InitBatchState();
+  InitBatchState* s = (InitBatchState*)c->init_batch;
+  int64_t bad = 0;
+  const int grc = init_group(n_obs, N, F, obs_cam, obs_obj, s->offsets, s->idx, &bad);
+  if (grc == INIT_GROUP_BAD_OBJ) return init_batch_fail(("obs_obj >= N at entry " + std::to_string(bad)).c_str(), ESL_ERR_INVALID);
+  if (grc == INIT_GROUP_BAD_CAM) return init_batch_fail(("obs_cam outside [0, F) at entry " + std::to_string(bad)).c_str(), ESL_ERR_INVALID);
+  if (N == 0) return ESL_OK;
+  const int64_t slab = init_order(N, s->offsets, kInitTile, min_observations, s->order);
+  if (slab < 0) return init_batch_fail("the spilled objects hold more than 2^31 - 1 observations", ESL_ERR_INVALID);
+  // the launch list falls in n: [0, n_over) more than kInitTile observations, [n_over, n_mid) more than kInitTileSmall, the rest
+  int n_over = 0, n_mid = 0;
+  while (n_over < N && s->order[n_over].n > kInitTile) ++n_over;
+  n_mid = n_over;
+  while (n_mid < N && s->order[n_mid].n > kInitTileSmall) ++n_mid;
+
+  ESL_HIP_TRY(hipSetDevice(c->device));
+  InitBatchArgs k{};
+  const size_t kept = s->idx.size();
+  if (cams) {
+    if (const int rc = init_batch_grow(c, s, InitBatchState::B_CAMS, (size_t)F * 7 * sizeof(double))) return rc;
+    if (F) ESL_HIP_TRY(hipMemcpyAsync(s->buf[InitBatchState::B_CAMS], cams, (size_t)F * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    k.cams = (const double*)s->buf[InitBatchState::B_CAMS];
+  } else k.cams = c->cams;
+  if (const int rc = init_batch_grow(c, s, InitBatchState::B_OCAM, (size_t)n_obs * sizeof(int32_t))) return rc;
+  if (const int rc = init_batch_grow(c, s, InitBatchState::B_BOX, (size_t)n_obs * 4 * sizeof(double))) return rc;
+  if (const int rc = init_batch_grow(c, s, InitBatchState::B_IDX, kept * sizeof(int32_t))) return rc;
+  if (const int rc = init_batch_grow(c, s, InitBatchState::B_ORDER, (size_t)N * sizeof(InitObj))) return rc;
+  if (const int rc = init_batch_grow(c, s, InitBatchState::B_SLAB, (size_t)slab * 40 * sizeof(double))) return rc;
+  if (const int rc = init_batch_grow(c, s, InitBatchState::B_ELL, (size_t)N * 10 * sizeof(double))) return rc;
+  if (kept) {   // entries that no object keeps are never read
+    ESL_HIP_TRY(hipMemcpyAsync(s->buf[InitBatchState::B_OCAM], obs_cam, (size_t)n_obs * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(s->buf[InitBatchState::B_BOX], obs_boxes, (size_t)n_obs * 4 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(s->buf[InitBatchState::B_IDX], s->idx.data(), kept * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  }
+  ESL_HIP_TRY(hipMemcpyAsync(s->buf[InitBatchState::B_ORDER], s->order.data(), (size_t)N * sizeof(InitObj), hipMemcpyHostToDevice, c->stream));
+  k.obs_cam = (const int*)s->buf[InitBatchState::B_OCAM]; k.obs_box = (const double*)s->buf[InitBatchState::B_BOX];
+  k.idx = (const int*)s->buf[InitBatchState::B_IDX]; k.order = (const InitObj*)s->buf[InitBatchState::B_ORDER];
+  k.slab = (double*)s->buf[InitBatchState::B_SLAB]; k.ell = (double*)s->buf[InitBatchState::B_ELL];
+  if (qstar_out) {
+    if (const int rc = init_batch_grow(c, s, InitBatchState::B_QS, (size_t)N * 16 * sizeof(double))) return rc;
+    k.qstar = (double*)s->buf[InitBatchState::B_QS];
+  }
+  if (plane_error_out) {
+    if (const int rc = init_batch_grow(c, s, InitBatchState::B_PERR, (size_t)N * sizeof(double))) return rc;
+    k.perr = (double*)s->buf[InitBatchState::B_PERR];
+  }
+  if (stats_out) {
+    if (const int rc = init_batch_grow(c, s, InitBatchState::B_STATS, (size_t)N * 4 * sizeof(int32_t))) return rc;
+    k.stats = (int*)s->buf[InitBatchState::B_STATS];
+  }
+  for (int i = 0; i < 4; ++i) k.K[i] = K[i];
+  k.rows = rows; k.cols = cols; k.faithful = faithful; k.min_obs = min_observations;
+  {
+    ProfScope ps(c, 4);
+    // the objects of the slab do not use the tile: they run with the small one, so that more of them are resident
+    if (n_over) hipLaunchKernelGGL(k_init_quadrics<kInitTileSmall>, dim3((unsigned)n_over), dim3(64), 0, c->stream, k, 0);
+    if (n_mid > n_over) hipLaunchKernelGGL(k_init_quadrics<kInitTile>, dim3((unsigned)(n_mid - n_over)), dim3(64), 0, c->stream, k, n_over);
+    if (N > n_mid) hipLaunchKernelGGL(k_init_quadrics<kInitTileSmall>, dim3((unsigned)(N - n_mid)), dim3(64), 0, c->stream, k, n_mid);
+  }
+  ESL_HIP_TRY(hipGetLastError());
+  ESL_HIP_TRY(hipMemcpyAsync(ellipsoids_out, k.ell, (size_t)N * 10 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (qstar_out) ESL_HIP_TRY(hipMemcpyAsync(qstar_out, k.qstar, (size_t)N * 16 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (plane_error_out) ESL_HIP_TRY(hipMemcpyAsync(plane_error_out, k.perr, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (stats_out) ESL_HIP_TRY(hipMemcpyAsync(stats_out, k.stats, (size_t)N * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  ESL_HIP_TRY(hipStreamSynchronize(c->stream));   // the caller's arrays are free again, the outputs filled
   return ESL_OK;
 }

@@ -23,7 +23,7 @@ EXPORTS = [
     "esl_ctx_synchronize", "esl_ctx_trim", "esl_lm_params_default", "esl_optimize", "esl_optimize_fixed", "esl_graph_upload", "esl_graph_upload_fixed", "esl_graph_obj_fixed", "esl_graph_append", "esl_graph_sizes", "esl_states_upload",
     "esl_states_download", "esl_optimize_resident", "esl_states_snapshot", "esl_states_restore", "esl_profile_enable", "esl_profile_get", "esl_lm_begin", "esl_lm_linearize", "esl_lm_reduced_system", "esl_lm_reduced_residual",
     "esl_lm_try_step", "esl_lm_commit", "esl_lm_solver_used", "esl_lm_solver_stats", "esl_lm_download", "esl_lm_set_robust", "esl_edge_chi2", "esl_pcg_params_default", "esl_lm_set_pcg", "esl_lm_pcg_stats", "esl_comm_unique_id", "esl_comm_init", "esl_comm_init_host", "esl_comm_set_replicated", "esl_comm_destroy", "esl_partition_objects", "esl_fit_params_default", "esl_fit_frame", "esl_fit_frame_debug", "esl_fit_frame_ex", "esl_selftest_cholesky", "esl_debug_chol_plan",
-    "esl_init_quadric", "esl_init_from_qstar", "esl_init_plane_error", "esl_plane_params_default", "esl_extract_ground_plane", "esl_extract_planes",
+    "esl_init_quadric", "esl_init_from_qstar", "esl_init_plane_error", "esl_init_quadrics", "esl_plane_params_default", "esl_extract_ground_plane", "esl_extract_planes",
     "esl_reloc_params_default", "esl_reloc_set_map", "esl_relocalize",
     "esl_assoc_params_default", "esl_predict_boxes", "esl_associate_boxes",
 ]
@@ -341,6 +341,38 @@ class Context:
                                            Kd.ctypes.data_as(_dp), C.c_int32(rows), C.c_int32(cols), e.ctypes.data_as(_dp),
                                            C.byref(err)), "esl_init_plane_error")
         return err.value
+
+    def init_quadrics(self, cams, N, obs_cam, obs_obj, obs_boxes, K, rows=480, cols=640, faithful=1, min_observations=0):
+        """esl_init_quadrics: Initializer::initializeQuadric for N objects in one call.  cams (F, 7) Tcw, or None for the resident
+        graph's current camera states; the observations as an edge list obs_cam (n_obs,), obs_obj (n_obs,; < 0 = skipped),
+        obs_boxes (n_obs, 4).  Returns (ellipsoids (N, 10), qstar (N, 4, 4), plane_error (N,), stats (N, 4): status, observations,
+        planes, spilled)."""
+        _ip = C.POINTER(C.c_int32)
+
+        def ptr(a, t):
+            return a.ctypes.data_as(t) if a.size else t()
+        Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(4)
+        oc = np.ascontiguousarray(obs_cam, dtype=np.int32).reshape(-1)
+        oo = np.ascontiguousarray(obs_obj, dtype=np.int32).reshape(-1)
+        ob = np.ascontiguousarray(obs_boxes, dtype=np.float64).reshape(-1, 4)
+        if not len(oc) == len(oo) == len(ob):
+            raise ValueError(f"{len(oc)} frame indices, {len(oo)} object indices, {len(ob)} boxes")
+        if cams is None:
+            F, cp = (self._graph.n_cams if self._graph is not None else 0), _dp()
+        else:
+            cams = np.ascontiguousarray(cams, dtype=np.float64).reshape(-1, 7)
+            F, cp = len(cams), ptr(cams, _dp)
+        N = int(N)
+        n = max(N, 1)
+        e = np.zeros((n, 10)); Q = np.zeros((n, 16)); err = np.zeros(n); stats = np.zeros((n, 4), dtype=np.int32)
+        t0 = time.perf_counter()
+        rc = load().esl_init_quadrics(self._h, cp, C.c_int32(F), C.c_int32(N), ptr(oc, _ip), ptr(oo, _ip), ptr(ob, _dp),
+                                      C.c_int64(len(oc)), Kc.ctypes.data_as(_dp), C.c_int32(rows), C.c_int32(cols), C.c_int32(faithful),
+                                      C.c_int32(min_observations), e.ctypes.data_as(_dp), Q.ctypes.data_as(_dp), err.ctypes.data_as(_dp),
+                                      stats.ctypes.data_as(_ip))
+        self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
+        _check(rc, "esl_init_quadrics")
+        return e[:max(N, 0)], Q[:max(N, 0)].reshape(-1, 4, 4), err[:max(N, 0)], stats[:max(N, 0)]
 
     def fit_frame(self, depth, bboxes, labels, Twc, intr, ground, params=None):
         """EllipsoidExtractor::EstimateLocalEllipsoid for every box of one frame.
