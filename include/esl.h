@@ -51,7 +51,7 @@ extern "C" {
                              *    esl_graph_obj_fixed) with ESL_SOLVER_CAMERA_CHAIN, and relocalisation against a fixed map
                              *    (esl_reloc_set_map, esl_relocalize), and 2-D data association against the projected map
                              *    (esl_predict_boxes, esl_associate_boxes), and the SVD initialisation of many ellipsoids in one call
-                             *    (esl_init_quadrics) */
+                             *    (esl_init_quadrics) and its outlier-rejecting form (esl_init_quadrics_robust) */
 #define ESL_MAX_TRACE 32
 
 typedef enum {
@@ -560,6 +560,61 @@ int esl_init_quadrics(esl_ctx* ctx,
                       const double K[4], int32_t rows, int32_t cols, int32_t faithful, int32_t min_observations,
                       double* ellipsoids_out /* N x 10 */, double* qstar_out /* N x 16 or NULL */,
                       double* plane_error_out /* N or NULL */, int32_t* stats_out /* N x 4 or NULL: status, observations, planes, spilled */);
+
+/* ---- consensus SVD initialisation: esl_init_quadrics that rejects outlier boxes (additive part of ABI 5: detect by the symbol) -------
+ * esl_init_quadrics takes the null vector of ALL tangent planes of an object: one box of a neighbouring object moves Q* far off or makes
+ * the decomposition reject it.  esl_init_quadrics_robust fits small view subsets instead, scores every fit by the boxes it projects and
+ * keeps the consensus: an exhaustive, totally ordered, bit-reproducible hypothesise-and-score search on the device.  Inputs, grouping,
+ * conventions (Tcw poses, cams == NULL = the resident states, entries with obs_obj < 0 skipped), errors and resource behaviour are
+ * esl_init_quadrics'.  Per object o with n list entries, local indices 0 .. n-1 in list order:
+ *  1. Early statuses 1 (n < min_observations) and 2 (fewer than 9 kept lines over all entries) as in esl_init_quadrics.
+ *  2. Hypotheses.  s = min(sample_size, n).  n <= sample_size: one hypothesis, h = 0, over all entries.  Otherwise h = 0 ..
+ *     n_hypotheses - 1, and hypothesis h uses the s distinct indices of Floyd's sampling: for k = 0 .. s-1, j = n - s + k,
+ *     t = (mix(seed, h, k) >> 11) % (j + 1); take t, or j if t was taken before.  mix = the splitmix64 finaliser (shifts 30, 27, 31,
+ *     multipliers 0xBF58476D1CE4E5B9, 0x94D049BB133111EB) of seed ^ (0x9E3779B97F4A7C15 * (uint64)(32 h + k + 1)), all mod 2^64.  The
+ *     indices are used in ascending order.  The stream depends on (seed, h, k, n) only: an object's result does not depend on the
+ *     rest of the batch.
+ *  3. Fit: the plane rows of the hypothesis's entries, the one-sided Jacobi SVD and the decomposition of esl_init_quadrics (the same
+ *     line-keeping rule, sign convention, faithful and Tcw convention).  Invalid with fewer than 9 planes or a rejected Q*.
+ *  4. Score over ALL n entries.  r_i = the largest |b_k - d_k| over entry i's kept lines, b the unclipped box of the projected outline
+ *     as the bbox edge computes it; r_i = +inf when the bbox edge's visibility predicate (checkVisibility, Optimizer.cpp:35-81) fails,
+ *     b is not finite, the entry has no kept line or all four of its coordinates are < 1.  Inlier iff r_i <= inlier_px; n_in = the
+ *     inliers, cost = the sum of r_i^2 over them (a lane adds its entries i = lane, lane + 64, .. in rising order, then a fixed
+ *     butterfly over the 64 lanes: the order depends on n alone).
+ *  5. Winner: largest n_in, then smallest cost, then smallest h -- a total order.  No valid hypothesis: status 4.  A winner with
+ *     n_in < min_inliers: status 5.
+ *  6. refine != 0: esl_init_quadrics' own arithmetic over the winner's inlier entries (the same call, non-inliers skipped: small tile,
+ *     large tile or slab by the inlier count), scored over all n entries, and kept iff it is valid and its (n_in, cost) is not worse.
+ *     Then the final inlier set is the re-scored one and refined = 1; otherwise the winner's ellipsoid, Q* and set are returned.
+ *  7. Outputs.  Status 0: the ellipsoid, its Q* (the SVD's) and quadricErrorWithPlanes over the planes of the final inlier entries.
+ *     stats_out[8 o ..] = status, observations, planes (kept lines of ALL entries), spilled (the refit's), final inliers, valid
+ *     hypotheses, winner h or -1, refined.  Statuses 1, 2, 4, 5: ellipsoid, Q* and plane error zero; 1 and 2 report status,
+ *     observations and planes as esl_init_quadrics does, 0 valid hypotheses and winner -1; 4 adds planes; 5 also reports the winner,
+ *     its inliers and the valid hypotheses.  inlier_out[i] = 1 / 0 and residual_out[i] = r_i under the RETURNED ellipsoid; 0 and NaN
+ *     for skipped entries and for objects whose status is not 0.  hyp_out[(o n_hypotheses + h) 4 ..] = valid, planes, n_in, cost of
+ *     hypothesis h, for tests and tuning; unused rows, and all rows of objects of status 1 or 2, are zero.
+ * ESL_ERR_INVALID, beside esl_init_quadrics' cases: sample_size outside 3..16, n_hypotheses outside 1..1024, inlier_px not finite or
+ * <= 0, min_inliers < 1, N * n_hypotheses >= 2^31.  The call keeps grow-only buffers of its own, allocates nothing when warm, issues no
+ * collective, leaves the resident graph alone and brackets its launches as kernel class 4.  With refine it synchronises twice more than
+ * esl_init_quadrics does: the host builds the refit's list from the winners' flags.
+ * The defaults below are design choices, not values tuned on real data. */
+typedef struct {
+  int32_t sample_size;    /* 5: views per hypothesis, 3..16 */
+  int32_t n_hypotheses;   /* 64: per object, 1..1024 */
+  double  inlier_px;      /* 10: finite, > 0 */
+  int32_t min_inliers;    /* 8: >= 1 */
+  int32_t refine;         /* 1: re-fit on the winner's inliers, kept only when not worse */
+  uint64_t seed;          /* 0 */
+} esl_init_robust_params; /* 32 bytes */
+void esl_init_robust_params_default(esl_init_robust_params* p);
+
+int esl_init_quadrics_robust(esl_ctx* ctx, const double* cams /* F x 7 Tcw, NULL = resident camera states */, int32_t F, int32_t N,
+                             const int32_t* obs_cam, const int32_t* obs_obj, const double* obs_boxes, int64_t n_obs,
+                             const double K[4], int32_t rows, int32_t cols, int32_t faithful, int32_t min_observations,
+                             const esl_init_robust_params* p /* NULL = defaults */,
+                             double* ellipsoids_out /* N x 10 */, double* qstar_out /* N x 16 or NULL */, double* plane_error_out /* N or NULL */,
+                             int32_t* stats_out /* N x 8 or NULL */, int32_t* inlier_out /* n_obs or NULL */, double* residual_out /* n_obs or NULL */,
+                             double* hyp_out /* N x n_hypotheses x 4 or NULL: valid, planes, inliers, cost */);
 
 /* ---- relocalisation: camera pose and detection -> map association with NO pose prior (additive part of ABI 5: detect by the symbol) ---
  * esl_optimize_fixed refines a pose that is already inside the basin of its edges and needs the edge lists, i.e. which detection is

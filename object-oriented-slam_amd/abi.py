@@ -169,6 +169,22 @@ def default_assoc_params(**kw):
     return p
 
 
+class EslInitRobustParams(C.Structure):
+    """esl_init_robust_params: the hypothesise-and-score search of esl_init_quadrics_robust."""
+    _fields_ = [("sample_size", C.c_int32), ("n_hypotheses", C.c_int32), ("inlier_px", C.c_double), ("min_inliers", C.c_int32),
+                ("refine", C.c_int32), ("seed", C.c_uint64)]
+
+
+def default_init_robust_params(**kw):
+    """esl_init_robust_params_default: design choices, not values tuned on real data (include/esl.h)."""
+    p = EslInitRobustParams(sample_size=5, n_hypotheses=64, inlier_px=10.0, min_inliers=8, refine=1, seed=0)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
 ROBUST_KINDS = {"none": 0, "huber": 1, "pseudo_huber": 2, "cauchy": 3, "tukey": 4}   # esl_robust_kind (include/esl.h)
 EDGE_CLASSES = {"bbox": 0, "e3d": 1, "grav": 2, "odom": 3}                         # esl_edge_class
 

@@ -26,6 +26,7 @@ EXPORTS = [
     "esl_init_quadric", "esl_init_from_qstar", "esl_init_plane_error", "esl_init_quadrics", "esl_plane_params_default", "esl_extract_ground_plane", "esl_extract_planes",
     "esl_reloc_params_default", "esl_reloc_set_map", "esl_relocalize",
     "esl_assoc_params_default", "esl_predict_boxes", "esl_associate_boxes",
+    "esl_init_robust_params_default", "esl_init_quadrics_robust",
 ]
 
 
@@ -373,6 +374,45 @@ class Context:
         self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
         _check(rc, "esl_init_quadrics")
         return e[:max(N, 0)], Q[:max(N, 0)].reshape(-1, 4, 4), err[:max(N, 0)], stats[:max(N, 0)]
+
+    def init_quadrics_robust(self, cams, N, obs_cam, obs_obj, obs_boxes, K, rows=480, cols=640, faithful=1, min_observations=0,
+                             params=None, want_hyp=False):
+        """esl_init_quadrics_robust: esl_init_quadrics by consensus over small view subsets, which rejects outlier boxes.  Arguments as
+        init_quadrics; params an abi.EslInitRobustParams (None: the defaults).  Returns dict(ellipsoids (N, 10), qstar (N, 4, 4),
+        plane_error (N,), stats (N, 8): status, observations, planes, spilled, final inliers, valid hypotheses, winner, refined;
+        inliers (n_obs,) 0 / 1, residuals (n_obs,) px or NaN, hyp (N, n_hypotheses, 4): valid, planes, inliers, cost -- or None)."""
+        _ip = C.POINTER(C.c_int32)
+
+        def ptr(a, t):
+            return a.ctypes.data_as(t) if a.size else t()
+        p = params if params is not None else abi.default_init_robust_params()
+        Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(4)
+        oc = np.ascontiguousarray(obs_cam, dtype=np.int32).reshape(-1)
+        oo = np.ascontiguousarray(obs_obj, dtype=np.int32).reshape(-1)
+        ob = np.ascontiguousarray(obs_boxes, dtype=np.float64).reshape(-1, 4)
+        if not len(oc) == len(oo) == len(ob):
+            raise ValueError(f"{len(oc)} frame indices, {len(oo)} object indices, {len(ob)} boxes")
+        if cams is None:
+            F, cp = (self._graph.n_cams if self._graph is not None else 0), _dp()
+        else:
+            cams = np.ascontiguousarray(cams, dtype=np.float64).reshape(-1, 7)
+            F, cp = len(cams), ptr(cams, _dp)
+        N = int(N)
+        n, no, H = max(N, 1), max(len(oc), 1), max(int(p.n_hypotheses), 1)
+        e = np.zeros((n, 10)); Q = np.zeros((n, 16)); err = np.zeros(n); stats = np.zeros((n, 8), dtype=np.int32)
+        inl = np.zeros(no, dtype=np.int32); res = np.full(no, np.nan)
+        hyp = np.zeros((n, H, 4)) if want_hyp else None
+        t0 = time.perf_counter()
+        rc = load().esl_init_quadrics_robust(self._h, cp, C.c_int32(F), C.c_int32(N), ptr(oc, _ip), ptr(oo, _ip), ptr(ob, _dp),
+                                             C.c_int64(len(oc)), Kc.ctypes.data_as(_dp), C.c_int32(rows), C.c_int32(cols),
+                                             C.c_int32(faithful), C.c_int32(min_observations), C.byref(p), e.ctypes.data_as(_dp),
+                                             Q.ctypes.data_as(_dp), err.ctypes.data_as(_dp), stats.ctypes.data_as(_ip),
+                                             inl.ctypes.data_as(_ip), res.ctypes.data_as(_dp), hyp.ctypes.data_as(_dp) if want_hyp else _dp())
+        self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
+        _check(rc, "esl_init_quadrics_robust")
+        N = max(N, 0)
+        return dict(ellipsoids=e[:N], qstar=Q[:N].reshape(-1, 4, 4), plane_error=err[:N], stats=stats[:N], inliers=inl[:len(oc)],
+                    residuals=res[:len(oc)], hyp=hyp[:N] if want_hyp else None)
 
     def fit_frame(self, depth, bboxes, labels, Twc, intr, ground, params=None):
         """EllipsoidExtractor::EstimateLocalEllipsoid for every box of one frame.
