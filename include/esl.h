@@ -51,7 +51,8 @@ extern "C" {
                              *    esl_graph_obj_fixed) with ESL_SOLVER_CAMERA_CHAIN, and relocalisation against a fixed map
                              *    (esl_reloc_set_map, esl_relocalize), and 2-D data association against the projected map
                              *    (esl_predict_boxes, esl_associate_boxes), and the SVD initialisation of many ellipsoids in one call
-                             *    (esl_init_quadrics) and its outlier-rejecting form (esl_init_quadrics_robust) */
+                             *    (esl_init_quadrics) and its outlier-rejecting form (esl_init_quadrics_robust), and map maintenance
+                             *    (esl_map_overlaps, esl_map_merge) */
 #define ESL_MAX_TRACE 32
 
 typedef enum {
@@ -726,6 +727,82 @@ int esl_associate_boxes(esl_ctx* ctx, const double* cams /* F x 7 Tcw, NULL = re
                         const int32_t* det_labels /* n_det */, const esl_assoc_params* p /* NULL = defaults */,
                         int32_t* assoc_out /* n_det: map index or -1 */, double* iou_out /* n_det or NULL */,
                         int32_t* frame_stats_out /* F x 4 or NULL: eligible, occluded, assigned, spilled */);
+
+/* ---- map maintenance: find and fuse duplicate ellipsoids of a map (additive part of ABI 5: detect by the symbol) --------------------------
+ * Every call above takes the association as given; a detection that matches no prediction becomes a new instance at the caller
+ * (CreateInstance, DataAssociation.cpp:127-131), so an object seen again after a gap, from the other side, after a loop closure, or
+ * split off as outliers by esl_init_quadrics_robust stands in the map twice.  esl_map_merge decides which ellipsoids of a map are the same
+ * object, fuses them and rewrites an edge list onto the repaired map, with the obs_obj < 0 = skipped convention of esl_init_quadrics
+ * and esl_associate_boxes.  Everything runs in FP64; every decision is an integer comparison or a total order, so the result does not
+ * depend on the order in which threads meet the pairs, and runs are bit-reproducible.
+ *  1. Valid ellipsoid: all ten numbers finite, the quaternion's norm finite and > 0 (it is normalised), the half-axes s = (|a|, |b|, |c|)
+ *     all > 0.  An invalid ellipsoid is in no pair and forms a group of its own.
+ *  2. Lattice.  With n = lattice: the integer triples k = (kx, ky, kz), each 2 p + 1 - n for p = 0 .. n - 1, with |k|^2 <= n^2 (an integer
+ *     test; no triple lies on the sphere), N_ball(n) of them: 32, 280, 2176, 17256 for n = 4, 8, 16, 32.  Unit-ball point u = k / n;
+ *     sample of ellipsoid i: x = c_i + R_i (s_i o u).
+ *  3. Counts.  cnt_ij = the samples of i with |diag(1 / s_j) R_j^T (x - c_j)|^2 <= 1, cnt_ji likewise with the roles swapped.
+ *     V = 4/3 pi s0 s1 s2; inter = (cnt_ij V_i + cnt_ji V_j) / (2 N_ball); iou = inter / (V_i + V_j - inter);
+ *     contain = min(1, inter / min(V_i, V_j)).  The lattice, not a closed form: there is none for two oriented ellipsoids, and counts
+ *     are integers, which every device reproduces.  The estimator's error at n = 16 is about 0.006 in IoU (tests/map_merge_scenes.py).
+ *  4. Candidates: the pairs i < j of valid ellipsoids, of equal label if match_labels, with |c_i - c_j|^2 <= (r_i + r_j)^2 (1 + 1e-9),
+ *     r = max(s) -- a pair that fails this has both counts 0, the gate only saves work.  All pairs are tried (M <= 65536).  The
+ *     OVERLAPPING pairs are the candidates with cnt_ij + cnt_ji > 0, in (i, j) lexicographic order.  More than max_pairs candidates:
+ *     status 3, nothing is merged.
+ *  5. Links: an overlapping pair with iou >= min_iou or contain >= min_contain.  Groups are the connected components of the links, so
+ *     chains merge transitively: A ~ B and B ~ C puts all three in one group even when A and C do not overlap.  A group's id is its
+ *     smallest member index.
+ *  6. Weights: int32 >= 0 with a total below 2^31; weights == NULL: the number of an object's list entries, or 1 for every object when
+ *     no list is given.  The representative of a group is the member with the largest weight, ties to the lowest index.  Groups are
+ *     numbered 0 .. n_groups - 1 in ascending order of group id, so unmerged objects keep their relative order.  Row g of the merged map
+ *     is the representative's ten numbers bit for bit -- no averaging of poses: an ellipsoid's axes are defined only up to permutation
+ *     and sign --, the merged label is the representative's, the merged weight the integer sum of the members' weights.
+ *  7. Edge list (n_obs > 0): obs_obj_out[e] = new_index[obs_obj[e]], entries with obs_obj < 0 stay -1.  Of the entries that now share
+ *     one (obs_cam, new object) -- both copies were boxed in one frame -- the one survives that comes first in the total order: larger
+ *     weight of the ORIGINAL object, then lower original index, then lower list position.  The others become -1 and are counted in
+ *     n_conflicts. */
+typedef struct {
+  int32_t lattice;      /* 16: n of step 2, 4 .. 32 */
+  int32_t match_labels; /* 1: candidates need equal labels; 0: labels ignored */
+  double min_iou;       /* 0.3: finite, in (0, 1] */
+  double min_contain;   /* 0.7: finite, > 0; > 1 = containment never links */
+  int32_t max_pairs;    /* 4194304: more candidates than this give status 3 */
+  int32_t pad;
+} esl_merge_params;     /* 32 bytes; design choices, not values tuned on real data */
+void esl_merge_params_default(esl_merge_params* p);
+
+/* Inspection and tests: the overlapping pairs of step 4 with their integers and measures.  n_pairs reports how many were found, only the
+ * first cap of them are written; with more than max_pairs candidates n_candidates reports them, n_pairs is -1 and nothing is written.
+ * Errors as esl_map_merge. */
+int esl_map_overlaps(esl_ctx* ctx, const double* objs /* M x 10, NULL = resident ellipsoid states (M must equal n_objs) */,
+                     const int32_t* labels /* M */, int32_t M, const esl_merge_params* p /* NULL = defaults */, int64_t cap,
+                     int32_t* pairs_out /* cap x 2: i, j */, int32_t* counts_out /* cap x 2: cnt_ij, cnt_ji */, double* iou_out /* cap */,
+                     double* contain_out /* cap */, int64_t* n_pairs, int64_t* n_candidates);
+
+typedef struct {
+  int32_t status;            /* 0 ok, 3 candidates > max_pairs */
+  int32_t n_valid, n_groups;
+  int32_t n_merged_groups;   /* groups of more than one member */
+  int32_t largest_group, n_conflicts;
+  int64_t n_candidates, n_pairs, n_links;
+} esl_merge_result;          /* 48 bytes */
+
+/* Steps 1 - 7.  Status 3 is a result, not an error: the return is ESL_OK, the last error text is left alone, every object is its own
+ * group (new_index = 0 .. M - 1, the merged map is the input, the weights are each object's own) and obs_obj_out is obs_obj with the
+ * negative entries as -1.
+ * ESL_ERR_INVALID: null or negative arguments (labels and the five map outputs are needed whenever M > 0, obs_cam and obs_obj whenever
+ * n_obs > 0), M > 65536, lattice outside 4 .. 32, min_iou not finite or outside (0, 1], min_contain not finite or <= 0, max_pairs < 0,
+ * a negative weight or a weight total >= 2^31, n_obs >= 2^31, a non-skipped entry with obs_obj >= M or obs_cam < 0, M differing from
+ * the resident graph's n_objs when objs == NULL.  ESL_ERR_STATE: objs == NULL without a resident graph and states.  M = 0 and n_obs = 0
+ * are valid.  The calls leave the resident graph, its states and the solver blobs alone, keep grow-only device buffers of their own
+ * (freed by esl_ctx_destroy; a warm call allocates nothing), run on this context's GPU only and issue no collective.  With
+ * esl_profile_enable(ctx, 2) their launches are bracketed as kernel class 4. */
+int esl_map_merge(esl_ctx* ctx, const double* objs /* M x 10, NULL = resident ellipsoid states */, const int32_t* labels /* M */,
+                  const int32_t* weights /* M or NULL */, int32_t M,
+                  const int32_t* obs_cam /* n_obs */, const int32_t* obs_obj /* n_obs: 0..M-1, < 0 = entry skipped */, int64_t n_obs /* may be 0 */,
+                  const esl_merge_params* p /* NULL = defaults */,
+                  int32_t* group_out /* M: group id */, int32_t* new_index_out /* M: row of the merged map */,
+                  double* merged_objs_out /* M x 10, the first n_groups rows are written */, int32_t* merged_labels_out /* M */,
+                  int32_t* merged_weights_out /* M */, int32_t* obs_obj_out /* n_obs or NULL */, esl_merge_result* out);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------*/
 /* Dense FP64-MFMA Cholesky factor + solve (the reduced-camera solver of SLAM mode) on a procedurally generated,

@@ -185,6 +185,32 @@ def default_init_robust_params(**kw):
     return p
 
 
+class EslMergeParams(C.Structure):
+    """esl_merge_params: the lattice and the thresholds of esl_map_overlaps / esl_map_merge."""
+    _fields_ = [("lattice", C.c_int32), ("match_labels", C.c_int32), ("min_iou", C.c_double), ("min_contain", C.c_double),
+                ("max_pairs", C.c_int32), ("pad", C.c_int32)]
+
+
+class EslMergeResult(C.Structure):
+    """esl_merge_result: what esl_map_merge did (status 0), or that it did nothing (3: more candidates than max_pairs)."""
+    _fields_ = [("status", C.c_int32), ("n_valid", C.c_int32), ("n_groups", C.c_int32), ("n_merged_groups", C.c_int32),
+                ("largest_group", C.c_int32), ("n_conflicts", C.c_int32), ("n_candidates", C.c_int64), ("n_pairs", C.c_int64),
+                ("n_links", C.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def default_merge_params(**kw):
+    """esl_merge_params_default: design choices, not values tuned on real data (include/esl.h)."""
+    p = EslMergeParams(lattice=16, match_labels=1, min_iou=0.3, min_contain=0.7, max_pairs=4194304, pad=0)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
 ROBUST_KINDS = {"none": 0, "huber": 1, "pseudo_huber": 2, "cauchy": 3, "tukey": 4}   # esl_robust_kind (include/esl.h)
 EDGE_CLASSES = {"bbox": 0, "e3d": 1, "grav": 2, "odom": 3}                         # esl_edge_class
 

@@ -27,6 +27,7 @@ EXPORTS = [
     "esl_reloc_params_default", "esl_reloc_set_map", "esl_relocalize",
     "esl_assoc_params_default", "esl_predict_boxes", "esl_associate_boxes",
     "esl_init_robust_params_default", "esl_init_quadrics_robust",
+    "esl_merge_params_default", "esl_map_overlaps", "esl_map_merge",
 ]
 
 
@@ -590,6 +591,77 @@ class Context:
         self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
         _check(rc, "esl_associate_boxes")
         return assoc[:n], iou[:n], stats[:F]
+
+    def _merge_map(self, objs, labels):
+        """(M, objs pointer, labels array, the array behind the pointer) of map_overlaps / map_merge; objs None: the resident states"""
+        lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        if objs is None:
+            return len(lab), _dp(), lab, None
+        objs = np.ascontiguousarray(objs, dtype=np.float64).reshape(-1, 10)
+        if len(objs) != len(lab):
+            raise ValueError(f"{len(objs)} ellipsoids, {len(lab)} labels")
+        return len(objs), (objs.ctypes.data_as(_dp) if len(objs) else _dp()), lab, objs
+
+    def map_overlaps(self, objs, labels, params=None, cap=None):
+        """esl_map_overlaps: the overlapping pairs of a map with their lattice counts and measures.  objs (M, 10) world ellipsoids, or
+        None for the resident graph's current ellipsoid states; labels (M,); cap: how many pairs to fetch at most (None: all).  Returns
+        dict(pairs (k, 2), counts (k, 2): cnt_ij, cnt_ji, iou (k,), contain (k,), n_pairs, n_candidates), k = min(cap, n_pairs);
+        n_pairs is -1 when there are more candidates than max_pairs."""
+        p = params if params is not None else abi.default_merge_params()
+        _ip, _lp = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        M, op, lab, _keep = self._merge_map(objs, labels)
+        n_pairs, n_cand = C.c_int64(0), C.c_int64(0)
+
+        def call(cap):
+            k = max(int(cap), 1)
+            pairs = np.zeros((k, 2), dtype=np.int32); cnt = np.zeros((k, 2), dtype=np.int32); iou = np.zeros(k); con = np.zeros(k)
+            t0 = time.perf_counter()
+            rc = load().esl_map_overlaps(self._h, op, lab.ctypes.data_as(_ip) if M else _ip(), C.c_int32(M), C.byref(p), C.c_int64(cap),
+                                         pairs.ctypes.data_as(_ip), cnt.ctypes.data_as(_ip), iou.ctypes.data_as(_dp), con.ctypes.data_as(_dp),
+                                         C.byref(n_pairs), C.byref(n_cand))
+            self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
+            _check(rc, "esl_map_overlaps")
+            return pairs, cnt, iou, con
+        if cap is None:              # ask for the count, then for everything
+            call(0)
+            cap = max(n_pairs.value, 0)
+        pairs, cnt, iou, con = call(cap)
+        k = max(min(int(cap), n_pairs.value), 0)
+        return dict(pairs=pairs[:k], counts=cnt[:k], iou=iou[:k], contain=con[:k], n_pairs=n_pairs.value, n_candidates=n_cand.value)
+
+    def map_merge(self, objs, labels, weights=None, obs_cam=None, obs_obj=None, params=None):
+        """esl_map_merge: find the duplicate ellipsoids of a map, fuse them, rewrite an edge list.  objs (M, 10) or None for the resident
+        ellipsoid states; labels (M,); weights (M,) int or None (the objects' list entries, or 1 without a list); obs_cam / obs_obj
+        (n_obs,) the edge list or None.  Returns dict(result: dict of esl_merge_result, group (M,), new_index (M,), objs (n_groups, 10),
+        labels (n_groups,), weights (n_groups,), obs_obj (n_obs,) or None)."""
+        p = params if params is not None else abi.default_merge_params()
+        _ip = C.POINTER(C.c_int32)
+
+        def ptr(a, t):
+            return a.ctypes.data_as(t) if a is not None and a.size else t()
+        M, op, lab, _keep = self._merge_map(objs, labels)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.int32).reshape(-1)
+        if w is not None and len(w) != M:
+            raise ValueError(f"{M} ellipsoids, {len(w)} weights")
+        oc = None if obs_cam is None else np.ascontiguousarray(obs_cam, dtype=np.int32).reshape(-1)
+        oo = None if obs_obj is None else np.ascontiguousarray(obs_obj, dtype=np.int32).reshape(-1)
+        if (oc is None) != (oo is None) or (oc is not None and len(oc) != len(oo)):
+            raise ValueError("obs_cam and obs_obj go together and have equal lengths")
+        n_obs = 0 if oo is None else len(oo)
+        m = max(M, 1)
+        group = np.zeros(m, dtype=np.int32); new = np.zeros(m, dtype=np.int32); mo = np.zeros((m, 10)); ml = np.zeros(m, dtype=np.int32)
+        mw = np.zeros(m, dtype=np.int32); out = np.full(max(n_obs, 1), -1, dtype=np.int32)
+        res = abi.EslMergeResult()
+        t0 = time.perf_counter()
+        rc = load().esl_map_merge(self._h, op, ptr(lab, _ip), ptr(w, _ip), C.c_int32(M), ptr(oc, _ip), ptr(oo, _ip), C.c_int64(n_obs),
+                                  C.byref(p), group.ctypes.data_as(_ip), new.ctypes.data_as(_ip), mo.ctypes.data_as(_dp),
+                                  ml.ctypes.data_as(_ip), mw.ctypes.data_as(_ip), out.ctypes.data_as(_ip) if n_obs else _ip(),
+                                  C.byref(res))
+        self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
+        _check(rc, "esl_map_merge")
+        G = res.n_groups
+        return dict(result=res.as_dict(), group=group[:M], new_index=new[:M], objs=mo[:G], labels=ml[:G], weights=mw[:G],
+                    obs_obj=out[:n_obs] if oo is not None else None)
 
     def selftest_cholesky(self, n):
         """(ms, relative residual) of the dense FP64-MFMA Cholesky factor + solve on a generated SPD system."""
