@@ -817,6 +817,10 @@ int esl_selftest_cholesky(esl_ctx* ctx, int32_t n, double* ms_out, double* rel_r
  * ESL_CHOL_FUSE=0 puts strips 0, 1 of every panel and the diagonal halves of the quarter tasks back on the list (the chain does
  * them itself by default).  Call with null buffers for the sizes. */
 int esl_debug_chol_plan(int32_t n, int32_t W, int32_t filler, int32_t* tasks_out, int64_t cap_tasks, int32_t* ns_out, int64_t cap_ns, int32_t meta_out[5]);
+/* test / debug: would the rank-K update of rows [base, rows) x columns [base, col_limit) of a matrix with leading dimension lda
+ * (ext != 0: the operand is external, leading dimension ldp) run on the 128 x 128 tile kernel -- the one whose assign form lets the
+ * camera-first trial run the segments' products beside the update?  Host code only; ESL_UPD_V=0 answers no everywhere. */
+int esl_debug_update_v_applies(int64_t lda, int64_t rows, int64_t base, int64_t col_limit, int32_t ext, int64_t ldp, int32_t* applies_out);
 
 #ifdef __cplusplus
 }

@@ -321,7 +321,12 @@ static __global__ __launch_bounds__(64) void k_cf_forward(int nf_all, int n_o, i
   constexpr bool SEP = MODE == 1;
   __shared__ double sM[kCfFwdCh * 36];
   __shared__ double sZ[kCfFwdCh * 36];
-  __shared__ double sv[kCfFwdCh * 6 * 64];
+  // MODE 2: the slab of a chunk in two HALVES of kCfFwdCh / 2 cameras, one after the other through the same LDS -- 34.5 KB per
+  // one-wave workgroup instead of 59 KB, so four of them fit a CU where two did (the grid is 23,565 waves at C4 and the kernel is
+  // bound by the waves in flight).  The entries of a slot are still added in list order, each half walks the chunk's entry
+  // range and takes its own slots: every sum has the bits it had.  MODE 0 and MODE 1: one part, the whole chunk.
+  constexpr int CH = MODE == 2 ? kCfFwdCh / 2 : kCfFwdCh;
+  __shared__ double sv[CH * 6 * 64];
   __shared__ double svy[kCfFwdCh * 6];
   const int lane = threadIdx.x;
   const int seg = SEP ? 0 : (MODE == 2 ? sg.fwork[2 * blockIdx.x] : (int)blockIdx.y);
@@ -357,95 +362,98 @@ static __global__ __launch_bounds__(64) void k_cf_forward(int nf_all, int n_o, i
 #pragma unroll
       for (int q = 0; q < 2; ++q) if (q * 64 + lane < kCfFwdCh * 6) svy[q * 64 + lane] = ty[q];   // (used by the right-hand-side lane only)
     }
-    if (SEP) {   // dense right-hand sides of the separators: rows 6 i0 .. of R
-      // clamped addresses + selects, ALL 96 loads of the chunk in flight together: the grid is one wave per 64 columns (282 waves
-      // at C4), so the bytes in flight per wave set the bandwidth -- a guarded load per element (96 dependent round trips per chunk)
-      // and batches of 16 both took 2.2 ms per trial at C4's 625 separators
-      const size_t jc = on ? (size_t)j : 0;
-      {
-        constexpr int kQ = kCfFwdCh * 6;
-        double t[kQ];
+    for (int h0 = 0; h0 < (MODE == 2 ? len : 1); h0 += CH) {   // the parts of the chunk: cameras i0 + h0 .. i0 + h0 + hl - 1
+      const int hl = MODE == 2 ? ((len - h0 < CH) ? len - h0 : CH) : len;
+      if (SEP) {   // dense right-hand sides of the separators: rows 6 i0 .. of R
+        // clamped addresses + selects, ALL 96 loads of the chunk in flight together: the grid is one wave per 64 columns (282 waves
+        // at C4), so the bytes in flight per wave set the bandwidth -- a guarded load per element (96 dependent round trips per chunk)
+        // and batches of 16 both took 2.2 ms per trial at C4's 625 separators
+        const size_t jc = on ? (size_t)j : 0;
+        {
+          constexpr int kQ = kCfFwdCh * 6;
+          double t[kQ];
 #pragma unroll
-        for (int q = 0; q < kQ; ++q) t[q] = R[jc + (size_t)(6 * i0 + (q < len * 6 ? q : 0)) * (size_t)ldx];
+          for (int q = 0; q < kQ; ++q) t[q] = R[jc + (size_t)(6 * i0 + (q < len * 6 ? q : 0)) * (size_t)ldx];
 #pragma unroll
-        for (int q = 0; q < kQ; ++q) sv[q * 64 + lane] = (on && q < len * 6) ? t[q] : 0.0;
-      }
-      __builtin_amdgcn_wave_barrier();
-    } else {
+          for (int q = 0; q < kQ; ++q) sv[q * 64 + lane] = (on && q < len * 6) ? t[q] : 0.0;
+        }
+        __builtin_amdgcn_wave_barrier();
+      } else {
 #pragma unroll
-      for (int q = 0; q < kCfFwdCh * 6; ++q) sv[q * 64 + lane] = 0.0;
-      __builtin_amdgcn_wave_barrier();
-      if (rhs) {
+        for (int q = 0; q < CH * 6; ++q) sv[q * 64 + lane] = 0.0;
+        __builtin_amdgcn_wave_barrier();
+        if (rhs) {
 #pragma unroll
-        for (int q = 0; q < kCfFwdCh * 6; ++q) sv[q * 64 + lane] = (q < len * 6) ? svy[q] : 0.0;
-      } else if (col) {
-        const int ka = cst[ch], kb = cst[ch + 1];
-        for (int k = ka; k < kb; k += 4) {       // batches of four entries: slots and records of a batch in flight together
-          int sl[4];
-          double rec[4][6];
+          for (int q = 0; q < CH * 6; ++q) sv[q * 64 + lane] = (q < hl * 6) ? svy[h0 * 6 + q] : 0.0;
+        } else if (col) {
+          const int ka = cst[ch], kb = cst[ch + 1];
+          for (int k = ka; k < kb; k += 4) {       // batches of four entries: slots and records of a batch in flight together
+            int sl[4];
+            double rec[4][6];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int kk = (k + e < kb) ? k + e : ka;
-            sl[e] = oe_slot[kk];
-            const double* src = V + ((size_t)kk * 9 + b) * 6;
+            for (int e = 0; e < 4; ++e) {
+              const int kk = (k + e < kb) ? k + e : ka;
+              sl[e] = oe_slot[kk];
+              const double* src = V + ((size_t)kk * 9 + b) * 6;
 #pragma unroll
-            for (int a = 0; a < 6; ++a) rec[e][a] = src[a];
+              for (int a = 0; a < 6; ++a) rec[e][a] = src[a];
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              if (k + e < kb && sl[e] - i0 >= h0 && sl[e] - i0 - h0 < hl) {   // (slots behind the segment's end in this chunk: the separator's entries)
+#pragma unroll
+                for (int a = 0; a < 6; ++a) sv[((sl[e] - i0 - h0) * 6 + a) * 64 + lane] += rec[e][a];   // (a bbox and a 3-D edge of one camera add up)
+              }
           }
+        }
+        __builtin_amdgcn_wave_barrier();
+      }
+      // (2) the serial steps, LDS only
+      for (int ii = 0; ii < hl; ++ii) {
+        const double* M = sM + (h0 + ii) * 36;
+        double xn[6];
 #pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (k + e < kb && sl[e] - i0 < len) {   // (slots behind the segment's end in this chunk: the separator's entries)
+        for (int a = 0; a < 6; ++a) {
+          double t = sv[(ii * 6 + a) * 64 + lane];
 #pragma unroll
-              for (int a = 0; a < 6; ++a) sv[((sl[e] - i0) * 6 + a) * 64 + lane] += rec[e][a];   // (a bbox and a 3-D edge of one camera add up)
+          for (int q = 0; q < 6; ++q) t -= M[a * 6 + q] * x[q];
+          xn[a] = t;
+        }
+#pragma unroll
+        for (int a = 0; a < 6; ++a) { x[a] = xn[a]; sv[(ii * 6 + a) * 64 + lane] = xn[a]; }
+        if (use_z) {
+          const double* Z = sZ + (h0 + ii) * 36;
+#pragma unroll
+          for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int q = 0; q < 6; ++q) acc[a] += Z[q * 6 + a] * xn[q];
+        }
+      }
+      // (3) out: batches of eight LDS reads, then their eight stores.  Straight-line code (fixed trip count, predicated stores): as a
+      // run-time loop every batch waited for the previous batch's stores (the s_waitcnt vmcnt(0) at the loop head) -- hidden where
+      // thousands of waves run, 18 us per chunk over the separators, where the grid is one wave per 64 columns
+      if (on) {
+#pragma unroll
+        for (int q0 = 0; q0 < CH * 6; q0 += 8) {
+          double t[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) t[e] = sv[((q0 + e < hl * 6) ? q0 + e : 0) * 64 + lane];
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            if (q0 + e < hl * 6) {
+              const int q = q0 + e;   // (MODE 0, 1: h0 = 0)
+              // separator k = i0 + q / 6 sits at slot k sep_stride + sep_stride - 1
+              if (MODE == 2) {
+                Xt[(size_t)sg.xoff[seg] + (size_t)(6 * (i0 - beg + h0) + q) * (size_t)sg.xld[seg] + (size_t)j] = t[e];
+              } else {
+                const size_t row = (SEP && sep_stride > 0) ? (size_t)(6 * ((i0 + q / 6) * sep_stride + sep_stride - 1) + q % 6) : (size_t)(6 * i0 + q);
+                Xt[(size_t)j + row * (size_t)ldx] = t[e];
+              }
             }
         }
       }
       __builtin_amdgcn_wave_barrier();
     }
-    // (2) the serial steps, LDS only
-    for (int ii = 0; ii < len; ++ii) {
-      const double* M = sM + ii * 36;
-      double xn[6];
-#pragma unroll
-      for (int a = 0; a < 6; ++a) {
-        double t = sv[(ii * 6 + a) * 64 + lane];
-#pragma unroll
-        for (int q = 0; q < 6; ++q) t -= M[a * 6 + q] * x[q];
-        xn[a] = t;
-      }
-#pragma unroll
-      for (int a = 0; a < 6; ++a) { x[a] = xn[a]; sv[(ii * 6 + a) * 64 + lane] = xn[a]; }
-      if (use_z) {
-        const double* Z = sZ + ii * 36;
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-          for (int q = 0; q < 6; ++q) acc[a] += Z[q * 6 + a] * xn[q];
-      }
-    }
-    // (3) out: batches of eight LDS reads, then their eight stores.  Straight-line code (fixed trip count, predicated stores): as a
-    // run-time loop every batch waited for the previous batch's stores (the s_waitcnt vmcnt(0) at the loop head) -- hidden where
-    // thousands of waves run, 18 us per chunk over the separators, where the grid is one wave per 64 columns
-    if (on) {
-#pragma unroll
-      for (int q0 = 0; q0 < kCfFwdCh * 6; q0 += 8) {
-        double t[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) t[e] = sv[((q0 + e < len * 6) ? q0 + e : 0) * 64 + lane];
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (q0 + e < len * 6) {
-            const int q = q0 + e;
-            // separator k = i0 + q / 6 sits at slot k sep_stride + sep_stride - 1
-            if (MODE == 2) {
-              Xt[(size_t)sg.xoff[seg] + (size_t)(6 * (i0 - beg) + q) * (size_t)sg.xld[seg] + (size_t)j] = t[e];
-            } else {
-              const size_t row = (SEP && sep_stride > 0) ? (size_t)(6 * ((i0 + q / 6) * sep_stride + sep_stride - 1) + q % 6) : (size_t)(6 * i0 + q);
-              Xt[(size_t)j + row * (size_t)ldx] = t[e];
-            }
-          }
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
   }
   if (use_z && on) {
 #pragma unroll

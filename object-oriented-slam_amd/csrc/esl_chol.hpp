@@ -73,6 +73,7 @@ struct CholSwitches {
   int timeout_ms = 0;            // ESL_CHOL_TIMEOUT_MS: bound of k_chol_persist's spins; unset (0): 3 s.  Debugging
   bool timing = false;           // ESL_CHOL_TIMING (set at all): the kernels' diagnostics on, the self test prints chol_print_timing.  Debugging
   bool debug = false;            // ESL_CHOL_DEBUG (set at all): the self test creates and destroys a stream while the factorisation runs.  Debugging
+  bool upd_v_cap = false;        // ESL_UPD_V_CAP=1: EVERY k_chol_update_v launch with one workgroup per CU (kCholLdsVCap): the update alone at half occupancy.  Debugging
 };
 inline CholSwitches chol_switches_from_env() {
   CholSwitches s;
@@ -90,6 +91,7 @@ inline CholSwitches chol_switches_from_env() {
   if (const char* e = std::getenv("ESL_CHOL_TIMEOUT_MS")) s.timeout_ms = std::max(1, std::atoi(e));
   s.timing = std::getenv("ESL_CHOL_TIMING") != nullptr;
   s.debug = std::getenv("ESL_CHOL_DEBUG") != nullptr;
+  if (const char* e = std::getenv("ESL_UPD_V_CAP")) s.upd_v_cap = e[0] == '1';
   return s;
 }
 
@@ -101,6 +103,12 @@ inline bool chol_update_v_applies(const CholSwitches& sw, long lda, long rows, l
   const long big_tiles = ((nrows + 255) / 256) * ((nc + 127) / 128) / (whole ? 2 : 1);
   return big_tiles >= 1024 && sw.upd_v && (lda & 1) == 0 && (base & 1) == 0 && (!ext || (ldp & 1) == 0);
 }
+// Occupancy cap of k_chol_update_v (`cap` below): the launch asks for more than half of a CU's 160 KB of LDS, so ONE of its four-wave
+// workgroups fits a CU instead of two, and half of every SIMD's registers stays free for the waves of a streaming kernel on another
+// stream (esl_slam.hip: the segments' products beside the rank-K update).  The kernel's code does not change: it uses the first
+// kCholLdsV bytes as before.  Alone, the capped rank-3,744 update of C4 takes 17.75 instead of 16.17 ms.
+constexpr size_t kCholLdsVCap = 84 * 1024;
+static_assert(2 * kCholLdsVCap > 160 * 1024 && kCholLdsVCap >= kCholLdsV, "one capped workgroup per CU");
 // C[base.., base..col_limit) -= P P^T on the lower triangle of the (rows x *) matrix M; P = columns [kcol0, kcol0 + K) of M, or
 // Pext (rows x K, leading dimension ldp) when given.  Needs chol_set_attributes() on the current device first.
 // part (optional, with Pext and base = 0): workspace of kCholMaxSplit x lda x col_limit doubles -- few tiles and a long K are split
@@ -108,7 +116,8 @@ inline bool chol_update_v_applies(const CholSwitches& sw, long lda, long rows, l
 // kfirst (optional, with Pext): per group of 64 columns the first row of Pext that can be non-zero there (see the kernel); the array
 // covers rows + 256 columns.
 inline void chol_launch_update(const CholSwitches& sw, double* M, long lda, long rows, hipStream_t stream, int kcol0, int K, long base, long col_limit,
-                               const double* Pext = nullptr, long ldp = 0, double* part = nullptr, const int* kfirst = nullptr, bool assign = false) {
+                               const double* Pext = nullptr, long ldp = 0, double* part = nullptr, const int* kfirst = nullptr, bool assign = false,
+                               bool cap = false) {
   // trailing region: rows [base, rows), cols [base, col_limit)
   const long nrows = rows - base, nc = col_limit - base;
   if (nrows <= 0 || nc <= 0) return;
@@ -123,7 +132,7 @@ inline void chol_launch_update(const CholSwitches& sw, double* M, long lda, long
     if (chol_update_v_applies(sw, lda, rows, base, col_limit, Pext != nullptr, ldp)) {
       const long vI = (nrows + kVT - 1) / kVT, vJ = (nc + kVT - 1) / kVT;
       const long vblk = whole ? chol_v_grid(vI) : vI * vJ;
-      hipLaunchKernelGGL(k_chol_update_v, dim3((unsigned)vblk), dim3(256), kCholLdsV, stream, M, lda, rows, col_limit, kcol0, K, base, (int)vJ, whole ? 0 : 1, Pext, ldp,
+      hipLaunchKernelGGL(k_chol_update_v, dim3((unsigned)vblk), dim3(256), (cap || sw.upd_v_cap) ? kCholLdsVCap : kCholLdsV, stream, M, lda, rows, col_limit, kcol0, K, base, (int)vJ, whole ? 0 : 1, Pext, ldp,
                          Pext ? kfirst : nullptr, assign ? 1 : 0);
       return;
     }
@@ -213,6 +222,7 @@ inline hipError_t chol_set_attributes(CholRuntime& rt) {
   rt.sw = chol_switches_from_env();
   hipError_t e = hipFuncSetAttribute((const void*)k_chol_potrf2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kP2Lds); if (e != hipSuccess) return e;
   e = hipFuncSetAttribute((const void*)k_chol_update_lds<256, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCholLdsBig); if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute((const void*)k_chol_update_v, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCholLdsVCap); if (e != hipSuccess) return e;
   e = hipFuncSetAttribute((const void*)k_chol_backsub, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBsLds); if (e != hipSuccess) return e;
   e = hipFuncSetAttribute((const void*)k_chol_persist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPwLds); if (e != hipSuccess) return e;
   const int on = rt.sw.timing ? 1 : 0;

@@ -342,6 +342,7 @@ struct esl_ctx {
   bool sw_chol_overlap = true;   // the distributed factorisation's messages on their own stream under the trailing updates
   // ESL_CF_OVERLAP as read when the CONTEXT was created (A/B; a serial and an overlapped context can live in one process): the
   // side-stream orders of slam_try_step_cf (esl_slam.hip).  0: every launch of a camera-first trial in stream order; 1 (default):
-  // both side-stream orders; 2: the separators' chain beside the interior rows only; 3: the products' early start only
-  int sw_cf_overlap = 1;
+  // both side-stream orders; 2: the separators' chain beside the interior rows only; 3: the products' early start only; 4 (default):
+  // as 1, and the rank-K update capped to one workgroup per CU so that the products' waves are resident beside it (1: uncapped, A/B)
+  int sw_cf_overlap = 4;
 };

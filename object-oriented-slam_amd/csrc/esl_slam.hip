@@ -718,8 +718,12 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
     };
     if (assign) {
       {
+        // ESL_CF_OVERLAP=4 (default): the update CAPPED to one workgroup per CU (chol_launch_update's `cap`).  At its two workgroups
+        // per CU (252 registers a lane) every slot that frees goes to the next update workgroup and the products' waves (240) are
+        // placed only when the update has nothing left to dispatch; capped, one products workgroup is resident on every CU beside it.
+        // C4: the update stretches from 16.4 to 20.0 ms and the products end with it instead of 4.5 ms later
         ProfScope pk(c, 7);   // the rank-K update (assign form), with the products running beside it
-        chol_launch_update(rt.sw, c->cf_T, ldt, (long)n_o + 1, c->stream, 0, Ks_, 0, (long)n_o, c->cf_Xs, ldx, nullptr, c->cf_kfirst, true);
+        chol_launch_update(rt.sw, c->cf_T, ldt, (long)n_o + 1, c->stream, 0, Ks_, 0, (long)n_o, c->cf_Xs, ldx, nullptr, c->cf_kfirst, true, c->sw_cf_overlap == 4);
       }
       ESL_HIP_TRY(join.wait(rt.cf_ev_p));
       {
@@ -1400,5 +1404,13 @@ extern "C" int esl_debug_chol_plan(int32_t n, int32_t W, int32_t filler, int32_t
     if ((int64_t)pl.ns.size() > cap_ns) return ESL_ERR_INVALID;
     for (size_t i = 0; i < pl.ns.size(); ++i) ns_out[i] = pl.ns[i];
   }
+  return ESL_OK;
+}
+
+// test / debug: would chol_launch_update run this region on k_chol_update_v, the tile with the assign form and the occupancy cap
+// (esl_chol.hpp)?  A pure host function, the switches read per call
+extern "C" int esl_debug_update_v_applies(int64_t lda, int64_t rows, int64_t base, int64_t col_limit, int32_t ext, int64_t ldp, int32_t* applies_out) {
+  if (!applies_out) return ESL_ERR_INVALID;
+  *applies_out = esl::chol_update_v_applies(esl::chol_switches_from_env(), (long)lda, (long)rows, (long)base, (long)col_limit, ext != 0, (long)ldp) ? 1 : 0;
   return ESL_OK;
 }

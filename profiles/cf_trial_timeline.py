@@ -37,7 +37,8 @@ def overlap(a, c):
     return max(0.0, min(a[3], c[3]) - max(a[2], c[2]))
 
 
-for (pa, ga), (pc, gc) in ((("k_cf_chain", 64), ("k_cf_forward<2>", None)), (("k_cf_forward<1>", None), ("k_cf_seg_syrk", None))):
+for (pa, ga), (pc, gc) in ((("k_cf_chain", 64), ("k_cf_forward<2>", None)), (("k_cf_forward<1>", None), ("k_cf_seg_syrk", None)),
+                           (("k_chol_update_v", None), ("k_cf_seg_syrk", None)), (("k_chol_update_v", None), ("k_cf_T_gather", None))):
     for a in find(pa, ga):
         for c in find(pc, gc):
             print("%s [%.1f, %.1f] against %s [%.1f, %.1f]: %.1f us side by side" % (
