@@ -52,7 +52,7 @@ extern "C" {
                              *    (esl_reloc_set_map, esl_relocalize), and 2-D data association against the projected map
                              *    (esl_predict_boxes, esl_associate_boxes), and the SVD initialisation of many ellipsoids in one call
                              *    (esl_init_quadrics) and its outlier-rejecting form (esl_init_quadrics_robust), and map maintenance
-                             *    (esl_map_overlaps, esl_map_merge) */
+                             *    (esl_map_overlaps, esl_map_merge), and the per-pixel rendering of a map (esl_render_map) */
 #define ESL_MAX_TRACE 32
 
 typedef enum {
@@ -691,7 +691,8 @@ int esl_relocalize(esl_ctx* ctx, const double* det_objs /* D x 10, camera frame 
  *     min_box_px wide AND high.  z_m = the camera-frame z of the centre.
  *  2. Occlusion (occlusion != 0).  An eligible m is occluded iff ONE other eligible m' is nearer (z_m' < z_m, or z_m' == z_m and
  *     m' < m) and covers it: area(c_m n c_m') >= occl_ratio * area(c_m).  An occluder may itself be occluded; there is no union of
- *     occluders.  O(V^2) per frame over the V eligible predictions, exact.
+ *     occluders (esl_render_map below counts, per pixel, what any number of nearer objects hide).  O(V^2) per frame over the V eligible
+ *     predictions, exact.
  *  3. Assignment.  The detections of a frame are taken in index order.  The candidates of a detection are the eligible, non-occluded,
  *     unclaimed predictions, of equal label if match_labels.  It takes the candidate with the largest IoU(detection box as given, c_m),
  *     ties to the lowest m; if that IoU is >= min_iou and > 0 the pair is assigned and m is claimed for the rest of the frame,
@@ -804,11 +805,65 @@ int esl_map_merge(esl_ctx* ctx, const double* objs /* M x 10, NULL = resident el
                   double* merged_objs_out /* M x 10, the first n_groups rows are written */, int32_t* merged_labels_out /* M */,
                   int32_t* merged_weights_out /* M */, int32_t* obs_obj_out /* n_obs or NULL */, esl_merge_result* out);
 
+/* ---- rendering the map: per-pixel depth, instance and visibility (additive part of ABI 5: detect by the symbol) ---------------------------
+ * Every call above sees an ellipsoid in an image through its bounding box only.  esl_render_map casts the ray of every pixel of every
+ * frame against every ellipsoid of the map and keeps the nearest hit: which pixels show which object (the union of occluders that
+ * esl_associate_boxes leaves out), and, against a measured depth image, whether the sensor agrees with the map, stops short of it (an
+ * unmodelled occluder) or sees through it (a moved or removed object).  The reference only draws its map (FrameDrawer::
+ * drawProjectionOnImage, Pangolin).  Everything runs in FP64; every choice is a strict comparison or a total order and the only atomics
+ * are integer atomics, so runs are bit-reproducible.
+ *  1. Valid object, as step 1 of esl_map_merge: all ten numbers finite, the quaternion's norm finite and > 0 (it is normalised), the
+ *     half-axes s = (|a|, |b|, |c|) all > 0.  An invalid object hits no pixel (flag bit 1).
+ *  2. Camera-frame body.  With Rco = Rcw Rwo and tco = Rcw two + tcw as the bbox edge forms them: A = Rco diag(1 / s^2) Rco^T, g = A tco,
+ *     c0 = tco^T A tco - 1.  c0 <= 0: the camera centre is inside or on the body, which is not drawn in this frame (flag bit 2).
+ *  3. Ray of pixel (col, row): d = ((col - cx) / fx, (row - cy) / fy, 1), the integer-pixel convention with which esl_fit_frame and the
+ *     plane extraction back-project a depth sample.  alpha = d^T A d, beta = d^T g, Delta = beta^2 - alpha c0.  Hit iff beta > 0 and
+ *     Delta > 0, both strict (a grazing ray is no hit); z = c0 / (beta + sqrt(Delta)), the near root of z^2 alpha - 2 z beta + c0 = 0 in the
+ *     form without cancellation.
+ *  4. Pixel: the hit with the smallest z wins, ties to the lowest m.  depth_out = z, inst_out = m; NaN / -1 without a hit.
+ *  5. Counts per (frame, object): cover[0] = the pixels it hits, whatever else is there; cover[1] = the pixels it wins.  The caller's
+ *     visibility is cover[1] / cover[0].
+ *  6. Depth comparison over the pixels m wins, with r the raw sample and z_meas = r / depth_scale: r == 0 or z_meas outside
+ *     [depth_min, depth_max] -> no data; |z_meas - z| <= depth_tol -> agree; z_meas < z - depth_tol -> nearer (something unmodelled stands
+ *     in front); otherwise farther (the sensor sees through the object).  The four counts of an object sum to its cover[1].
+ * flags_out per (frame, object): bit 0 drawn (valid, camera outside, not wholly behind the principal plane), bit 1 invalid, bit 2 camera
+ * inside, bit 3 bounded by its conic box: the body lies wholly in front of the principal plane (the dual conic's C22 < 0, tco_z > 0, the
+ * outline's box finite), so the kernel tests it only on the pixels of that box widened by one.  A body wholly behind has no flag; one
+ * that meets the principal plane is tested on every pixel.  These bounds only cull: they never change a result. */
+typedef struct {
+  double depth_scale;  /* 5000: raw units per metre, intr[4] of esl_fit_frame */
+  double depth_min;    /* 0.1 */
+  double depth_max;    /* 6.0: a measured sample outside [depth_min, depth_max], or raw 0, is "no data" */
+  double depth_tol;    /* 0.05 m: |z_meas - z| <= depth_tol agrees */
+} esl_render_params;   /* 32 bytes; design choices, not tuned on real data */
+void esl_render_params_default(esl_render_params* p);
+
+/* ESL_ERR_INVALID: null ctx or K, negative F or M, rows or cols < 1 or > 16384, fx or fy not finite or <= 0, a non-finite or negative
+ * parameter, depth_scale <= 0, depth_min > depth_max, cmp_out without depth_meas, F or M differing from the resident graph when the NULL
+ * forms are used.  ESL_ERR_STATE: a NULL source without a resident graph and states.  F = 0, M = 0 and all outputs NULL are valid; with
+ * M = 0 the images are NaN / -1.  An output that is not asked for is neither computed into nor allocated; depth_meas without cmp_out is
+ * not read.  The call leaves the resident graph, its states and the solver blobs alone, keeps grow-only device buffers of its own (freed
+ * by esl_ctx_destroy; a warm call of the same shape allocates nothing; at most F (96 M + 14 rows cols) bytes), runs on this context's GPU
+ * only and issues no collective.  With esl_profile_enable(ctx, 2) its launches are bracketed as kernel class 4. */
+int esl_render_map(esl_ctx* ctx,
+                   const double* cams /* F x 7 Tcw, NULL = resident camera states (F must equal n_cams) */, int32_t F,
+                   const double* objs /* M x 10 world, NULL = resident ellipsoid states (M must equal n_objs) */, int32_t M,
+                   const double K[4], int32_t rows, int32_t cols,
+                   const uint16_t* depth_meas /* F x rows x cols or NULL */, const esl_render_params* p /* NULL = defaults */,
+                   double* depth_out /* F x rows x cols or NULL: z of the nearest hit, NaN where none */,
+                   int32_t* inst_out /* F x rows x cols or NULL: its map index, -1 where none */,
+                   int32_t* cover_out /* F x M x 2 or NULL: pixels the object hits alone; pixels where it is the nearest */,
+                   int32_t* cmp_out /* F x M x 4 or NULL, needs depth_meas: agree, nearer, farther, no data (over the pixels it wins) */,
+                   int32_t* flags_out /* F x M or NULL: bit 0 drawn, bit 1 invalid, bit 2 camera inside, bit 3 bounded by its conic box */);
+
 /* ---- diagnostics ---------------------------------------------------------------------------------*/
 /* Dense FP64-MFMA Cholesky factor + solve (the reduced-camera solver of SLAM mode) on a procedurally generated,
  * strictly diagonally dominant n x n system; returns the time of factor + solve (HIP events) and |A x - b| / |b|.
  * A known-answer test of the solver and the micro-benchmark behind the "mfma" roofline numbers. */
 int esl_selftest_cholesky(esl_ctx* ctx, int32_t n, double* ms_out, double* rel_residual_out);
+/* test / debug: how many device allocations esl_render_map has made on this context so far and how many bytes its grow-only buffers
+ * hold -- a warm call of a shape no larger than an earlier one changes neither.  Host code only. */
+int esl_debug_render_allocs(esl_ctx* ctx, int64_t* allocs_out, int64_t* bytes_out);
 /* test / debug: the static task list of the persistent dense factorisation for an order-n system (outer panels of W 128-panels,
  * `filler` far-update tasks between the chain-dependent groups): 4 int32 per task {type, a, b, c} -- 0: S(panel a, strip b),
  * 1: u(panel a, row tile b, column tile c), 2: U(outer panel a, row tile b, column tile c), 3: one 128 x 64 QUARTER of a rank-128 update

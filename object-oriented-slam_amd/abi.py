@@ -211,6 +211,32 @@ def default_merge_params(**kw):
     return p
 
 
+class EslRenderParams(C.Structure):
+    """esl_render_params: how esl_render_map reads a measured depth image."""
+    _fields_ = [("depth_scale", C.c_double), ("depth_min", C.c_double), ("depth_max", C.c_double), ("depth_tol", C.c_double)]
+
+
+def default_render_params(**kw):
+    """esl_render_params_default: design choices, not values tuned on real data (include/esl.h)."""
+    p = EslRenderParams(depth_scale=5000.0, depth_min=0.1, depth_max=6.0, depth_tol=0.05)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def render_argtypes(L):
+    """esl_render_map takes fifteen arguments, most of them nullable pointers: declared, so that None passes as NULL and a wrong type
+    raises instead of reaching the library"""
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    L.esl_render_params_default.argtypes = [C.POINTER(EslRenderParams)]
+    L.esl_render_params_default.restype = None
+    L.esl_render_map.argtypes = [C.c_void_p, dp, C.c_int32, dp, C.c_int32, dp, C.c_int32, C.c_int32, C.POINTER(C.c_uint16),
+                                 C.POINTER(EslRenderParams), dp, ip, ip, ip, ip]
+    L.esl_render_map.restype = C.c_int
+
+
 ROBUST_KINDS = {"none": 0, "huber": 1, "pseudo_huber": 2, "cauchy": 3, "tukey": 4}   # esl_robust_kind (include/esl.h)
 EDGE_CLASSES = {"bbox": 0, "e3d": 1, "grav": 2, "odom": 3}                         # esl_edge_class
 

@@ -135,6 +135,7 @@ void plane_release(esl_ctx* c);
 void reloc_release(esl_ctx* c);   // esl_reloc.hip
 void assoc_release(esl_ctx* c);   // esl_assoc.hip
 void merge_release(esl_ctx* c);   // esl_merge.hip
+void render_release(esl_ctx* c);  // esl_render.hip
 void init_batch_release(esl_ctx* c);   // esl_init.hip
 // all-gather the 8-double dev_scal block of every rank into c->dev_gather (device), ordered on the context's stream
 int comm_gather_scalars_device(esl_ctx* c);
@@ -235,6 +236,7 @@ struct esl_ctx {
   void* reloc = nullptr;                                    // esl_reloc_set_map / esl_relocalize: the map and the search's buffers (esl_reloc.hip RelocState)
   void* assoc = nullptr;                                    // esl_predict_boxes / esl_associate_boxes: their buffers (esl_assoc.hip AssocState)
   void* merge = nullptr;                                    // esl_map_overlaps / esl_map_merge: their buffers (esl_merge.hip MergeState)
+  void* render = nullptr;                                   // esl_render_map: its buffers (esl_render.hip RenderState)
   void* init_batch = nullptr;                               // esl_init_quadrics: its buffers (esl_init.hip InitBatchState)
   void* fit_graph_cache = nullptr;                         // captured launch sequences (std::vector<FitGraphEntry>)
   bool parts_fresh = false;      // host_part holds the last trial's scalars already (slam_try_step fetched them with the solver's flag)

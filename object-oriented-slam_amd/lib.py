@@ -28,6 +28,7 @@ EXPORTS = [
     "esl_assoc_params_default", "esl_predict_boxes", "esl_associate_boxes",
     "esl_init_robust_params_default", "esl_init_quadrics_robust",
     "esl_merge_params_default", "esl_map_overlaps", "esl_map_merge",
+    "esl_render_params_default", "esl_render_map", "esl_debug_render_allocs",
 ]
 
 
@@ -53,6 +54,7 @@ def load():
         for name in EXPORTS:
             if not hasattr(L, name):
                 raise EslError(f"libesl_hip.so does not export {name}")
+        abi.render_argtypes(L)
         _lib = L
     return _lib
 
@@ -662,6 +664,67 @@ class Context:
         G = res.n_groups
         return dict(result=res.as_dict(), group=group[:M], new_index=new[:M], objs=mo[:G], labels=ml[:G], weights=mw[:G],
                     obs_obj=out[:n_obs] if oo is not None else None)
+
+    def render_map(self, cams, objs, K, rows, cols, depth_meas=None, params=None, want=("depth", "inst", "cover", "flags")):
+        """esl_render_map: the ray cast of every pixel against every ellipsoid, nearest hit kept.  cams (F, 7) Tcw and objs (M, 10) world,
+        or None for the resident graph's current states; depth_meas (F, rows, cols) uint16 or None.  want names the outputs to compute;
+        "cmp" is added when a depth is given.  Returns a dict of numpy arrays: depth (F, rows, cols) NaN where nothing is hit, inst
+        (F, rows, cols) map index or -1, cover (F, M, 2) pixels hit / pixels won, cmp (F, M, 4) agree / nearer / farther / no data,
+        flags (F, M) bit 0 drawn, bit 1 invalid, bit 2 camera inside, bit 3 bounded by its conic box."""
+        p = params if params is not None else abi.default_render_params()
+        want = set(want)
+        if depth_meas is not None:
+            want.add("cmp")
+        unknown = want - {"depth", "inst", "cover", "cmp", "flags"}
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        _ip, _up = C.POINTER(C.c_int32), C.POINTER(C.c_uint16)
+        sizes = self.graph_sizes() if cams is None or objs is None else None
+        if cams is None:
+            F, cp = sizes["n_cams"], None
+        else:
+            cams = np.ascontiguousarray(cams, dtype=np.float64).reshape(-1, 7)
+            F, cp = len(cams), (cams.ctypes.data_as(_dp) if len(cams) else None)
+        if objs is None:
+            M, op = sizes["n_objs"], None
+        else:
+            objs = np.ascontiguousarray(objs, dtype=np.float64).reshape(-1, 10)
+            M, op = len(objs), (objs.ctypes.data_as(_dp) if len(objs) else None)
+        Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(4)
+        rows, cols = int(rows), int(cols)
+        mp = None
+        if depth_meas is not None:
+            depth_meas = np.ascontiguousarray(depth_meas, dtype=np.uint16)
+            if depth_meas.shape != (F, rows, cols):
+                raise ValueError(f"depth_meas has shape {depth_meas.shape}, expected {(F, rows, cols)}")
+            mp = depth_meas.ctypes.data_as(_up)          # an empty array has a valid address too
+        r, c = (rows, cols) if rows > 0 and cols > 0 else (0, 0)          # the library refuses such a shape before it writes
+        out = {}
+        if "depth" in want:
+            out["depth"] = np.full((F, r, c), np.nan)
+        if "inst" in want:
+            out["inst"] = np.full((F, r, c), -1, dtype=np.int32)
+        if "cover" in want:
+            out["cover"] = np.zeros((F, M, 2), dtype=np.int32)
+        if "cmp" in want:
+            out["cmp"] = np.zeros((F, M, 4), dtype=np.int32)
+        if "flags" in want:
+            out["flags"] = np.zeros((F, M), dtype=np.int32)
+
+        def optr(k, t):
+            return out[k].ctypes.data_as(t) if k in out else None
+        t0 = time.perf_counter()
+        rc = load().esl_render_map(self._h, cp, F, op, M, Kc.ctypes.data_as(_dp), rows, cols, mp, C.byref(p), optr("depth", _dp),
+                                   optr("inst", _ip), optr("cover", _ip), optr("cmp", _ip), optr("flags", _ip))
+        self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
+        _check(rc, "esl_render_map")
+        return out
+
+    def render_allocs(self):
+        """esl_debug_render_allocs: (device allocations render_map has made on this context, bytes its buffers hold)"""
+        n, b = C.c_int64(0), C.c_int64(0)
+        _check(load().esl_debug_render_allocs(self._h, C.byref(n), C.byref(b)), "esl_debug_render_allocs")
+        return n.value, b.value
 
     def selftest_cholesky(self, n):
         """(ms, relative residual) of the dense FP64-MFMA Cholesky factor + solve on a generated SPD system."""
