@@ -861,8 +861,19 @@ int esl_render_map(esl_ctx* ctx,
  * strictly diagonally dominant n x n system; returns the time of factor + solve (HIP events) and |A x - b| / |b|.
  * A known-answer test of the solver and the micro-benchmark behind the "mfma" roofline numbers. */
 int esl_selftest_cholesky(esl_ctx* ctx, int32_t n, double* ms_out, double* rel_residual_out);
-/* test / debug: how many device allocations esl_render_map has made on this context so far and how many bytes its grow-only buffers
- * hold -- a warm call of a shape no larger than an earlier one changes neither.  Host code only. */
+/* test / debug (additive part of ABI 5: detect by the symbol): how many device allocations the map-side calls of one owner have made
+ * on this context so far and how many bytes the owner's grow-only buffers hold -- a warm call of a shape no larger than an earlier
+ * one changes neither.  Zeros for an owner that has not run yet; ESL_ERR_INVALID for an unknown owner or a null pointer.  Host code only. */
+typedef enum {
+  ESL_SCRATCH_RELOC = 0,        /* esl_reloc_set_map, esl_relocalize */
+  ESL_SCRATCH_ASSOC = 1,        /* esl_predict_boxes, esl_associate_boxes */
+  ESL_SCRATCH_MERGE = 2,        /* esl_map_overlaps, esl_map_merge */
+  ESL_SCRATCH_RENDER = 3,       /* esl_render_map */
+  ESL_SCRATCH_INIT_BATCH = 4,   /* esl_init_quadrics (the robust call's refit included) */
+  ESL_SCRATCH_INIT_ROBUST = 5   /* esl_init_quadrics_robust's own buffers */
+} esl_scratch_owner;
+int esl_debug_scratch_allocs(esl_ctx* ctx, int32_t owner, int64_t* allocs_out, int64_t* bytes_out);
+/* = esl_debug_scratch_allocs(ctx, ESL_SCRATCH_RENDER, ...) */
 int esl_debug_render_allocs(esl_ctx* ctx, int64_t* allocs_out, int64_t* bytes_out);
 /* test / debug: the static task list of the persistent dense factorisation for an order-n system (outer panels of W 128-panels,
  * `filler` far-update tasks between the chain-dependent groups): 4 int32 per task {type, a, b, c} -- 0: S(panel a, strip b),

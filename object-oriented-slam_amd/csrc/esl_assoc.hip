@@ -48,12 +48,9 @@ struct AssocArgs {
   int* spill_list; int* spill_count;              // the frames left to k_assoc_spilled (all null when M <= kAssocTile)
 };
 
-struct AssocState {
-  static constexpr int kBufs = 14;
-  void* buf[kBufs] = {};
-  size_t cap[kBufs] = {};
-};
-enum { AB_CAMS, AB_OBJS, AB_OLAB, AB_OFF, AB_DBOX, AB_DLAB, AB_ASSOC, AB_IOU, AB_STATS, AB_PBOX, AB_PDEPTH, AB_PFLAGS, AB_SCRATCH, AB_SPILL };
+enum { AB_CAMS, AB_OBJS, AB_OLAB, AB_OFF, AB_DBOX, AB_DLAB, AB_ASSOC, AB_IOU, AB_STATS, AB_PBOX, AB_PDEPTH, AB_PFLAGS, AB_SCRATCH, AB_SPILL,
+       AB_COUNT };
+struct AssocState { ScratchSet<AB_COUNT> set; };
 
 static __device__ __forceinline__ AssocTile assoc_tile_at(char* base, size_t cap) {
   AssocTile t;
@@ -225,11 +222,13 @@ static __global__ __launch_bounds__(kAssocThreads) void k_assoc_spilled(AssocArg
   }
 }
 
+void assoc_scratch_stats(const esl_ctx* c, int64_t* allocs, int64_t* bytes) {
+  if (c->assoc) { *allocs = c->assoc->set.allocs(); *bytes = (int64_t)c->assoc->set.held(); }
+}
+
 void assoc_release(esl_ctx* c) {   // called by esl_ctx_destroy
-  AssocState* s = (AssocState*)c->assoc;
-  if (!s) return;
-  for (void* p : s->buf) if (p) (void)hipFree(p);
-  delete s;
+  if (c->assoc) c->assoc->set.release();
+  delete c->assoc;
   c->assoc = nullptr;
 }
 
@@ -238,16 +237,6 @@ void assoc_release(esl_ctx* c) {   // called by esl_ctx_destroy
 using namespace esl;
 
 namespace {
-
-int assoc_grow(esl_ctx* c, AssocState* s, int k, size_t bytes) {   // grow-only; contents are not kept
-  if (bytes <= s->cap[k] && s->buf[k]) return ESL_OK;
-  ESL_HIP_TRY(hipStreamSynchronize(c->stream));
-  if (s->buf[k]) (void)hipFree(s->buf[k]);
-  s->buf[k] = nullptr; s->cap[k] = 0;
-  ESL_HIP_TRY(hipMalloc(&s->buf[k], std::max<size_t>(bytes, 16)));
-  s->cap[k] = bytes;
-  return ESL_OK;
-}
 
 struct AssocCall {
   const double* cams; int F;             // host, or null = resident
@@ -267,65 +256,48 @@ int assoc_check(esl_ctx* c, const AssocCall& a, const char* who, esl_assoc_param
   if (a.p) p = *a.p; else esl_assoc_params_default(&p);
   for (double v : {p.min_iou, p.occl_ratio, p.min_box_px})
     if (!std::isfinite(v) || v < 0) { set_error(w + ": non-finite or negative min_iou / occl_ratio / min_box_px"); return ESL_ERR_INVALID; }
-  const bool res_cams = !a.cams && a.F > 0, res_objs = !a.objs && a.M > 0;
-  if (res_cams || res_objs) {
-    if (!c->graph_loaded || !c->states_loaded) { set_error(w + ": a NULL source needs a resident graph with states"); return ESL_ERR_STATE; }
-    if (res_cams && a.F != c->g.n_cams) { set_error(w + ": F differs from the resident graph's n_cams"); return ESL_ERR_INVALID; }
-    if (res_objs && a.M != c->g.n_objs) { set_error(w + ": M differs from the resident graph's n_objs"); return ESL_ERR_INVALID; }
-  }
-  return ESL_OK;
+  return resident_source_check(c, who, !a.cams && a.F > 0, a.F, !a.objs && a.M > 0, a.M);
 }
 
 int assoc_run(esl_ctx* c, const AssocCall& a, const esl_assoc_params& p) {
   ESL_HIP_TRY(hipSetDevice(c->device));
   if (!c->assoc) c->assoc = new AssocState();
-  AssocState* s = (AssocState*)c->assoc;
+  ScratchSet<AB_COUNT>& s = c->assoc->set;
   const int F = a.F, M = a.M;
   const size_t n_det = a.det_off ? (size_t)a.det_off[F] : 0;
   const bool predict = a.boxes_out != nullptr;
   AssocArgs k;
   std::memset(&k, 0, sizeof(k));
-  if (a.cams) {
-    if (const int rc = assoc_grow(c, s, AB_CAMS, (size_t)F * 7 * sizeof(double))) return rc;
-    ESL_HIP_TRY(hipMemcpyAsync(s->buf[AB_CAMS], a.cams, (size_t)F * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    k.cams = (const double*)s->buf[AB_CAMS];
-  } else k.cams = c->cams;
-  if (a.objs) {
-    if (const int rc = assoc_grow(c, s, AB_OBJS, (size_t)M * 10 * sizeof(double))) return rc;
-    ESL_HIP_TRY(hipMemcpyAsync(s->buf[AB_OBJS], a.objs, (size_t)M * 10 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    k.objs = (const double*)s->buf[AB_OBJS];
-  } else k.objs = c->objs;
-  if (a.obj_labels) {
-    if (const int rc = assoc_grow(c, s, AB_OLAB, (size_t)M * sizeof(int32_t))) return rc;
-    ESL_HIP_TRY(hipMemcpyAsync(s->buf[AB_OLAB], a.obj_labels, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    k.obj_lab = (const int*)s->buf[AB_OLAB];
-  }
+  if (const int rc = source(c, s, AB_CAMS, a.cams, c->cams, (size_t)F * 7 * sizeof(double), &k.cams)) return rc;
+  if (const int rc = source(c, s, AB_OBJS, a.objs, c->objs, (size_t)M * 10 * sizeof(double), &k.objs)) return rc;
+  if (a.obj_labels)
+    if (const int rc = upload(c, s, AB_OLAB, a.obj_labels, (size_t)M * sizeof(int32_t), &k.obj_lab)) return rc;
   // offsets (zeros when there are no detections at all), boxes, labels
-  if (const int rc = assoc_grow(c, s, AB_OFF, (size_t)(F + 1) * sizeof(int32_t))) return rc;
-  if (a.det_off) ESL_HIP_TRY(hipMemcpyAsync(s->buf[AB_OFF], a.det_off, (size_t)(F + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  else ESL_HIP_TRY(hipMemsetAsync(s->buf[AB_OFF], 0, (size_t)(F + 1) * sizeof(int32_t), c->stream));
-  k.det_off = (const int*)s->buf[AB_OFF];
-  if (const int rc = assoc_grow(c, s, AB_DBOX, n_det * 4 * sizeof(double))) return rc;
-  if (const int rc = assoc_grow(c, s, AB_DLAB, n_det * sizeof(int32_t))) return rc;
-  if (const int rc = assoc_grow(c, s, AB_ASSOC, n_det * sizeof(int32_t))) return rc;
+  if (const int rc = s.grow(c, AB_OFF, (size_t)(F + 1) * sizeof(int32_t))) return rc;
+  if (a.det_off) ESL_HIP_TRY(hipMemcpyAsync(s.buf[AB_OFF], a.det_off, (size_t)(F + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  else ESL_HIP_TRY(hipMemsetAsync(s.buf[AB_OFF], 0, (size_t)(F + 1) * sizeof(int32_t), c->stream));
+  k.det_off = s.at<int>(AB_OFF);
+  if (const int rc = s.grow(c, AB_DBOX, n_det * 4 * sizeof(double))) return rc;
+  if (const int rc = s.grow(c, AB_DLAB, n_det * sizeof(int32_t))) return rc;
+  if (const int rc = s.grow(c, AB_ASSOC, n_det * sizeof(int32_t))) return rc;
   if (n_det) {
-    ESL_HIP_TRY(hipMemcpyAsync(s->buf[AB_DBOX], a.det_boxes, n_det * 4 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    ESL_HIP_TRY(hipMemcpyAsync(s->buf[AB_DLAB], a.det_labels, n_det * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(s.buf[AB_DBOX], a.det_boxes, n_det * 4 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(s.buf[AB_DLAB], a.det_labels, n_det * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
   }
-  k.det_box = (const double*)s->buf[AB_DBOX]; k.det_lab = (const int*)s->buf[AB_DLAB]; k.assoc = (int*)s->buf[AB_ASSOC];
+  k.det_box = s.at<double>(AB_DBOX); k.det_lab = s.at<int>(AB_DLAB); k.assoc = s.at<int>(AB_ASSOC);
   if (a.iou_out) {
-    if (const int rc = assoc_grow(c, s, AB_IOU, n_det * sizeof(double))) return rc;
-    k.iou = (double*)s->buf[AB_IOU];
+    if (const int rc = s.grow(c, AB_IOU, n_det * sizeof(double))) return rc;
+    k.iou = s.at<double>(AB_IOU);
   }
   if (a.stats_out) {
-    if (const int rc = assoc_grow(c, s, AB_STATS, (size_t)F * 4 * sizeof(int32_t))) return rc;
-    k.stats = (int*)s->buf[AB_STATS];
+    if (const int rc = s.grow(c, AB_STATS, (size_t)F * 4 * sizeof(int32_t))) return rc;
+    k.stats = s.at<int>(AB_STATS);
   }
   if (predict) {
-    if (const int rc = assoc_grow(c, s, AB_PBOX, (size_t)M * 4 * sizeof(double))) return rc;
-    if (const int rc = assoc_grow(c, s, AB_PDEPTH, (size_t)M * sizeof(double))) return rc;
-    if (const int rc = assoc_grow(c, s, AB_PFLAGS, (size_t)M * sizeof(int32_t))) return rc;
-    k.p_box = (double*)s->buf[AB_PBOX]; k.p_depth = (double*)s->buf[AB_PDEPTH]; k.p_flags = (int*)s->buf[AB_PFLAGS];
+    if (const int rc = s.grow(c, AB_PBOX, (size_t)M * 4 * sizeof(double))) return rc;
+    if (const int rc = s.grow(c, AB_PDEPTH, (size_t)M * sizeof(double))) return rc;
+    if (const int rc = s.grow(c, AB_PFLAGS, (size_t)M * sizeof(int32_t))) return rc;
+    k.p_box = s.at<double>(AB_PBOX); k.p_depth = s.at<double>(AB_PDEPTH); k.p_flags = s.at<int>(AB_PFLAGS);
   }
   // frames that overflow the tile (possible only when M > kAssocTile) go on a list; as many of them at a time as the scratch bound
   // admits slices run in a second launch (at least one)
@@ -333,10 +305,10 @@ int assoc_run(esl_ctx* c, const AssocCall& a, const esl_assoc_params& p) {
   if (M > kAssocTile) {
     k.slice = ((size_t)M * kAssocEntryBytes + 15) / 16 * 16;
     n_slices = (int)std::max<size_t>(1, std::min<size_t>((size_t)F, kAssocScratchBytes / k.slice));
-    if (const int rc = assoc_grow(c, s, AB_SCRATCH, k.slice * (size_t)n_slices)) return rc;
-    if (const int rc = assoc_grow(c, s, AB_SPILL, (size_t)(F + 1) * sizeof(int))) return rc;
-    k.scratch = (char*)s->buf[AB_SCRATCH];
-    k.spill_count = (int*)s->buf[AB_SPILL]; k.spill_list = k.spill_count + 1;
+    if (const int rc = s.grow(c, AB_SCRATCH, k.slice * (size_t)n_slices)) return rc;
+    if (const int rc = s.grow(c, AB_SPILL, (size_t)(F + 1) * sizeof(int))) return rc;
+    k.scratch = s.at<char>(AB_SCRATCH);
+    k.spill_count = s.at<int>(AB_SPILL); k.spill_list = k.spill_count + 1;
     ESL_HIP_TRY(hipMemsetAsync(k.spill_count, 0, sizeof(int), c->stream));
   }
   k.M = M; k.rows = a.rows; k.cols = a.cols;

@@ -173,9 +173,9 @@ int esl_ctx_destroy(esl_ctx* c) {
   if (c->stage_host) (void)hipHostFree(c->stage_host);
   if (c->append_dev) (void)hipFree(c->append_dev);
   if (c->slam_tab_dev) (void)hipFree(c->slam_tab_dev);
-  if (c->eq_buf) (void)hipFree(c->eq_buf);
+  c->eq_buf.release();
   if (c->fx_blob) (void)hipFree(c->fx_blob);
-  if (c->chain_ws) (void)hipFree(c->chain_ws);
+  c->chain_ws.release();
   fit_release(c);
   plane_release(c);
   reloc_release(c);
@@ -207,6 +207,22 @@ int esl_ctx_trim(esl_ctx* c) {
   ESL_HIP_TRY(hipSetDevice(c->device));
   ESL_HIP_TRY(hipStreamSynchronize(c->stream));
   slam_trim(c, c->graph_loaded && c->g.n_free_cams > 0);
+  return ESL_OK;
+}
+
+int esl_debug_scratch_allocs(esl_ctx* c, int32_t owner, int64_t* allocs_out, int64_t* bytes_out) {
+  if (!c || !allocs_out || !bytes_out || owner < ESL_SCRATCH_RELOC || owner > ESL_SCRATCH_INIT_ROBUST) {
+    set_error("esl_debug_scratch_allocs: null pointer or unknown owner");
+    return ESL_ERR_INVALID;
+  }
+  *allocs_out = 0; *bytes_out = 0;
+  switch (owner) {
+    case ESL_SCRATCH_RELOC: reloc_scratch_stats(c, allocs_out, bytes_out); break;
+    case ESL_SCRATCH_ASSOC: assoc_scratch_stats(c, allocs_out, bytes_out); break;
+    case ESL_SCRATCH_MERGE: merge_scratch_stats(c, allocs_out, bytes_out); break;
+    case ESL_SCRATCH_RENDER: render_scratch_stats(c, allocs_out, bytes_out); break;
+    default: init_scratch_stats(c, owner == ESL_SCRATCH_INIT_ROBUST, allocs_out, bytes_out);
+  }
   return ESL_OK;
 }
 
@@ -865,13 +881,9 @@ static int edge_chi2_plain(esl_ctx* c, int32_t edge_class, double* chi2, double*
   const int n_slots = edge_class == ESL_EDGE_BBOX ? g.n_bbox : edge_class == ESL_EDGE_E3D ? g.n_e3d : edge_class == ESL_EDGE_GRAVITY ? g.n_objs : g.n_odom;
   ESL_HIP_TRY(hipSetDevice(c->device));
   const size_t need = (size_t)n_slots * 2;
-  if (need > c->eq_cap) {   // grow-only: a query per frame allocates nothing once the graph has stopped growing
-    if (c->eq_buf) ESL_HIP_TRY(hipFree(c->eq_buf));
-    c->eq_buf = nullptr; c->eq_cap = 0;
-    ESL_HIP_TRY(hipMalloc((void**)&c->eq_buf, need * sizeof(double)));
-    c->eq_cap = need;
-  }
-  double* d = c->eq_buf;
+  // grow-only: a query per frame allocates nothing once the graph has stopped growing
+  if (const int rc = c->eq_buf.grow(c, 0, need * sizeof(double))) return rc;
+  double* d = c->eq_buf.at<double>(0);
   std::vector<double> h(need);
   hipLaunchKernelGGL(k_edge_chi2, dim3((n_slots + 255) / 256), dim3(256), 0, c->stream, g, (int)edge_class, c->cams, c->objs, d, d + n_slots);
   hipError_t e = hipGetLastError();

@@ -108,6 +108,8 @@ inline void robust_dispatch(bool on, F&& f) {
 }
 
 struct HostImage;   // esl_graph.hip
+// the map-side calls' buffers, each defined by the translation unit named after it (InitBatchState: esl_init.hip)
+struct RelocState; struct AssocState; struct MergeState; struct RenderState; struct InitBatchState;
 struct LmState {
   bool begun = false;
   esl_lm_params p;
@@ -117,6 +119,8 @@ struct LmState {
 };
 
 }  // namespace esl
+
+#include "esl_scratch.hpp"   // ScratchSet: after set_error / ESL_HIP_TRY, ahead of esl_ctx
 
 // device blob + its pinned staging twin + the event of the last staging -> device copy
 struct BlobArena { char* dev = nullptr; size_t cap = 0; char* host = nullptr; size_t host_cap = 0; hipEvent_t ev = nullptr; };
@@ -137,6 +141,12 @@ void assoc_release(esl_ctx* c);   // esl_assoc.hip
 void merge_release(esl_ctx* c);   // esl_merge.hip
 void render_release(esl_ctx* c);  // esl_render.hip
 void init_batch_release(esl_ctx* c);   // esl_init.hip
+// esl_debug_scratch_allocs: each owner's counters, written only when its state exists
+void reloc_scratch_stats(const esl_ctx* c, int64_t* allocs, int64_t* bytes);
+void assoc_scratch_stats(const esl_ctx* c, int64_t* allocs, int64_t* bytes);
+void merge_scratch_stats(const esl_ctx* c, int64_t* allocs, int64_t* bytes);
+void render_scratch_stats(const esl_ctx* c, int64_t* allocs, int64_t* bytes);
+void init_scratch_stats(const esl_ctx* c, bool robust, int64_t* allocs, int64_t* bytes);
 // all-gather the 8-double dev_scal block of every rank into c->dev_gather (device), ordered on the context's stream
 int comm_gather_scalars_device(esl_ctx* c);
 // SLAM mode: in-place sum over ranks of a device buffer (RCCL all-reduce); no-op without a communicator
@@ -180,14 +190,14 @@ struct esl_ctx {
   double* od_part = nullptr;  // n_odom : chi2 per odometry edge
   int* chol_info = nullptr;
   // reductions
-  double* host_part = nullptr;  // pinned: 8 doubles
+  double* host_part = nullptr;  // pinned: 16 doubles
   double* dev_part = nullptr;
   esl::LmState lm;
   esl_robust_params robust = {{0, 0, 0, 0}, {1, 1, 1, 1}};   // esl_lm_set_robust; copied into g at the start of every run
   bool robust_on = false;                                     // the current run has a kernel on some class: ROBUST instantiations
   // caller order -> slot of the ellipsoid-sorted edge arrays (esl_edge_chi2), kept across esl_graph_append; gravity: caller's ellipsoids
   std::vector<int> h_bb_slot_of, h_e3_slot_of, h_grav_obj;
-  double* eq_buf = nullptr; size_t eq_cap = 0;   // grow-only device buffer of esl_edge_chi2 (2 doubles per slot)
+  esl::Scratch eq_buf;   // esl_edge_chi2: 2 doubles per slot
   double* cams_snap = nullptr; double* objs_snap = nullptr;
   // profiling (HIP events on this stream)
   bool prof_on = false;
@@ -232,12 +242,12 @@ struct esl_ctx {
   char* fit_slab = nullptr; size_t fit_slab_cap = 0;        // esl_fit_frame's device slab (esl_fit.hip)
   char* fit_in = nullptr;  size_t fit_in_cap = 0;           // pinned staging of its inputs / outputs
   char* fit_out = nullptr; size_t fit_out_cap = 0;
-  char* plane_slab = nullptr; size_t plane_slab_cap = 0;    // esl_extract_ground_plane / esl_extract_planes (esl_plane.hip)
-  void* reloc = nullptr;                                    // esl_reloc_set_map / esl_relocalize: the map and the search's buffers (esl_reloc.hip RelocState)
-  void* assoc = nullptr;                                    // esl_predict_boxes / esl_associate_boxes: their buffers (esl_assoc.hip AssocState)
-  void* merge = nullptr;                                    // esl_map_overlaps / esl_map_merge: their buffers (esl_merge.hip MergeState)
-  void* render = nullptr;                                   // esl_render_map: its buffers (esl_render.hip RenderState)
-  void* init_batch = nullptr;                               // esl_init_quadrics: its buffers (esl_init.hip InitBatchState)
+  esl::Scratch plane_slab;                                   // esl_extract_ground_plane / esl_extract_planes (esl_plane.hip)
+  esl::RelocState* reloc = nullptr;                               // esl_reloc_set_map / esl_relocalize: the map and the search's buffers (esl_reloc.hip RelocState)
+  esl::AssocState* assoc = nullptr;                               // esl_predict_boxes / esl_associate_boxes: their buffers (esl_assoc.hip AssocState)
+  esl::MergeState* merge = nullptr;                               // esl_map_overlaps / esl_map_merge: their buffers (esl_merge.hip MergeState)
+  esl::RenderState* render = nullptr;                             // esl_render_map: its buffers (esl_render.hip RenderState)
+  esl::InitBatchState* init_batch = nullptr;                     // esl_init_quadrics: its buffers (esl_init.hip InitBatchState)
   void* fit_graph_cache = nullptr;                         // captured launch sequences (std::vector<FitGraphEntry>)
   bool parts_fresh = false;      // host_part holds the last trial's scalars already (slam_try_step fetched them with the solver's flag)
   bool cams_match_snap = false;  // cameras untouched since the snapshot: esl_states_restore skips their copy
@@ -317,7 +327,7 @@ struct esl_ctx {
   std::vector<int> fx_bb_map, fx_e3_map;
   std::vector<int> fx_grav_obj;             // the caller's gravity edges (all of them; h_grav_obj holds those of free ellipsoids)
   bool chain_ok = false;                    // the odometry edges between free cameras join neighbours only (slam_alloc)
-  double* chain_ws = nullptr; size_t chain_ws_cap = 0;   // ESL_SOLVER_CAMERA_CHAIN: D, L, rhs (two sets) + the blocks' inverses; grow-only
+  esl::Scratch chain_ws;                    // ESL_SOLVER_CAMERA_CHAIN: D, L, rhs (two sets) + the blocks' inverses
   // ESL_SOLVER_PCG (esl_pcg.hpp).  pcg: esl_lm_set_pcg, read when a run starts (pcg_run); pcg_ws: state block, M, M^-1, b_s, r, z, p (two),
   // q, D^-1 b_o, the edges' products, the partials -- O(edges + cameras), grow-only, freed by slam_release; pcg_M: the diagonal blocks of S
   // of the last PCG trial (interior pointer, null when the last trial ran another solver); pcg_host: pinned, the done flag's landing place

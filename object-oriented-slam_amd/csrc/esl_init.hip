@@ -779,8 +779,7 @@ static __global__ __launch_bounds__(64) void k_init_robust(InitRobustArgs a, int
 
 struct InitRobustState {   // InitBatchState::rob
   enum { R_CAMS, R_OCAM, R_BOX, R_IDX, R_OBJS, R_HYP, R_OI, R_OD, R_RES, R_INL, R_RFELL, R_RFOK, kBufs };
-  void* buf[kBufs] = {};
-  size_t cap[kBufs] = {};
+  ScratchSet<kBufs> set;
   // the host's grouping, what comes back from the passes and the refit's list and results, kept for their capacity
   std::vector<int32_t> offsets, idx, masked, oi, inl, rf_ok, rf_stats;
   std::vector<InitObj> objs;
@@ -789,23 +788,26 @@ struct InitRobustState {   // InitBatchState::rob
 
 struct InitBatchState {   // esl_ctx::init_batch
   enum { B_CAMS, B_OCAM, B_BOX, B_IDX, B_ORDER, B_SLAB, B_ELL, B_QS, B_PERR, B_STATS, kBufs };
-  void* buf[kBufs] = {};
-  size_t cap[kBufs] = {};
+  ScratchSet<kBufs> set;
   std::vector<int32_t> offsets, idx;   // the host's grouping, kept for their capacity
   std::vector<InitObj> order;
   InitRobustState* rob = nullptr;      // esl_init_quadrics_robust's own buffers
 };
 
 void init_batch_release(esl_ctx* c) {   // called by esl_ctx_destroy
-  InitBatchState* s = (InitBatchState*)c->init_batch;
+  InitBatchState* s = c->init_batch;
   if (!s) return;
-  for (void* p : s->buf) if (p) (void)hipFree(p);
-  if (s->rob) {
-    for (void* p : s->rob->buf) if (p) (void)hipFree(p);
-    delete s->rob;
-  }
+  s->set.release();
+  if (s->rob) s->rob->set.release();
+  delete s->rob;
   delete s;
   c->init_batch = nullptr;
+}
+
+void init_scratch_stats(const esl_ctx* c, bool robust, int64_t* allocs, int64_t* bytes) {
+  const InitBatchState* s = c->init_batch;
+  if (s && !robust) { *allocs = s->set.allocs(); *bytes = (int64_t)s->set.held(); }
+  if (s && robust && s->rob) { *allocs = s->rob->set.allocs(); *bytes = (int64_t)s->rob->set.held(); }
 }
 
 }  // namespace esl
@@ -894,16 +896,6 @@ extern "C" int esl_init_plane_error(esl_ctx* c, const double* poses_Twc, const d
 
 namespace {
 
-int init_batch_grow(esl_ctx* c, InitBatchState* s, int k, size_t bytes) {   // grow-only; contents are not kept
-  if (bytes <= s->cap[k] && s->buf[k]) return ESL_OK;
-  ESL_HIP_TRY(hipStreamSynchronize(c->stream));
-  if (s->buf[k]) (void)hipFree(s->buf[k]);
-  s->buf[k] = nullptr; s->cap[k] = 0;
-  ESL_HIP_TRY(hipMalloc(&s->buf[k], std::max<size_t>(bytes, 16)));
-  s->cap[k] = bytes;
-  return ESL_OK;
-}
-
 int init_batch_fail(const char* what, int rc) { set_error(std::string("esl_init_quadrics: ") + what); return rc; }
 
 }  // namespace
@@ -922,7 +914,9 @@ extern "C" int esl_init_quadrics(esl_ctx* c, const double* cams, int32_t F, int3
     if (F != c->g.n_cams) return init_batch_fail("F differs from the resident graph's n_cams", ESL_ERR_INVALID);
   }
   if (!c->init_batch) c->init_batch = new InitBatchState();
-  InitBatchState* s = (InitBatchState*)c->init_batch;
+  InitBatchState* s = c->init_batch;
+  typedef InitBatchState B;
+  ScratchSet<B::kBufs>& d = s->set;
   int64_t bad = 0;
   const int grc = init_group(n_obs, N, F, obs_cam, obs_obj, s->offsets, s->idx, &bad);
   if (grc == INIT_GROUP_BAD_OBJ) return init_batch_fail(("obs_obj >= N at entry " + std::to_string(bad)).c_str(), ESL_ERR_INVALID);
@@ -939,37 +933,32 @@ extern "C" int esl_init_quadrics(esl_ctx* c, const double* cams, int32_t F, int3
   ESL_HIP_TRY(hipSetDevice(c->device));
   InitBatchArgs k{};
   const size_t kept = s->idx.size();
-  if (cams) {
-    if (const int rc = init_batch_grow(c, s, InitBatchState::B_CAMS, (size_t)F * 7 * sizeof(double))) return rc;
-    if (F) ESL_HIP_TRY(hipMemcpyAsync(s->buf[InitBatchState::B_CAMS], cams, (size_t)F * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    k.cams = (const double*)s->buf[InitBatchState::B_CAMS];
-  } else k.cams = c->cams;
-  if (const int rc = init_batch_grow(c, s, InitBatchState::B_OCAM, (size_t)n_obs * sizeof(int32_t))) return rc;
-  if (const int rc = init_batch_grow(c, s, InitBatchState::B_BOX, (size_t)n_obs * 4 * sizeof(double))) return rc;
-  if (const int rc = init_batch_grow(c, s, InitBatchState::B_IDX, kept * sizeof(int32_t))) return rc;
-  if (const int rc = init_batch_grow(c, s, InitBatchState::B_ORDER, (size_t)N * sizeof(InitObj))) return rc;
-  if (const int rc = init_batch_grow(c, s, InitBatchState::B_SLAB, (size_t)slab * 40 * sizeof(double))) return rc;
-  if (const int rc = init_batch_grow(c, s, InitBatchState::B_ELL, (size_t)N * 10 * sizeof(double))) return rc;
+  if (const int rc = source(c, d, B::B_CAMS, cams, c->cams, (size_t)F * 7 * sizeof(double), &k.cams)) return rc;
+  if (const int rc = d.grow(c, B::B_OCAM, (size_t)n_obs * sizeof(int32_t))) return rc;
+  if (const int rc = d.grow(c, B::B_BOX, (size_t)n_obs * 4 * sizeof(double))) return rc;
+  if (const int rc = d.grow(c, B::B_IDX, kept * sizeof(int32_t))) return rc;
+  if (const int rc = d.grow(c, B::B_SLAB, (size_t)slab * 40 * sizeof(double))) return rc;
+  if (const int rc = d.grow(c, B::B_ELL, (size_t)N * 10 * sizeof(double))) return rc;
   if (kept) {   // entries that no object keeps are never read
-    ESL_HIP_TRY(hipMemcpyAsync(s->buf[InitBatchState::B_OCAM], obs_cam, (size_t)n_obs * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    ESL_HIP_TRY(hipMemcpyAsync(s->buf[InitBatchState::B_BOX], obs_boxes, (size_t)n_obs * 4 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    ESL_HIP_TRY(hipMemcpyAsync(s->buf[InitBatchState::B_IDX], s->idx.data(), kept * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(d.buf[B::B_OCAM], obs_cam, (size_t)n_obs * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(d.buf[B::B_BOX], obs_boxes, (size_t)n_obs * 4 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(d.buf[B::B_IDX], s->idx.data(), kept * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
   }
-  ESL_HIP_TRY(hipMemcpyAsync(s->buf[InitBatchState::B_ORDER], s->order.data(), (size_t)N * sizeof(InitObj), hipMemcpyHostToDevice, c->stream));
-  k.obs_cam = (const int*)s->buf[InitBatchState::B_OCAM]; k.obs_box = (const double*)s->buf[InitBatchState::B_BOX];
-  k.idx = (const int*)s->buf[InitBatchState::B_IDX]; k.order = (const InitObj*)s->buf[InitBatchState::B_ORDER];
-  k.slab = (double*)s->buf[InitBatchState::B_SLAB]; k.ell = (double*)s->buf[InitBatchState::B_ELL];
+  if (const int rc = upload(c, d, B::B_ORDER, (const InitObj*)s->order.data(), (size_t)N * sizeof(InitObj), &k.order)) return rc;
+  k.obs_cam = d.at<const int>(B::B_OCAM); k.obs_box = d.at<const double>(B::B_BOX);
+  k.idx = d.at<const int>(B::B_IDX);
+  k.slab = d.at<double>(B::B_SLAB); k.ell = d.at<double>(B::B_ELL);
   if (qstar_out) {
-    if (const int rc = init_batch_grow(c, s, InitBatchState::B_QS, (size_t)N * 16 * sizeof(double))) return rc;
-    k.qstar = (double*)s->buf[InitBatchState::B_QS];
+    if (const int rc = d.grow(c, B::B_QS, (size_t)N * 16 * sizeof(double))) return rc;
+    k.qstar = d.at<double>(B::B_QS);
   }
   if (plane_error_out) {
-    if (const int rc = init_batch_grow(c, s, InitBatchState::B_PERR, (size_t)N * sizeof(double))) return rc;
-    k.perr = (double*)s->buf[InitBatchState::B_PERR];
+    if (const int rc = d.grow(c, B::B_PERR, (size_t)N * sizeof(double))) return rc;
+    k.perr = d.at<double>(B::B_PERR);
   }
   if (stats_out) {
-    if (const int rc = init_batch_grow(c, s, InitBatchState::B_STATS, (size_t)N * 4 * sizeof(int32_t))) return rc;
-    k.stats = (int*)s->buf[InitBatchState::B_STATS];
+    if (const int rc = d.grow(c, B::B_STATS, (size_t)N * 4 * sizeof(int32_t))) return rc;
+    k.stats = d.at<int>(B::B_STATS);
   }
   for (int i = 0; i < 4; ++i) k.K[i] = K[i];
   k.rows = rows; k.cols = cols; k.faithful = faithful; k.min_obs = min_observations;
@@ -991,16 +980,6 @@ extern "C" int esl_init_quadrics(esl_ctx* c, const double* cams, int32_t F, int3
 
 // ---- esl_init_quadrics_robust ---------------------------------------------------------------------------------------------------
 namespace {
-
-int rob_grow(esl_ctx* c, InitRobustState* s, int k, size_t bytes) {   // grow-only; contents are not kept
-  if (bytes <= s->cap[k] && s->buf[k]) return ESL_OK;
-  ESL_HIP_TRY(hipStreamSynchronize(c->stream));
-  if (s->buf[k]) (void)hipFree(s->buf[k]);
-  s->buf[k] = nullptr; s->cap[k] = 0;
-  ESL_HIP_TRY(hipMalloc(&s->buf[k], std::max<size_t>(bytes, 16)));
-  s->cap[k] = bytes;
-  return ESL_OK;
-}
 
 int rob_fail(const char* what, int rc) { set_error(std::string("esl_init_quadrics_robust: ") + what); return rc; }
 
@@ -1034,7 +1013,7 @@ extern "C" int esl_init_quadrics_robust(esl_ctx* c, const double* cams, int32_t 
     if (F != c->g.n_cams) return rob_fail("F differs from the resident graph's n_cams", ESL_ERR_INVALID);
   }
   if (!c->init_batch) c->init_batch = new InitBatchState();
-  InitBatchState* bs = (InitBatchState*)c->init_batch;
+  InitBatchState* bs = c->init_batch;
   if (!bs->rob) bs->rob = new InitRobustState();
   InitRobustState* s = bs->rob;
   int64_t bad = 0;
@@ -1051,35 +1030,32 @@ extern "C" int esl_init_quadrics_robust(esl_ctx* c, const double* cams, int32_t 
 
   ESL_HIP_TRY(hipSetDevice(c->device));
   typedef InitRobustState R;
+  ScratchSet<R::kBufs>& d = s->set;
   InitRobustArgs k{};
   const size_t kept = s->idx.size(), nobs = (size_t)n_obs;
-  if (cams) {
-    if (const int rc = rob_grow(c, s, R::R_CAMS, (size_t)F * 7 * sizeof(double))) return rc;
-    if (F) ESL_HIP_TRY(hipMemcpyAsync(s->buf[R::R_CAMS], cams, (size_t)F * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    k.b.cams = (const double*)s->buf[R::R_CAMS];
-  } else k.b.cams = c->cams;
+  if (const int rc = source(c, d, R::R_CAMS, cams, c->cams, (size_t)F * 7 * sizeof(double), &k.b.cams)) return rc;
   const size_t want[R::kBufs] = {0, nobs * sizeof(int32_t), nobs * 4 * sizeof(double), kept * sizeof(int32_t), (size_t)N * sizeof(InitObj),
                                  (size_t)N * H * 4 * sizeof(double), (size_t)N * 16 * sizeof(int32_t), (size_t)N * 56 * sizeof(double),
                                  nobs * 2 * sizeof(double), nobs * 2 * sizeof(int32_t), (size_t)N * 10 * sizeof(double), (size_t)N * sizeof(int32_t)};
   for (int b = R::R_OCAM; b < R::kBufs; ++b)
-    if (const int rc = rob_grow(c, s, b, want[b])) return rc;
+    if (const int rc = d.grow(c, b, want[b])) return rc;
   if (kept) {   // entries that no object keeps are never read
-    ESL_HIP_TRY(hipMemcpyAsync(s->buf[R::R_OCAM], obs_cam, nobs * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    ESL_HIP_TRY(hipMemcpyAsync(s->buf[R::R_BOX], obs_boxes, nobs * 4 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    ESL_HIP_TRY(hipMemcpyAsync(s->buf[R::R_IDX], s->idx.data(), kept * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(d.buf[R::R_OCAM], obs_cam, nobs * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(d.buf[R::R_BOX], obs_boxes, nobs * 4 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(d.buf[R::R_IDX], s->idx.data(), kept * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
   }
-  ESL_HIP_TRY(hipMemcpyAsync(s->buf[R::R_OBJS], s->objs.data(), (size_t)N * sizeof(InitObj), hipMemcpyHostToDevice, c->stream));
-  k.b.obs_cam = (const int*)s->buf[R::R_OCAM]; k.b.obs_box = (const double*)s->buf[R::R_BOX]; k.b.idx = (const int*)s->buf[R::R_IDX];
+  ESL_HIP_TRY(hipMemcpyAsync(d.buf[R::R_OBJS], s->objs.data(), (size_t)N * sizeof(InitObj), hipMemcpyHostToDevice, c->stream));
+  k.b.obs_cam = d.at<const int>(R::R_OCAM); k.b.obs_box = d.at<const double>(R::R_BOX); k.b.idx = d.at<const int>(R::R_IDX);
   for (int i = 0; i < 4; ++i) k.b.K[i] = K[i];
   k.b.rows = rows; k.b.cols = cols; k.b.faithful = faithful; k.b.min_obs = min_observations;
-  k.objs = (const InitObj*)s->buf[R::R_OBJS];
+  k.objs = d.at<const InitObj>(R::R_OBJS);
   k.H = H; k.sample_size = p.sample_size; k.min_inliers = p.min_inliers; k.inlier_px = p.inlier_px; k.seed = p.seed;
-  k.hyp = (double*)s->buf[R::R_HYP];
+  k.hyp = d.at<double>(R::R_HYP);
   for (int q = 0; q < 2; ++q) {
-    k.oi[q] = (int*)s->buf[R::R_OI] + (size_t)q * N * 8; k.od[q] = (double*)s->buf[R::R_OD] + (size_t)q * N * 28;
-    k.res_e[q] = (double*)s->buf[R::R_RES] + (size_t)q * nobs; k.inl_e[q] = (int*)s->buf[R::R_INL] + (size_t)q * nobs;
+    k.oi[q] = d.at<int>(R::R_OI) + (size_t)q * N * 8; k.od[q] = d.at<double>(R::R_OD) + (size_t)q * N * 28;
+    k.res_e[q] = d.at<double>(R::R_RES) + (size_t)q * nobs; k.inl_e[q] = d.at<int>(R::R_INL) + (size_t)q * nobs;
   }
-  k.rf_ell = (const double*)s->buf[R::R_RFELL]; k.rf_ok = (const int*)s->buf[R::R_RFOK];
+  k.rf_ell = d.at<const double>(R::R_RFELL); k.rf_ok = d.at<const int>(R::R_RFOK);
   {
     ProfScope ps(c, 4);
     hipLaunchKernelGGL(k_init_robust, dim3((unsigned)((int64_t)N * H)), dim3(64), 0, c->stream, k, 0);
@@ -1116,8 +1092,8 @@ extern "C" int esl_init_quadrics_robust(esl_ctx* c, const double* cams, int32_t 
                                          s->rf_qs.data(), s->rf_perr.data(), s->rf_stats.data()))
       return rc;
     for (int32_t o = 0; o < N; ++o) s->rf_ok[o] = oi1[(size_t)o * 8] == 0 && s->rf_stats[(size_t)o * 4] == 0;
-    ESL_HIP_TRY(hipMemcpyAsync(s->buf[R::R_RFELL], s->rf_ell.data(), (size_t)N * 10 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    ESL_HIP_TRY(hipMemcpyAsync(s->buf[R::R_RFOK], s->rf_ok.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(d.buf[R::R_RFELL], s->rf_ell.data(), (size_t)N * 10 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(d.buf[R::R_RFOK], s->rf_ok.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     {
       ProfScope ps(c, 4);
       hipLaunchKernelGGL(k_init_robust, dim3((unsigned)N), dim3(64), 0, c->stream, k, 2);

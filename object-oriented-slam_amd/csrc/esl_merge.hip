@@ -42,15 +42,11 @@ struct MergeObj {
 
 enum { MS_NVALID, MS_NPAIRS, MS_NLINKS, MS_CHANGED, MS_NMERGED, MS_LARGEST, MS_NCONFLICTS, MS_COUNT = 8 };
 
-struct MergeState {
-  static constexpr int kBufs = 32;
-  void* buf[kBufs] = {};
-  size_t cap[kBufs] = {};
-};
 enum { MB_OBJS, MB_LAB, MB_W, MB_REC, MB_GATE, MB_ROWCNT, MB_ROWOFF, MB_CAND, MB_RES, MB_MEAS, MB_SCAL, MB_PROWCNT, MB_PROWOFF, MB_OPAIRS,
        MB_OCNT, MB_OIOU, MB_OCON, MB_COMP, MB_REPKEY, MB_WSUM, MB_GSIZE, MB_ROOT, MB_NEWOFF, MB_NEWIDX, MB_MOBJ, MB_MLAB, MB_MW, MB_OCAM,
-       MB_OOBJ, MB_OOUT, MB_SLOT, MB_TAB };
-static_assert(MB_TAB < MergeState::kBufs, "buffer table too small");
+       MB_OOBJ, MB_OOUT, MB_SLOT, MB_TAB, MB_COUNT };
+using MergeSet = ScratchSet<MB_COUNT>;
+struct MergeState { MergeSet set; };
 
 // ---- step 1 ---------------------------------------------------------------------------------------------------------------------------
 static __global__ __launch_bounds__(kMergeThreads) void k_merge_prep(const double* objs, int M, MergeObj* rec, double4* gate,
@@ -342,11 +338,13 @@ static __global__ __launch_bounds__(kMergeThreads) void k_merge_list_p3(const in
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(&scal[MS_NCONFLICTS], (unsigned long long)__popcll(m));
 }
 
+void merge_scratch_stats(const esl_ctx* c, int64_t* allocs, int64_t* bytes) {
+  if (c->merge) { *allocs = c->merge->set.allocs(); *bytes = (int64_t)c->merge->set.held(); }
+}
+
 void merge_release(esl_ctx* c) {   // called by esl_ctx_destroy
-  MergeState* s = (MergeState*)c->merge;
-  if (!s) return;
-  for (void* p : s->buf) if (p) (void)hipFree(p);
-  delete s;
+  if (c->merge) c->merge->set.release();
+  delete c->merge;
   c->merge = nullptr;
 }
 
@@ -355,16 +353,6 @@ void merge_release(esl_ctx* c) {   // called by esl_ctx_destroy
 using namespace esl;
 
 namespace {
-
-int merge_grow(esl_ctx* c, MergeState* s, int k, size_t bytes) {   // grow-only; contents are not kept
-  if (bytes <= s->cap[k] && s->buf[k]) return ESL_OK;
-  ESL_HIP_TRY(hipStreamSynchronize(c->stream));
-  if (s->buf[k]) (void)hipFree(s->buf[k]);
-  s->buf[k] = nullptr; s->cap[k] = 0;
-  ESL_HIP_TRY(hipMalloc(&s->buf[k], std::max<size_t>(bytes, 16)));
-  s->cap[k] = bytes;
-  return ESL_OK;
-}
 
 unsigned blocks_of(long long n) { return (unsigned)((n + kMergeThreads - 1) / kMergeThreads); }
 
@@ -380,11 +368,7 @@ int merge_check(esl_ctx* c, const double* objs, const int32_t* labels, int M, co
   if (!std::isfinite(p.min_iou) || !(p.min_iou > 0) || p.min_iou > 1) { set_error(w + ": min_iou outside (0, 1]"); return ESL_ERR_INVALID; }
   if (!std::isfinite(p.min_contain) || !(p.min_contain > 0)) { set_error(w + ": min_contain not finite or <= 0"); return ESL_ERR_INVALID; }
   if (p.max_pairs < 0) { set_error(w + ": negative max_pairs"); return ESL_ERR_INVALID; }
-  if (!objs && M > 0) {
-    if (!c->graph_loaded || !c->states_loaded) { set_error(w + ": a NULL source needs a resident graph with states"); return ESL_ERR_STATE; }
-    if (M != c->g.n_objs) { set_error(w + ": M differs from the resident graph's n_objs"); return ESL_ERR_INVALID; }
-  }
-  return ESL_OK;
+  return resident_source_check(c, who, false, 0, !objs && M > 0, M);
 }
 
 struct MergeFront {          // what steps 1 - 5 leave on the device
@@ -394,26 +378,20 @@ struct MergeFront {          // what steps 1 - 5 leave on the device
 };
 
 // steps 1 - 5 up to the candidates' integers and measures.  M > 0.
-int merge_front(esl_ctx* c, MergeState* s, const double* objs, const int32_t* labels, int M, const esl_merge_params& p, MergeFront& f) {
-  if (objs) {
-    if (const int rc = merge_grow(c, s, MB_OBJS, (size_t)M * 10 * sizeof(double))) return rc;
-    ESL_HIP_TRY(hipMemcpyAsync(s->buf[MB_OBJS], objs, (size_t)M * 10 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    f.objs = (const double*)s->buf[MB_OBJS];
-  } else f.objs = c->objs;
-  if (const int rc = merge_grow(c, s, MB_LAB, (size_t)M * sizeof(int32_t))) return rc;
-  ESL_HIP_TRY(hipMemcpyAsync(s->buf[MB_LAB], labels, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  f.lab = (const int*)s->buf[MB_LAB];
-  if (const int rc = merge_grow(c, s, MB_REC, (size_t)M * sizeof(MergeObj))) return rc;
-  if (const int rc = merge_grow(c, s, MB_GATE, (size_t)M * sizeof(double4))) return rc;
-  if (const int rc = merge_grow(c, s, MB_ROWCNT, (size_t)M * sizeof(int))) return rc;
-  if (const int rc = merge_grow(c, s, MB_ROWOFF, (size_t)(M + 1) * sizeof(long long))) return rc;
-  if (const int rc = merge_grow(c, s, MB_SCAL, MS_COUNT * sizeof(unsigned long long))) return rc;
-  f.scal = (unsigned long long*)s->buf[MB_SCAL];
+int merge_front(esl_ctx* c, MergeSet& s, const double* objs, const int32_t* labels, int M, const esl_merge_params& p, MergeFront& f) {
+  if (const int rc = source(c, s, MB_OBJS, objs, c->objs, (size_t)M * 10 * sizeof(double), &f.objs)) return rc;
+  if (const int rc = upload(c, s, MB_LAB, labels, (size_t)M * sizeof(int32_t), &f.lab)) return rc;
+  if (const int rc = s.grow(c, MB_REC, (size_t)M * sizeof(MergeObj))) return rc;
+  if (const int rc = s.grow(c, MB_GATE, (size_t)M * sizeof(double4))) return rc;
+  if (const int rc = s.grow(c, MB_ROWCNT, (size_t)M * sizeof(int))) return rc;
+  if (const int rc = s.grow(c, MB_ROWOFF, (size_t)(M + 1) * sizeof(long long))) return rc;
+  if (const int rc = s.grow(c, MB_SCAL, MS_COUNT * sizeof(unsigned long long))) return rc;
+  f.scal = s.at<unsigned long long>(MB_SCAL);
   ESL_HIP_TRY(hipMemsetAsync(f.scal, 0, MS_COUNT * sizeof(unsigned long long), c->stream));
-  MergeObj* rec = (MergeObj*)s->buf[MB_REC];
-  double4* gate = (double4*)s->buf[MB_GATE];
-  int* rowcnt = (int*)s->buf[MB_ROWCNT];
-  long long* rowoff = (long long*)s->buf[MB_ROWOFF];
+  MergeObj* rec = s.at<MergeObj>(MB_REC);
+  double4* gate = s.at<double4>(MB_GATE);
+  int* rowcnt = s.at<int>(MB_ROWCNT);
+  long long* rowoff = s.at<long long>(MB_ROWOFF);
   const unsigned mb = blocks_of(M);
   {
     ProfScope ps(c, 4);
@@ -429,17 +407,17 @@ int merge_front(esl_ctx* c, MergeState* s, const double* objs, const int32_t* la
   ESL_HIP_TRY(hipStreamSynchronize(c->stream));
   f.n_cand = n_cand; f.n_valid = (int)n_valid; f.over = n_cand > (long long)p.max_pairs;
   if (f.over || n_cand == 0) return ESL_OK;
-  if (const int rc = merge_grow(c, s, MB_CAND, (size_t)n_cand * sizeof(int2))) return rc;
-  if (const int rc = merge_grow(c, s, MB_RES, (size_t)n_cand * sizeof(int4))) return rc;
-  if (const int rc = merge_grow(c, s, MB_MEAS, (size_t)n_cand * sizeof(double2))) return rc;
+  if (const int rc = s.grow(c, MB_CAND, (size_t)n_cand * sizeof(int2))) return rc;
+  if (const int rc = s.grow(c, MB_RES, (size_t)n_cand * sizeof(int4))) return rc;
+  if (const int rc = s.grow(c, MB_MEAS, (size_t)n_cand * sizeof(double2))) return rc;
   const int n = p.lattice;
   const unsigned ob = (unsigned)std::min<long long>((n_cand + 3) / 4, kMergeOverlapBlocks);
   {
     ProfScope ps(c, 4);
     hipLaunchKernelGGL(k_merge_cand, dim3(mb), dim3(kMergeThreads), 0, c->stream, gate, f.lab, M, p.match_labels != 0 ? 1 : 0, 1, rowcnt,
-                       rowoff, (int2*)s->buf[MB_CAND]);
-    hipLaunchKernelGGL(k_merge_overlap, dim3(ob), dim3(kMergeThreads), 0, c->stream, rec, (const int2*)s->buf[MB_CAND], n_cand, n,
-                       merge_lattice_count(n), p.min_iou, p.min_contain, (int4*)s->buf[MB_RES], (double2*)s->buf[MB_MEAS], f.scal);
+                       rowoff, s.at<int2>(MB_CAND));
+    hipLaunchKernelGGL(k_merge_overlap, dim3(ob), dim3(kMergeThreads), 0, c->stream, rec, s.at<const int2>(MB_CAND), n_cand, n,
+                       merge_lattice_count(n), p.min_iou, p.min_contain, s.at<int4>(MB_RES), s.at<double2>(MB_MEAS), f.scal);
   }
   ESL_HIP_TRY(hipGetLastError());
   return ESL_OK;
@@ -465,28 +443,28 @@ extern "C" int esl_map_overlaps(esl_ctx* c, const double* objs, const int32_t* l
   if (M == 0) return ESL_OK;
   ESL_HIP_TRY(hipSetDevice(c->device));
   if (!c->merge) c->merge = new MergeState();
-  MergeState* s = (MergeState*)c->merge;
+  MergeSet& s = c->merge->set;
   MergeFront f;
   if (const int rc = merge_front(c, s, objs, labels, M, p, f)) return rc;
   *n_candidates = f.n_cand;
   if (f.over) { *n_pairs = -1; return ESL_OK; }   // more candidates than max_pairs: not computed
   if (f.n_cand == 0) return ESL_OK;
   const long long wcap = std::min<long long>(cap, f.n_cand);
-  if (const int rc = merge_grow(c, s, MB_PROWCNT, (size_t)M * sizeof(int))) return rc;
-  if (const int rc = merge_grow(c, s, MB_PROWOFF, (size_t)(M + 1) * sizeof(long long))) return rc;
-  if (const int rc = merge_grow(c, s, MB_OPAIRS, (size_t)wcap * sizeof(int2))) return rc;
-  if (const int rc = merge_grow(c, s, MB_OCNT, (size_t)wcap * sizeof(int2))) return rc;
-  if (const int rc = merge_grow(c, s, MB_OIOU, (size_t)wcap * sizeof(double))) return rc;
-  if (const int rc = merge_grow(c, s, MB_OCON, (size_t)wcap * sizeof(double))) return rc;
-  int* prowcnt = (int*)s->buf[MB_PROWCNT];
-  long long* prowoff = (long long*)s->buf[MB_PROWOFF];
+  if (const int rc = s.grow(c, MB_PROWCNT, (size_t)M * sizeof(int))) return rc;
+  if (const int rc = s.grow(c, MB_PROWOFF, (size_t)(M + 1) * sizeof(long long))) return rc;
+  if (const int rc = s.grow(c, MB_OPAIRS, (size_t)wcap * sizeof(int2))) return rc;
+  if (const int rc = s.grow(c, MB_OCNT, (size_t)wcap * sizeof(int2))) return rc;
+  if (const int rc = s.grow(c, MB_OIOU, (size_t)wcap * sizeof(double))) return rc;
+  if (const int rc = s.grow(c, MB_OCON, (size_t)wcap * sizeof(double))) return rc;
+  int* prowcnt = s.at<int>(MB_PROWCNT);
+  long long* prowoff = s.at<long long>(MB_PROWOFF);
   const unsigned mb = blocks_of(M);
   {
     ProfScope ps(c, 4);
     for (int fill = 0; fill < 2; ++fill) {
-      hipLaunchKernelGGL(k_merge_rows, dim3(mb), dim3(kMergeThreads), 0, c->stream, (const int2*)s->buf[MB_CAND], (const int4*)s->buf[MB_RES],
-                         (const double2*)s->buf[MB_MEAS], (const long long*)s->buf[MB_ROWOFF], M, fill, prowcnt, prowoff, wcap,
-                         (int2*)s->buf[MB_OPAIRS], (int2*)s->buf[MB_OCNT], (double*)s->buf[MB_OIOU], (double*)s->buf[MB_OCON]);
+      hipLaunchKernelGGL(k_merge_rows, dim3(mb), dim3(kMergeThreads), 0, c->stream, s.at<const int2>(MB_CAND), s.at<const int4>(MB_RES),
+                         s.at<const double2>(MB_MEAS), s.at<const long long>(MB_ROWOFF), M, fill, prowcnt, prowoff, wcap,
+                         s.at<int2>(MB_OPAIRS), s.at<int2>(MB_OCNT), s.at<double>(MB_OIOU), s.at<double>(MB_OCON));
       if (!fill) hipLaunchKernelGGL(k_merge_scan, dim3(1), dim3(1024), 0, c->stream, prowcnt, M, prowoff);
     }
   }
@@ -497,10 +475,10 @@ extern "C" int esl_map_overlaps(esl_ctx* c, const double* objs, const int32_t* l
   *n_pairs = np;
   const size_t nw = (size_t)std::min<long long>(np, wcap);
   if (nw) {
-    ESL_HIP_TRY(hipMemcpyAsync(pairs_out, s->buf[MB_OPAIRS], nw * sizeof(int2), hipMemcpyDeviceToHost, c->stream));
-    ESL_HIP_TRY(hipMemcpyAsync(counts_out, s->buf[MB_OCNT], nw * sizeof(int2), hipMemcpyDeviceToHost, c->stream));
-    ESL_HIP_TRY(hipMemcpyAsync(iou_out, s->buf[MB_OIOU], nw * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    ESL_HIP_TRY(hipMemcpyAsync(contain_out, s->buf[MB_OCON], nw * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(pairs_out, s.buf[MB_OPAIRS], nw * sizeof(int2), hipMemcpyDeviceToHost, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(counts_out, s.buf[MB_OCNT], nw * sizeof(int2), hipMemcpyDeviceToHost, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(iou_out, s.buf[MB_OIOU], nw * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(contain_out, s.buf[MB_OCON], nw * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     ESL_HIP_TRY(hipStreamSynchronize(c->stream));
   }
   return ESL_OK;
@@ -538,7 +516,7 @@ extern "C" int esl_map_merge(esl_ctx* c, const double* objs, const int32_t* labe
   }
   ESL_HIP_TRY(hipSetDevice(c->device));
   if (!c->merge) c->merge = new MergeState();
-  MergeState* s = (MergeState*)c->merge;
+  MergeSet& s = c->merge->set;
   MergeFront f;
   if (const int rc = merge_front(c, s, objs, labels, M, p, f)) return rc;
   out->n_valid = f.n_valid; out->n_candidates = f.n_cand;
@@ -562,25 +540,25 @@ extern "C" int esl_map_merge(esl_ctx* c, const double* objs, const int32_t* labe
   const unsigned mb = blocks_of(M);
   const size_t mi = (size_t)M * sizeof(int);
   for (int k : {MB_W, MB_COMP, MB_WSUM, MB_GSIZE, MB_ROOT, MB_NEWIDX, MB_MLAB, MB_MW})
-    if (const int rc = merge_grow(c, s, k, mi)) return rc;
-  if (const int rc = merge_grow(c, s, MB_REPKEY, (size_t)M * sizeof(unsigned long long))) return rc;
-  if (const int rc = merge_grow(c, s, MB_NEWOFF, (size_t)(M + 1) * sizeof(long long))) return rc;
-  if (const int rc = merge_grow(c, s, MB_MOBJ, (size_t)M * 10 * sizeof(double))) return rc;
+    if (const int rc = s.grow(c, k, mi)) return rc;
+  if (const int rc = s.grow(c, MB_REPKEY, (size_t)M * sizeof(unsigned long long))) return rc;
+  if (const int rc = s.grow(c, MB_NEWOFF, (size_t)(M + 1) * sizeof(long long))) return rc;
+  if (const int rc = s.grow(c, MB_MOBJ, (size_t)M * 10 * sizeof(double))) return rc;
   unsigned long long slots = 64;
   if (n_obs > 0) {
     while (slots < 2ull * (unsigned long long)n_obs) slots <<= 1;
     const size_t ob = (size_t)n_obs * sizeof(int);
     for (int k : {MB_OCAM, MB_OOBJ, MB_OOUT, MB_SLOT})
-      if (const int rc = merge_grow(c, s, k, ob)) return rc;
-    if (const int rc = merge_grow(c, s, MB_TAB, (size_t)slots * 3 * sizeof(unsigned long long))) return rc;
-    ESL_HIP_TRY(hipMemcpyAsync(s->buf[MB_OCAM], obs_cam, ob, hipMemcpyHostToDevice, c->stream));
-    ESL_HIP_TRY(hipMemcpyAsync(s->buf[MB_OOBJ], obs_obj, ob, hipMemcpyHostToDevice, c->stream));
-    ESL_HIP_TRY(hipMemsetAsync(s->buf[MB_TAB], 0xff, (size_t)slots * 3 * sizeof(unsigned long long), c->stream));
+      if (const int rc = s.grow(c, k, ob)) return rc;
+    if (const int rc = s.grow(c, MB_TAB, (size_t)slots * 3 * sizeof(unsigned long long))) return rc;
+    ESL_HIP_TRY(hipMemcpyAsync(s.buf[MB_OCAM], obs_cam, ob, hipMemcpyHostToDevice, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(s.buf[MB_OOBJ], obs_obj, ob, hipMemcpyHostToDevice, c->stream));
+    ESL_HIP_TRY(hipMemsetAsync(s.buf[MB_TAB], 0xff, (size_t)slots * 3 * sizeof(unsigned long long), c->stream));
   }
-  int* w = (int*)s->buf[MB_W];
-  int* comp = (int*)s->buf[MB_COMP];
-  const int* o_cam = (const int*)s->buf[MB_OCAM];
-  const int* o_obj = (const int*)s->buf[MB_OOBJ];
+  int* w = s.at<int>(MB_W);
+  int* comp = s.at<int>(MB_COMP);
+  const int* o_cam = s.at<const int>(MB_OCAM);
+  const int* o_obj = s.at<const int>(MB_OOBJ);
   const unsigned eb = blocks_of(n_obs);
   // weights: given, the objects' list entries, or 1
   if (weights) ESL_HIP_TRY(hipMemcpyAsync(w, weights, mi, hipMemcpyHostToDevice, c->stream));
@@ -601,8 +579,8 @@ extern "C" int esl_map_merge(esl_ctx* c, const double* objs, const int32_t* labe
       ESL_HIP_TRY(hipMemsetAsync(f.scal + MS_CHANGED, 0, sizeof(unsigned long long), c->stream));
       {
         ProfScope ps(c, 4);
-        hipLaunchKernelGGL(k_merge_hook, dim3(hb), dim3(kMergeThreads), 0, c->stream, (const int2*)s->buf[MB_CAND],
-                           (const int4*)s->buf[MB_RES], f.n_cand, comp, f.scal);
+        hipLaunchKernelGGL(k_merge_hook, dim3(hb), dim3(kMergeThreads), 0, c->stream, s.at<const int2>(MB_CAND),
+                           s.at<const int4>(MB_RES), f.n_cand, comp, f.scal);
         hipLaunchKernelGGL(k_merge_jump, dim3(mb), dim3(kMergeThreads), 0, c->stream, comp, M);
       }
       ESL_HIP_TRY(hipGetLastError());
@@ -611,45 +589,45 @@ extern "C" int esl_map_merge(esl_ctx* c, const double* objs, const int32_t* labe
       if (!changed) break;
     }
   }
-  ESL_HIP_TRY(hipMemsetAsync(s->buf[MB_REPKEY], 0, (size_t)M * sizeof(unsigned long long), c->stream));
-  ESL_HIP_TRY(hipMemsetAsync(s->buf[MB_WSUM], 0, mi, c->stream));
-  ESL_HIP_TRY(hipMemsetAsync(s->buf[MB_GSIZE], 0, mi, c->stream));
+  ESL_HIP_TRY(hipMemsetAsync(s.buf[MB_REPKEY], 0, (size_t)M * sizeof(unsigned long long), c->stream));
+  ESL_HIP_TRY(hipMemsetAsync(s.buf[MB_WSUM], 0, mi, c->stream));
+  ESL_HIP_TRY(hipMemsetAsync(s.buf[MB_GSIZE], 0, mi, c->stream));
   {
     ProfScope ps(c, 4);
-    hipLaunchKernelGGL(k_merge_group_acc, dim3(mb), dim3(kMergeThreads), 0, c->stream, comp, w, M, (unsigned long long*)s->buf[MB_REPKEY],
-                       (int*)s->buf[MB_WSUM], (int*)s->buf[MB_GSIZE]);
-    hipLaunchKernelGGL(k_merge_group_roots, dim3(mb), dim3(kMergeThreads), 0, c->stream, comp, (const int*)s->buf[MB_GSIZE], M,
-                       (int*)s->buf[MB_ROOT], f.scal);
-    hipLaunchKernelGGL(k_merge_scan, dim3(1), dim3(1024), 0, c->stream, (const int*)s->buf[MB_ROOT], M, (long long*)s->buf[MB_NEWOFF]);
-    hipLaunchKernelGGL(k_merge_group_write, dim3(mb), dim3(kMergeThreads), 0, c->stream, comp, (const int*)s->buf[MB_ROOT],
-                       (const long long*)s->buf[MB_NEWOFF], (const unsigned long long*)s->buf[MB_REPKEY], (const int*)s->buf[MB_WSUM],
-                       f.objs, f.lab, M, (int*)s->buf[MB_NEWIDX], (double*)s->buf[MB_MOBJ], (int*)s->buf[MB_MLAB], (int*)s->buf[MB_MW]);
+    hipLaunchKernelGGL(k_merge_group_acc, dim3(mb), dim3(kMergeThreads), 0, c->stream, comp, w, M, s.at<unsigned long long>(MB_REPKEY),
+                       s.at<int>(MB_WSUM), s.at<int>(MB_GSIZE));
+    hipLaunchKernelGGL(k_merge_group_roots, dim3(mb), dim3(kMergeThreads), 0, c->stream, comp, s.at<const int>(MB_GSIZE), M,
+                       s.at<int>(MB_ROOT), f.scal);
+    hipLaunchKernelGGL(k_merge_scan, dim3(1), dim3(1024), 0, c->stream, s.at<const int>(MB_ROOT), M, s.at<long long>(MB_NEWOFF));
+    hipLaunchKernelGGL(k_merge_group_write, dim3(mb), dim3(kMergeThreads), 0, c->stream, comp, s.at<const int>(MB_ROOT),
+                       s.at<const long long>(MB_NEWOFF), s.at<const unsigned long long>(MB_REPKEY), s.at<const int>(MB_WSUM),
+                       f.objs, f.lab, M, s.at<int>(MB_NEWIDX), s.at<double>(MB_MOBJ), s.at<int>(MB_MLAB), s.at<int>(MB_MW));
     if (n_obs > 0) {
-      unsigned long long* keys = (unsigned long long*)s->buf[MB_TAB];
+      unsigned long long* keys = s.at<unsigned long long>(MB_TAB);
       unsigned long long* val1 = keys + slots;
       unsigned long long* val2 = val1 + slots;
-      unsigned int* slot_of = (unsigned int*)s->buf[MB_SLOT];
+      unsigned int* slot_of = s.at<unsigned int>(MB_SLOT);
       hipLaunchKernelGGL(k_merge_list_p1, dim3(eb), dim3(kMergeThreads), 0, c->stream, o_cam, o_obj, (long long)n_obs, comp, w, slots - 1,
                          keys, val1, slot_of);
       hipLaunchKernelGGL(k_merge_list_p2, dim3(eb), dim3(kMergeThreads), 0, c->stream, o_obj, (long long)n_obs, slot_of, val1, val2);
       hipLaunchKernelGGL(k_merge_list_p3, dim3(eb), dim3(kMergeThreads), 0, c->stream, o_obj, (long long)n_obs, slot_of, val1, val2,
-                         (const int*)s->buf[MB_NEWIDX], (int*)s->buf[MB_OOUT], f.scal);
+                         s.at<const int>(MB_NEWIDX), s.at<int>(MB_OOUT), f.scal);
     }
   }
   ESL_HIP_TRY(hipGetLastError());
   unsigned long long sc[MS_COUNT];
   long long n_groups = 0;
   ESL_HIP_TRY(hipMemcpyAsync(sc, f.scal, sizeof(sc), hipMemcpyDeviceToHost, c->stream));
-  ESL_HIP_TRY(hipMemcpyAsync(&n_groups, (long long*)s->buf[MB_NEWOFF] + M, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+  ESL_HIP_TRY(hipMemcpyAsync(&n_groups, s.at<long long>(MB_NEWOFF) + M, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
   ESL_HIP_TRY(hipMemcpyAsync(group_out, comp, mi, hipMemcpyDeviceToHost, c->stream));
-  ESL_HIP_TRY(hipMemcpyAsync(new_index_out, s->buf[MB_NEWIDX], mi, hipMemcpyDeviceToHost, c->stream));
+  ESL_HIP_TRY(hipMemcpyAsync(new_index_out, s.buf[MB_NEWIDX], mi, hipMemcpyDeviceToHost, c->stream));
   ESL_HIP_TRY(hipStreamSynchronize(c->stream));
   const size_t G = (size_t)n_groups;
-  ESL_HIP_TRY(hipMemcpyAsync(merged_objs_out, s->buf[MB_MOBJ], G * 10 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  ESL_HIP_TRY(hipMemcpyAsync(merged_labels_out, s->buf[MB_MLAB], G * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  ESL_HIP_TRY(hipMemcpyAsync(merged_weights_out, s->buf[MB_MW], G * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  ESL_HIP_TRY(hipMemcpyAsync(merged_objs_out, s.buf[MB_MOBJ], G * 10 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  ESL_HIP_TRY(hipMemcpyAsync(merged_labels_out, s.buf[MB_MLAB], G * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  ESL_HIP_TRY(hipMemcpyAsync(merged_weights_out, s.buf[MB_MW], G * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   if (n_obs > 0 && obs_obj_out)
-    ESL_HIP_TRY(hipMemcpyAsync(obs_obj_out, s->buf[MB_OOUT], (size_t)n_obs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(obs_obj_out, s.buf[MB_OOUT], (size_t)n_obs * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   ESL_HIP_TRY(hipStreamSynchronize(c->stream));
   out->status = 0; out->n_groups = (int32_t)n_groups; out->n_merged_groups = (int32_t)sc[MS_NMERGED];
   out->largest_group = (int32_t)sc[MS_LARGEST]; out->n_conflicts = (int32_t)sc[MS_NCONFLICTS];

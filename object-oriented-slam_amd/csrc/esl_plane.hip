@@ -609,8 +609,7 @@ extern "C" void esl_plane_params_default(esl_plane_params* p) {
 
 namespace esl {
 void plane_release(esl_ctx* c) {
-  if (c->plane_slab) (void)hipFree(c->plane_slab);
-  c->plane_slab = nullptr; c->plane_slab_cap = 0;
+  c->plane_slab.release();
 }
 }  // namespace esl
 
@@ -628,16 +627,10 @@ int plane_reserve(esl_ctx* c, size_t npx, int max_planes, int model_min, PlaneWo
                          al((size_t)w.list_cap * 5 * sizeof(double)), al(npx * 4), al((size_t)w.list_cap * sizeof(int)), al(((npx + 255) / 256 + 1) * sizeof(int))};
   size_t need = 0;
   for (size_t v : sz) need += v;
-  if (need > c->plane_slab_cap) {
-    ESL_HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->plane_slab) (void)hipFree(c->plane_slab);
-    c->plane_slab = nullptr; c->plane_slab_cap = 0;
-    ESL_HIP_TRY(hipMalloc((void**)&c->plane_slab, need));
-    c->plane_slab_cap = need;
-  }
+  if (const int rc = c->plane_slab.grow(c, 0, need)) return rc;
   Buf* b[11] = {&w.depth, &w.nrm, &w.par, &w.cnt, &w.mom, &w.out, &w.map, &w.list, &w.labels, &w.grown, &w.blk};
   size_t off = 0;
-  for (int k = 0; k < 11; ++k) { b[k]->p = c->plane_slab + off; off += sz[k]; }
+  for (int k = 0; k < 11; ++k) { b[k]->p = c->plane_slab.at<char>(0) + off; off += sz[k]; }
   return ESL_OK;
 }
 

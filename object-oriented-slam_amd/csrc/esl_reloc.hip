@@ -47,20 +47,12 @@ struct RelocState {
   bool have_map = false;
   int M = 0;
   RelocFrame Gw;
-  // map (grow-only)
-  size_t map_cap = 0;
-  double* m_objs = nullptr; double* m_xyh = nullptr; double* m_ax = nullptr; int* m_lab = nullptr;
-  // detections
-  double* d_objs = nullptr; double* d_xyh = nullptr; double* d_ax = nullptr; int* d_lab = nullptr;
-  // candidate compaction
-  size_t wave_cap = 0; int* wave_cnt = nullptr; int* wave_off = nullptr;
-  int* row = nullptr;                       // kRelocMaxDet + 1
-  size_t cand_cap = 0; int* c_d = nullptr; int* c_m = nullptr; double2* c_p = nullptr;
-  // hypotheses
-  size_t surv_cap = 0; unsigned long long* surv = nullptr;
-  unsigned long long* counters = nullptr;   // [0] survivors of the current slice, [1] hypotheses so far, [2] P
-  RelocBest* part = nullptr; RelocBest* best = nullptr;
-  RelocOut* out_dev = nullptr;
+  // the map (double objs, xyh, ax; int lab), the detections (the same four, kRelocMaxDet of them), the candidate compaction (int
+  // wave_cnt, wave_off, row[kRelocMaxDet + 1], c_d, c_m; double2 c_p), the hypotheses (u64 surv; u64 counters[4]: [0] survivors of the
+  // current slice, [1] hypotheses so far, [2] P; RelocBest part[kRelocScoreBlocks], best; RelocOut out)
+  enum { M_OBJS, M_XYH, M_AX, M_LAB, D_OBJS, D_XYH, D_AX, D_LAB, WAVE_CNT, WAVE_OFF, ROW, C_D, C_M, C_P, SURV, COUNTERS, PART, BEST, OUT,
+         kBufs };
+  ScratchSet<kBufs> set;
   char* host = nullptr;                     // pinned: detections in, RelocOut / counters back
 };
 
@@ -382,12 +374,14 @@ static __global__ __launch_bounds__(64) void k_reloc_final(RelocFinalArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------
+void reloc_scratch_stats(const esl_ctx* c, int64_t* allocs, int64_t* bytes) {
+  if (c->reloc) { *allocs = c->reloc->set.allocs(); *bytes = (int64_t)c->reloc->set.held(); }
+}
+
 void reloc_release(esl_ctx* c) {   // called by esl_ctx_destroy
-  RelocState* r = (RelocState*)c->reloc;
+  RelocState* r = c->reloc;
   if (!r) return;
-  void* dev[] = {r->m_objs, r->m_xyh, r->m_ax, r->m_lab, r->d_objs, r->d_xyh, r->d_ax, r->d_lab, r->wave_cnt, r->wave_off, r->row,
-                 r->c_d, r->c_m, r->c_p, r->surv, r->counters, r->part, r->best, r->out_dev};
-  for (void* p : dev) if (p) (void)hipFree(p);
+  r->set.release();
   if (r->host) (void)hipHostFree(r->host);
   delete r;
   c->reloc = nullptr;
@@ -399,32 +393,19 @@ using namespace esl;
 
 namespace {
 
-template <class T>
-int reloc_grow(esl_ctx* c, T** p, size_t* cap, size_t need) {   // grow-only; contents are not kept
-  if (need <= *cap && *p) return ESL_OK;
-  ESL_HIP_TRY(hipStreamSynchronize(c->stream));
-  if (*p) (void)hipFree(*p);
-  *p = nullptr; *cap = 0;
-  ESL_HIP_TRY(hipMalloc((void**)p, std::max<size_t>(need, 1) * sizeof(T)));
-  *cap = need;
-  return ESL_OK;
-}
-
 // the buffers whose size never changes
 int reloc_state(esl_ctx* c, RelocState** out) {
   if (!c->reloc) c->reloc = new RelocState();
-  RelocState* r = (RelocState*)c->reloc;
+  RelocState* r = c->reloc;
   *out = r;
   if (r->host) return ESL_OK;
-  ESL_HIP_TRY(hipMalloc((void**)&r->d_objs, kRelocMaxDet * 10 * sizeof(double)));
-  ESL_HIP_TRY(hipMalloc((void**)&r->d_xyh, kRelocMaxDet * 3 * sizeof(double)));
-  ESL_HIP_TRY(hipMalloc((void**)&r->d_ax, kRelocMaxDet * 3 * sizeof(double)));
-  ESL_HIP_TRY(hipMalloc((void**)&r->d_lab, kRelocMaxDet * sizeof(int)));
-  ESL_HIP_TRY(hipMalloc((void**)&r->row, (kRelocMaxDet + 1) * sizeof(int)));
-  ESL_HIP_TRY(hipMalloc((void**)&r->counters, 4 * sizeof(unsigned long long)));
-  ESL_HIP_TRY(hipMalloc((void**)&r->part, kRelocScoreBlocks * sizeof(RelocBest)));
-  ESL_HIP_TRY(hipMalloc((void**)&r->best, sizeof(RelocBest)));
-  ESL_HIP_TRY(hipMalloc((void**)&r->out_dev, sizeof(RelocOut)));
+  using R = RelocState;
+  const int slot[9] = {R::D_OBJS, R::D_XYH, R::D_AX, R::D_LAB, R::ROW, R::COUNTERS, R::PART, R::BEST, R::OUT};
+  const size_t bytes[9] = {kRelocMaxDet * 10 * sizeof(double), kRelocMaxDet * 3 * sizeof(double), kRelocMaxDet * 3 * sizeof(double),
+                           kRelocMaxDet * sizeof(int), (kRelocMaxDet + 1) * sizeof(int), 4 * sizeof(unsigned long long),
+                           kRelocScoreBlocks * sizeof(RelocBest), sizeof(RelocBest), sizeof(RelocOut)};
+  for (int i = 0; i < 9; ++i)
+    if (const int rc = r->set.grow(c, slot[i], bytes[i])) return rc;
   ESL_HIP_TRY(hipHostMalloc((void**)&r->host, 8192, hipHostMallocDefault));
   return ESL_OK;
 }
@@ -488,27 +469,24 @@ extern "C" int esl_reloc_set_map(esl_ctx* c, const double* objs, const int32_t* 
   if (!c || M < 0 || !ground_world || (M > 0 && !labels)) { set_error("esl_reloc_set_map: bad argument"); return ESL_ERR_INVALID; }
   RelocFrame f;
   if (!reloc_frame(ground_world, f)) { set_error("esl_reloc_set_map: the ground plane's normal is shorter than 1e-12"); return ESL_ERR_INVALID; }
-  if (!objs && M > 0) {
-    if (!c->graph_loaded || !c->states_loaded) { set_error("esl_reloc_set_map: objs == NULL needs a resident graph with states"); return ESL_ERR_STATE; }
-    if (M != c->g.n_objs) { set_error("esl_reloc_set_map: M differs from the resident graph's n_objs"); return ESL_ERR_INVALID; }
-  }
+  if (const int rc = resident_source_check(c, "esl_reloc_set_map", false, 0, !objs && M > 0, M)) return rc;
   ESL_HIP_TRY(hipSetDevice(c->device));
   RelocState* r = nullptr;
   if (const int rc = reloc_state(c, &r)) return rc;
   r->have_map = false;
-  if ((size_t)M > r->map_cap || !r->m_objs) {
-    size_t c0 = r->map_cap, c1 = r->map_cap, c2 = r->map_cap, c3 = r->map_cap;
-    if (const int rc = reloc_grow(c, &r->m_objs, &c0, (size_t)M * 10)) return rc;
-    if (const int rc = reloc_grow(c, &r->m_xyh, &c1, (size_t)M * 3)) return rc;
-    if (const int rc = reloc_grow(c, &r->m_ax, &c2, (size_t)M * 3)) return rc;
-    if (const int rc = reloc_grow(c, &r->m_lab, &c3, (size_t)M)) return rc;
-    r->map_cap = (size_t)M;
-  }
+  using R = RelocState;
+  ScratchSet<R::kBufs>& s = r->set;
+  if (const int rc = s.grow(c, R::M_OBJS, (size_t)M * 10 * sizeof(double))) return rc;
+  if (const int rc = s.grow(c, R::M_XYH, (size_t)M * 3 * sizeof(double))) return rc;
+  if (const int rc = s.grow(c, R::M_AX, (size_t)M * 3 * sizeof(double))) return rc;
+  if (const int rc = s.grow(c, R::M_LAB, (size_t)M * sizeof(int))) return rc;
   if (M > 0) {
-    if (objs) ESL_HIP_TRY(hipMemcpyAsync(r->m_objs, objs, (size_t)M * 10 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    else ESL_HIP_TRY(hipMemcpyAsync(r->m_objs, c->objs, (size_t)M * 10 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    ESL_HIP_TRY(hipMemcpyAsync(r->m_lab, labels, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_reloc_prep, dim3((M + 255) / 256), dim3(256), 0, c->stream, (const double*)r->m_objs, (int)M, f, r->m_xyh, r->m_ax);
+    double* m_objs = s.at<double>(R::M_OBJS);   // a copy of the map: the resident states may move on, the map stays
+    if (objs) ESL_HIP_TRY(hipMemcpyAsync(m_objs, objs, (size_t)M * 10 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    else ESL_HIP_TRY(hipMemcpyAsync(m_objs, c->objs, (size_t)M * 10 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(s.buf[R::M_LAB], labels, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_reloc_prep, dim3((M + 255) / 256), dim3(256), 0, c->stream, (const double*)m_objs, (int)M, f, s.at<double>(R::M_XYH),
+                       s.at<double>(R::M_AX));
     ESL_HIP_TRY(hipGetLastError());
     ESL_HIP_TRY(hipStreamSynchronize(c->stream));   // the caller's arrays are free again
   }
@@ -530,7 +508,7 @@ extern "C" int esl_relocalize(esl_ctx* c, const double* det_objs, const int32_t*
   }
   RelocFrame fc;
   if (!reloc_frame(ground_cam, fc)) { set_error("esl_relocalize: the ground plane's normal is shorter than 1e-12"); return ESL_ERR_INVALID; }
-  RelocState* r = (RelocState*)c->reloc;
+  RelocState* r = c->reloc;
   if (!r || !r->have_map) { set_error("esl_relocalize: no map (esl_reloc_set_map)"); return ESL_ERR_STATE; }
   ESL_HIP_TRY(hipSetDevice(c->device));
 
@@ -545,42 +523,46 @@ extern "C" int esl_relocalize(esl_ctx* c, const double* det_objs, const int32_t*
   g.size_gate = p.size_ratio > 1; g.log_ratio = g.size_gate ? std::log(p.size_ratio) : 0; g.min_baseline = p.min_baseline;
   g.min_inliers = p.min_inliers; g.match_labels = p.match_labels != 0; g.refine = p.refine != 0;
 
+  using R = RelocState;
+  ScratchSet<R::kBufs>& s = r->set;
+  double *const d_objs = s.at<double>(R::D_OBJS), *const d_xyh = s.at<double>(R::D_XYH), *const d_ax = s.at<double>(R::D_AX);
+  int *const d_lab = s.at<int>(R::D_LAB), *const row = s.at<int>(R::ROW);
+  unsigned long long* const counters = s.at<unsigned long long>(R::COUNTERS);
+  RelocBest *const part = s.at<RelocBest>(R::PART), *const best = s.at<RelocBest>(R::BEST);
+
   // detections: staged through the pinned block, prepared on the device
   double* h_objs = (double*)r->host; int32_t* h_lab = (int32_t*)(r->host + kRelocMaxDet * 10 * sizeof(double));
   std::memcpy(h_objs, det_objs, (size_t)D * 10 * sizeof(double));
   std::memcpy(h_lab, det_labels, (size_t)D * sizeof(int32_t));
-  ESL_HIP_TRY(hipMemcpyAsync(r->d_objs, h_objs, (size_t)D * 10 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  ESL_HIP_TRY(hipMemcpyAsync(r->d_lab, h_lab, (size_t)D * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(k_reloc_prep, dim3(1), dim3(256), 0, c->stream, (const double*)r->d_objs, (int)D, fc, r->d_xyh, r->d_ax);
+  ESL_HIP_TRY(hipMemcpyAsync(d_objs, h_objs, (size_t)D * 10 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  ESL_HIP_TRY(hipMemcpyAsync(d_lab, h_lab, (size_t)D * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_reloc_prep, dim3(1), dim3(256), 0, c->stream, (const double*)d_objs, (int)D, fc, d_xyh, d_ax);
 
   // candidates: count per wave, scan, (after the host has seen P) fill
   const int wpd = (M + 63) / 64;
   const size_t nw = (size_t)D * wpd;
-  if (nw > r->wave_cap || !r->wave_cnt) {
-    size_t c0 = r->wave_cap, c1 = r->wave_cap;
-    if (const int rc = reloc_grow(c, &r->wave_cnt, &c0, nw)) return rc;
-    if (const int rc = reloc_grow(c, &r->wave_off, &c1, nw)) return rc;
-    r->wave_cap = nw;
-  }
+  if (const int rc = s.grow(c, R::WAVE_CNT, nw * sizeof(int))) return rc;
+  if (const int rc = s.grow(c, R::WAVE_OFF, nw * sizeof(int))) return rc;
   const size_t ccap = (size_t)std::max(p.max_candidates, 2);
-  if (ccap > r->cand_cap || !r->c_d) {
-    size_t c0 = r->cand_cap, c1 = r->cand_cap, c2 = r->cand_cap;
-    if (const int rc = reloc_grow(c, &r->c_d, &c0, ccap)) return rc;
-    if (const int rc = reloc_grow(c, &r->c_m, &c1, ccap)) return rc;
-    if (const int rc = reloc_grow(c, &r->c_p, &c2, ccap)) return rc;
-    r->cand_cap = ccap;
-  }
+  if (const int rc = s.grow(c, R::C_D, ccap * sizeof(int))) return rc;
+  if (const int rc = s.grow(c, R::C_M, ccap * sizeof(int))) return rc;
+  if (const int rc = s.grow(c, R::C_P, ccap * sizeof(double2))) return rc;
+  int *const wave_cnt = s.at<int>(R::WAVE_CNT), *const wave_off = s.at<int>(R::WAVE_OFF);
+  int *const c_d = s.at<int>(R::C_D), *const c_m = s.at<int>(R::C_M);
+  double2* const c_p = s.at<double2>(R::C_P);
   RelocGateArgs ga;
-  ga.m_xyh = r->m_xyh; ga.m_ax = r->m_ax; ga.m_lab = r->m_lab; ga.d_xyh = r->d_xyh; ga.d_ax = r->d_ax; ga.d_lab = r->d_lab;
-  ga.M = M; ga.D = D; ga.wpd = wpd; ga.wave_cnt = r->wave_cnt; ga.wave_off = r->wave_off;
-  ga.c_d = r->c_d; ga.c_m = r->c_m; ga.c_p = r->c_p; ga.cand_cap = (int)r->cand_cap; ga.g = g;
+  ga.m_xyh = s.at<double>(R::M_XYH); ga.m_ax = s.at<double>(R::M_AX); ga.m_lab = s.at<int>(R::M_LAB);
+  ga.d_xyh = d_xyh; ga.d_ax = d_ax; ga.d_lab = d_lab;
+  ga.M = M; ga.D = D; ga.wpd = wpd; ga.wave_cnt = wave_cnt; ga.wave_off = wave_off;
+  // the candidate lists' capacity in entries: the largest max_candidates so far, not this call's (the three lists grow together)
+  ga.c_d = c_d; ga.c_m = c_m; ga.c_p = c_p; ga.cand_cap = (int)(s.cap[R::C_D] / sizeof(int)); ga.g = g;
   const dim3 ggrid((M + 255) / 256, D);
   hipLaunchKernelGGL(k_reloc_gate<false>, ggrid, dim3(256), 0, c->stream, ga);
-  hipLaunchKernelGGL(k_reloc_scan, dim3(1), dim3(256), 0, c->stream, (const int*)r->wave_cnt, r->wave_off, (long long)nw, (int)D, wpd,
-                     r->row, r->counters, r->best);
+  hipLaunchKernelGGL(k_reloc_scan, dim3(1), dim3(256), 0, c->stream, (const int*)wave_cnt, wave_off, (long long)nw, (int)D, wpd,
+                     row, counters, best);
   ESL_HIP_TRY(hipGetLastError());
   unsigned long long* h_cnt = (unsigned long long*)(r->host + 6144);
-  ESL_HIP_TRY(hipMemcpyAsync(h_cnt, r->counters, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  ESL_HIP_TRY(hipMemcpyAsync(h_cnt, counters, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
   ESL_HIP_TRY(hipStreamSynchronize(c->stream));
   const unsigned long long P = h_cnt[2];
   out->n_candidates = (int32_t)std::min<unsigned long long>(P, 0x7fffffff);
@@ -593,26 +575,27 @@ extern "C" int esl_relocalize(esl_ctx* c, const double* det_objs, const int32_t*
   if (const char* e = std::getenv("ESL_RELOC_SLICE")) { const long long v = std::atoll(e); if (v >= 64) slice = (uint64_t)v; }
   const uint64_t n_pairs = reloc_pair_count(P);
   slice = std::min<uint64_t>(slice, n_pairs);
-  if (const int rc = reloc_grow(c, &r->surv, &r->surv_cap, (size_t)slice)) return rc;
+  if (const int rc = s.grow(c, R::SURV, (size_t)slice * sizeof(unsigned long long))) return rc;
+  unsigned long long* const surv = s.at<unsigned long long>(R::SURV);
   for (uint64_t t0 = 0; t0 < n_pairs; t0 += slice) {
     const uint64_t t1 = std::min<uint64_t>(t0 + slice, n_pairs);
-    hipLaunchKernelGGL(k_reloc_hyp_gate, dim3((unsigned)((t1 - t0 + 255) / 256)), dim3(256), 0, c->stream, (const int*)r->c_d,
-                       (const int*)r->c_m, (const double2*)r->c_p, (const double*)r->d_xyh, P, (unsigned long long)t0, (unsigned long long)t1,
-                       g.min_baseline, g.two_tol, r->surv, (unsigned long long)slice, r->counters);
+    hipLaunchKernelGGL(k_reloc_hyp_gate, dim3((unsigned)((t1 - t0 + 255) / 256)), dim3(256), 0, c->stream, (const int*)c_d,
+                       (const int*)c_m, (const double2*)c_p, (const double*)d_xyh, P, (unsigned long long)t0, (unsigned long long)t1,
+                       g.min_baseline, g.two_tol, surv, (unsigned long long)slice, counters);
     const int nb = (int)std::min<uint64_t>((t1 - t0 + 255) / 256, kRelocScoreBlocks);
-    hipLaunchKernelGGL(k_reloc_score, dim3(nb), dim3(256), 0, c->stream, (const int*)r->row, (const int*)r->c_d, (const double2*)r->c_p,
-                       (const double*)r->d_xyh, (int)D, P, (const unsigned long long*)r->surv, (unsigned long long)slice,
-                       (const unsigned long long*)r->counters, g.center_tol2, r->part);
-    hipLaunchKernelGGL(k_reloc_merge, dim3(1), dim3(256), 0, c->stream, (const RelocBest*)r->part, nb, r->best, r->counters,
+    hipLaunchKernelGGL(k_reloc_score, dim3(nb), dim3(256), 0, c->stream, (const int*)row, (const int*)c_d, (const double2*)c_p,
+                       (const double*)d_xyh, (int)D, P, (const unsigned long long*)surv, (unsigned long long)slice,
+                       (const unsigned long long*)counters, g.center_tol2, part);
+    hipLaunchKernelGGL(k_reloc_merge, dim3(1), dim3(256), 0, c->stream, (const RelocBest*)part, nb, best, counters,
                        (unsigned long long)slice);
   }
   RelocFinalArgs fa;
-  fa.row = r->row; fa.c_d = r->c_d; fa.c_m = r->c_m; fa.c_p = r->c_p; fa.d_xyh = r->d_xyh; fa.best = r->best; fa.counters = r->counters;
-  fa.D = D; fa.g = g; fa.out = r->out_dev;
+  fa.row = row; fa.c_d = c_d; fa.c_m = c_m; fa.c_p = c_p; fa.d_xyh = d_xyh; fa.best = best; fa.counters = counters;
+  fa.D = D; fa.g = g; fa.out = s.at<RelocOut>(R::OUT);
   hipLaunchKernelGGL(k_reloc_final, dim3(1), dim3(64), 0, c->stream, fa);
   ESL_HIP_TRY(hipGetLastError());
   RelocOut* ho = (RelocOut*)(r->host + 6144);
-  ESL_HIP_TRY(hipMemcpyAsync(ho, r->out_dev, sizeof(RelocOut), hipMemcpyDeviceToHost, c->stream));
+  ESL_HIP_TRY(hipMemcpyAsync(ho, fa.out, sizeof(RelocOut), hipMemcpyDeviceToHost, c->stream));
   ESL_HIP_TRY(hipStreamSynchronize(c->stream));
 
   out->status = ho->status; out->n_candidates = ho->n_candidates; out->n_hypotheses = ho->n_hypotheses;

@@ -42,13 +42,8 @@ struct RenderArgs {
   double* depth; int* inst; int* cover; int* cmp; int* flags;   // null: not asked for
 };
 
-struct RenderState {
-  static constexpr int kBufs = 9;
-  void* buf[kBufs] = {};
-  size_t cap[kBufs] = {};
-  long long n_allocs = 0;   // hipMalloc calls so far (esl_debug_render_allocs)
-};
-enum { RB_CAMS, RB_OBJS, RB_REC, RB_MEAS, RB_DEPTH, RB_INST, RB_COVER, RB_CMP, RB_FLAGS };
+enum { RB_CAMS, RB_OBJS, RB_REC, RB_MEAS, RB_DEPTH, RB_INST, RB_COVER, RB_CMP, RB_FLAGS, RB_COUNT };
+struct RenderState { ScratchSet<RB_COUNT> set; };
 
 static __global__ __launch_bounds__(kRenderThreads) void k_render_prep(RenderArgs a) {
   const long long i = (long long)blockIdx.x * kRenderThreads + threadIdx.x;
@@ -169,11 +164,13 @@ static __global__ __launch_bounds__(kRenderThreads) void k_render_tiles(RenderAr
   }
 }
 
+void render_scratch_stats(const esl_ctx* c, int64_t* allocs, int64_t* bytes) {
+  if (c->render) { *allocs = c->render->set.allocs(); *bytes = (int64_t)c->render->set.held(); }
+}
+
 void render_release(esl_ctx* c) {   // called by esl_ctx_destroy
-  RenderState* s = (RenderState*)c->render;
-  if (!s) return;
-  for (void* p : s->buf) if (p) (void)hipFree(p);
-  delete s;
+  if (c->render) c->render->set.release();
+  delete c->render;
   c->render = nullptr;
 }
 
@@ -182,17 +179,6 @@ void render_release(esl_ctx* c) {   // called by esl_ctx_destroy
 using namespace esl;
 
 namespace {
-
-int render_grow(esl_ctx* c, RenderState* s, int k, size_t bytes) {   // grow-only; contents are not kept
-  if (bytes <= s->cap[k] && s->buf[k]) return ESL_OK;
-  ESL_HIP_TRY(hipStreamSynchronize(c->stream));
-  if (s->buf[k]) (void)hipFree(s->buf[k]);
-  s->buf[k] = nullptr; s->cap[k] = 0;
-  ESL_HIP_TRY(hipMalloc(&s->buf[k], std::max<size_t>(bytes, 16)));
-  s->cap[k] = bytes;
-  ++s->n_allocs;
-  return ESL_OK;
-}
 
 int render_invalid(const char* what) {
   set_error(std::string("esl_render_map: ") + what);
@@ -207,13 +193,7 @@ extern "C" void esl_render_params_default(esl_render_params* p) {
 }
 
 extern "C" int esl_debug_render_allocs(esl_ctx* c, int64_t* allocs_out, int64_t* bytes_out) {
-  if (!c || !allocs_out || !bytes_out) { set_error("esl_debug_render_allocs: null pointer"); return ESL_ERR_INVALID; }
-  const RenderState* s = (const RenderState*)c->render;
-  *allocs_out = s ? s->n_allocs : 0;
-  size_t held = 0;
-  if (s) for (size_t b : s->cap) held += b;
-  *bytes_out = (int64_t)held;
-  return ESL_OK;
+  return esl_debug_scratch_allocs(c, ESL_SCRATCH_RENDER, allocs_out, bytes_out);
 }
 
 extern "C" int esl_render_map(esl_ctx* c, const double* cams, int32_t F, const double* objs, int32_t M, const double K[4], int32_t rows,
@@ -235,15 +215,7 @@ extern "C" int esl_render_map(esl_ctx* c, const double* cams, int32_t F, const d
   if (!std::isfinite(p.depth_tol) || p.depth_tol < 0) return render_invalid("depth_tol not finite or negative");
   if (p.depth_min > p.depth_max) return render_invalid("depth_min > depth_max");
   if (cmp_out && !depth_meas) return render_invalid("cmp_out needs depth_meas");
-  const bool res_cams = !cams && F > 0, res_objs = !objs && M > 0;
-  if (res_cams || res_objs) {
-    if (!c->graph_loaded || !c->states_loaded) {
-      set_error(std::string("esl_render_map: NULL ") + (res_cams ? "cams" : "objs") + " needs a resident graph with states");
-      return ESL_ERR_STATE;
-    }
-    if (res_cams && F != c->g.n_cams) return render_invalid("F differs from the resident graph's n_cams");
-    if (res_objs && M != c->g.n_objs) return render_invalid("M differs from the resident graph's n_objs");
-  }
+  if (const int rc = resident_source_check(c, "esl_render_map", !cams && F > 0, F, !objs && M > 0, M)) return rc;
   if (F == 0) return ESL_OK;
   if (!depth_out && !inst_out && !cover_out && !cmp_out && !flags_out) return ESL_OK;
   const size_t npix = (size_t)rows * cols, n_img = (size_t)F * npix, n_rec = (size_t)F * M;
@@ -254,46 +226,36 @@ extern "C" int esl_render_map(esl_ctx* c, const double* cams, int32_t F, const d
   }
   ESL_HIP_TRY(hipSetDevice(c->device));
   if (!c->render) c->render = new RenderState();
-  RenderState* s = (RenderState*)c->render;
+  ScratchSet<RB_COUNT>& s = c->render->set;
   RenderArgs k;
   std::memset(&k, 0, sizeof(k));
-  if (cams) {
-    if (const int rc = render_grow(c, s, RB_CAMS, (size_t)F * 7 * sizeof(double))) return rc;
-    ESL_HIP_TRY(hipMemcpyAsync(s->buf[RB_CAMS], cams, (size_t)F * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    k.cams = (const double*)s->buf[RB_CAMS];
-  } else k.cams = c->cams;
-  if (objs) {
-    if (const int rc = render_grow(c, s, RB_OBJS, (size_t)M * 10 * sizeof(double))) return rc;
-    ESL_HIP_TRY(hipMemcpyAsync(s->buf[RB_OBJS], objs, (size_t)M * 10 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    k.objs = (const double*)s->buf[RB_OBJS];
-  } else k.objs = c->objs;
-  if (const int rc = render_grow(c, s, RB_REC, n_rec * sizeof(RenderRec))) return rc;
-  k.rec = (RenderRec*)s->buf[RB_REC];
+  if (const int rc = source(c, s, RB_CAMS, cams, c->cams, (size_t)F * 7 * sizeof(double), &k.cams)) return rc;
+  if (const int rc = source(c, s, RB_OBJS, objs, c->objs, (size_t)M * 10 * sizeof(double), &k.objs)) return rc;
+  if (const int rc = s.grow(c, RB_REC, n_rec * sizeof(RenderRec))) return rc;
+  k.rec = s.at<RenderRec>(RB_REC);
   const bool tiles = depth_out || inst_out || cover_out || cmp_out;   // flags alone need the prepare kernel only
   if (cmp_out) {
-    if (const int rc = render_grow(c, s, RB_MEAS, n_img * sizeof(uint16_t))) return rc;
-    ESL_HIP_TRY(hipMemcpyAsync(s->buf[RB_MEAS], depth_meas, n_img * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
-    k.meas = (const unsigned short*)s->buf[RB_MEAS];
-    if (const int rc = render_grow(c, s, RB_CMP, n_rec * 4 * sizeof(int32_t))) return rc;
-    k.cmp = (int*)s->buf[RB_CMP];
+    if (const int rc = upload(c, s, RB_MEAS, depth_meas, n_img * sizeof(uint16_t), &k.meas)) return rc;
+    if (const int rc = s.grow(c, RB_CMP, n_rec * 4 * sizeof(int32_t))) return rc;
+    k.cmp = s.at<int>(RB_CMP);
     ESL_HIP_TRY(hipMemsetAsync(k.cmp, 0, n_rec * 4 * sizeof(int32_t), c->stream));
   }
   if (depth_out) {
-    if (const int rc = render_grow(c, s, RB_DEPTH, n_img * sizeof(double))) return rc;
-    k.depth = (double*)s->buf[RB_DEPTH];
+    if (const int rc = s.grow(c, RB_DEPTH, n_img * sizeof(double))) return rc;
+    k.depth = s.at<double>(RB_DEPTH);
   }
   if (inst_out) {
-    if (const int rc = render_grow(c, s, RB_INST, n_img * sizeof(int32_t))) return rc;
-    k.inst = (int*)s->buf[RB_INST];
+    if (const int rc = s.grow(c, RB_INST, n_img * sizeof(int32_t))) return rc;
+    k.inst = s.at<int>(RB_INST);
   }
   if (cover_out) {
-    if (const int rc = render_grow(c, s, RB_COVER, n_rec * 2 * sizeof(int32_t))) return rc;
-    k.cover = (int*)s->buf[RB_COVER];
+    if (const int rc = s.grow(c, RB_COVER, n_rec * 2 * sizeof(int32_t))) return rc;
+    k.cover = s.at<int>(RB_COVER);
     ESL_HIP_TRY(hipMemsetAsync(k.cover, 0, n_rec * 2 * sizeof(int32_t), c->stream));
   }
   if (flags_out) {
-    if (const int rc = render_grow(c, s, RB_FLAGS, n_rec * sizeof(int32_t))) return rc;
-    k.flags = (int*)s->buf[RB_FLAGS];
+    if (const int rc = s.grow(c, RB_FLAGS, n_rec * sizeof(int32_t))) return rc;
+    k.flags = s.at<int>(RB_FLAGS);
   }
   k.F = F; k.M = M; k.rows = rows; k.cols = cols;
   for (int i = 0; i < 4; ++i) k.K[i] = K[i];

@@ -973,16 +973,12 @@ static void anch_trial_chi2(esl_ctx* c) {
 static int slam_try_step_chain(esl_ctx* c, double lambda) {
   const DevGraph& g = c->g;
   const int N = g.n_objs, F = g.n_cams, nf = g.n_free_cams;
-  const size_t need = (size_t)nf * 192;
-  if (need > c->chain_ws_cap) {
-    if (c->chain_ws) { ESL_HIP_TRY(hipStreamSynchronize(c->stream)); (void)hipFree(c->chain_ws); c->chain_ws = nullptr; c->chain_ws_cap = 0; }
-    ESL_HIP_TRY(hipMalloc((void**)&c->chain_ws, need * sizeof(double)));
-    c->chain_ws_cap = need;
-  }
-  double* D[2] = {c->chain_ws, c->chain_ws + (size_t)nf * 36};
-  double* L[2] = {c->chain_ws + (size_t)nf * 72, c->chain_ws + (size_t)nf * 108};
-  double* Di = c->chain_ws + (size_t)nf * 144;
-  double* R[2] = {c->chain_ws + (size_t)nf * 180, c->chain_ws + (size_t)nf * 186};
+  if (const int rc = c->chain_ws.grow(c, 0, (size_t)nf * 192 * sizeof(double))) return rc;
+  double* const ws = c->chain_ws.at<double>(0);
+  double* D[2] = {ws, ws + (size_t)nf * 36};
+  double* L[2] = {ws + (size_t)nf * 72, ws + (size_t)nf * 108};
+  double* Di = ws + (size_t)nf * 144;
+  double* R[2] = {ws + (size_t)nf * 180, ws + (size_t)nf * 186};
   {
     ProfScope ps(c, 3);
     ESL_HIP_TRY(hipMemsetAsync(c->chol_info, 0, sizeof(int), c->stream));

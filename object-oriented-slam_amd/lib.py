@@ -28,7 +28,7 @@ EXPORTS = [
     "esl_assoc_params_default", "esl_predict_boxes", "esl_associate_boxes",
     "esl_init_robust_params_default", "esl_init_quadrics_robust",
     "esl_merge_params_default", "esl_map_overlaps", "esl_map_merge",
-    "esl_render_params_default", "esl_render_map", "esl_debug_render_allocs",
+    "esl_render_params_default", "esl_render_map", "esl_debug_render_allocs", "esl_debug_scratch_allocs",
 ]
 
 
@@ -719,6 +719,16 @@ class Context:
         self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
         _check(rc, "esl_render_map")
         return out
+
+    SCRATCH_OWNERS = ("reloc", "assoc", "merge", "render", "init_batch", "init_robust")   # esl_scratch_owner
+
+    def scratch_allocs(self, owner):
+        """esl_debug_scratch_allocs: (device allocations the owner's calls have made on this context, bytes its buffers hold);
+        owner: a name of SCRATCH_OWNERS or the enum's value"""
+        n, b = C.c_int64(0), C.c_int64(0)
+        k = self.SCRATCH_OWNERS.index(owner) if isinstance(owner, str) else int(owner)
+        _check(load().esl_debug_scratch_allocs(self._h, k, C.byref(n), C.byref(b)), "esl_debug_scratch_allocs")
+        return n.value, b.value
 
     def render_allocs(self):
         """esl_debug_render_allocs: (device allocations render_map has made on this context, bytes its buffers hold)"""
