@@ -743,6 +743,7 @@ static __global__ __launch_bounds__(kWave* kWavesPerBlock) void k_slam_backsub(
   const bool active = (g.bb_start[o + 1] > g.bb_start[o]) || (g.e3_start[o + 1] > g.e3_start[o]) || g.gr_cnt[o] > 0;
   if (!active) {
     if (lane == 0) { ell_store(e, objs_trial + 10 * o); part[o * 4 + 2] = 0; }
+    if (lane < 9) xo[(size_t)o * 9 + lane] = 0;   // x_o of an ellipsoid without an active edge (a fixed one) reads as zero, not as the last graph's step
     return;
   }
   double t[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
