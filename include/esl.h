@@ -52,7 +52,8 @@ extern "C" {
                              *    (esl_reloc_set_map, esl_relocalize), and 2-D data association against the projected map
                              *    (esl_predict_boxes, esl_associate_boxes), and the SVD initialisation of many ellipsoids in one call
                              *    (esl_init_quadrics) and its outlier-rejecting form (esl_init_quadrics_robust), and map maintenance
-                             *    (esl_map_overlaps, esl_map_merge), and the per-pixel rendering of a map (esl_render_map) */
+                             *    (esl_map_overlaps, esl_map_merge), and the per-pixel rendering of a map (esl_render_map), and the voxel-fused
+                             *    dense map of many RGB-D frames (esl_dense_begin / _add_frames / _info_get / _extract / _end) */
 #define ESL_MAX_TRACE 32
 
 typedef enum {
@@ -855,6 +856,74 @@ int esl_render_map(esl_ctx* ctx,
                    int32_t* cover_out /* F x M x 2 or NULL: pixels the object hits alone; pixels where it is the nearest */,
                    int32_t* cmp_out /* F x M x 4 or NULL, needs depth_meas: agree, nearer, farther, no data (over the pixels it wins) */,
                    int32_t* flags_out /* F x M or NULL: bit 0 drawn, bit 1 invalid, bit 2 camera inside, bit 3 bounded by its conic box */);
+
+/* ---- the dense map: voxel-fused points of many RGB-D frames (additive part of ABI 5: detect by the symbol) ---------------------------------
+ * The reference's dense builder (src/dense_builder/builder.cpp, Tracking.cpp:232-249) back-projects every depth pixel of every frame,
+ * moves it into the world with the frame's pose and voxel-filters the growing cloud at 1 cm, re-filtering already filtered centroids
+ * every frame: its result depends on the frame order and on float summation.  Here the map is stated the way esl_fit_frame states its
+ * voxel grid: every sample of every frame counts once, all sums are integers, the result is a function of the SET of samples alone.
+ * Everything is FP64 and integers; every reduction is an integer sum or a total order, so the map after any sequence of
+ * esl_dense_add_frames calls equals, bit for bit, the map after one call with all the frames, in any frame order, from run to run.
+ * Frames may differ in size and intrinsics from call to call.
+ *  1. Sample: pixel (col, row) of frame f with row and col multiples of stride (n_sampled).  r = the raw depth; r == 0 counts in n_zero.
+ *     z = r / depth_scale; z < depth_min or z > depth_max counts in n_depth_out.  p_c = ((col - cx) z / fx, (row - cy) z / fy, z):
+ *     multiply, then divide (builder.cpp:66-67), integer pixels as in esl_fit_frame and esl_render_map.
+ *  2. World point.  Poses are Tcw = (t, q), the graph's convention.  The quaternion is divided by its norm sqrt(x^2 + y^2 + z^2 + w^2)
+ *     (summed left to right), R is the rotation matrix by the library's formula (R00 = 1 - (2y y + 2z z), R01 = 2y x - 2z w, ...),
+ *     d = p_c - t, p_w[a] = (R[0][a] d0 + R[1][a] d1) + R[2][a] d2: p_w = R^T (p_c - t).  No product is contracted with a sum.  A
+ *     non-finite pose number, or a quaternion whose norm is 0 or not finite, gives ESL_ERR_INVALID before anything is added.
+ *  3. Key: k_a = floor(p_w[a] / leaf).  |k_a| > 2^20 - 1 on any axis (or not finite) counts in n_key_out and the sample is dropped;
+ *     the others count in n_used.  Packed key = (kx + 2^20) << 42 | (ky + 2^20) << 21 | (kz + 2^20): its unsigned order is the
+ *     lexicographic order of (kx, ky, kz).
+ *  4. Voxel: count; S_a = the sum of llrint(p_w[a] 2^30) as int64; with colour the sums of B, G and R.  n_samples may not reach 2^31:
+ *     a call whose sampled pixels (before the depth test) could take it there returns ESL_ERR_INVALID and adds nothing.  S_a itself
+ *     is exact while count * max |p_w[a]| of a voxel stays below 2^33 m (it wraps beyond).
+ *  5. Votes (with_inst): per (voxel, id >= 0) the number of samples.  A voxel's label is the id with the most samples, ties to the
+ *     lowest id; votes is that number; -1 / 0 without a labelled sample.
+ *  6. Capacity: the voxel table has the smallest power of two >= 2 max_voxels slots, the pair table twice that.  More than max_voxels
+ *     voxels, or more than 2 max_voxels pairs, sets the sticky status 3 -- a result, not an error: the return is ESL_OK.  From then on
+ *     the map is invalid until the next esl_dense_begin: esl_dense_add_frames adds nothing more (its counts are 0), esl_dense_extract
+ *     writes nothing and reports n_voxels = -1, esl_dense_info_get reports n_voxels = n_pairs = -1.  No probe loop is unbounded.
+ *  7. Extract: the voxels in ascending packed-key order, the first cap of them written, n_voxels reporting all.  key_out = (kx, ky, kz);
+ *     xyz_out[a] = (double)S_a / 2^30 / (double)count; bgr_out = (2 sum + count) / (2 count) in integers (0 on a map without colour);
+ *     inst_out / votes_out as step 5 (-1 / 0 on a map without labels).  Extract does not change the map; adds and extracts may alternate. */
+typedef struct {
+  double  leaf;         /* 0.01 m  (Tracking.cpp:241 voxelFilter(0.01)); finite, > 0 */
+  double  depth_scale;  /* 5000   raw units per metre; finite, > 0 */
+  double  depth_min;    /* 0.5    (builder.cpp:63) */
+  double  depth_max;    /* 6.0    (depth_thresh); finite, depth_min <= depth_max */
+  int32_t stride;       /* 1: every stride-th row and column from 0; >= 1 */
+  int32_t max_voxels;   /* 1048576: 1 .. 2^26 */
+} esl_dense_params;     /* 40 bytes; design choices except where a reference line is named */
+void esl_dense_params_default(esl_dense_params* p);
+
+/* Start an empty map (forgetting any earlier one of this context).  ESL_ERR_INVALID: null ctx, a bad parameter, a negative flag.  The
+ * tables take 72 bytes per slot, 24 more per slot with labels: 144 MiB / 192 MiB at the default max_voxels. */
+int esl_dense_begin(esl_ctx* ctx, const esl_dense_params* p /* NULL = defaults */, int32_t with_color, int32_t with_inst);
+
+typedef struct { int64_t n_sampled, n_zero, n_depth_out, n_key_out, n_used; int32_t status, pad; } esl_dense_add_result; /* 48 bytes */
+/* ESL_ERR_STATE: no esl_dense_begin before; bgr or inst NULL when esl_dense_begin asked for them (passing them when it did not is
+ * allowed: they are not read); cams == NULL without a resident graph and states.  ESL_ERR_INVALID: null ctx, K or depth, negative F,
+ * rows or cols < 1 or > 16384, fx or fy not finite or <= 0, an invalid pose (step 2), n_samples reaching 2^31 (step 4), F differing
+ * from the resident graph's n_cams when cams == NULL.  F = 0 is valid.  An error leaves the map as it was. */
+int esl_dense_add_frames(esl_ctx* ctx, const double* cams /* F x 7 Tcw, NULL = resident camera states */, int32_t F,
+                         const double K[4], int32_t rows, int32_t cols,
+                         const uint16_t* depth /* F x rows x cols */, const uint8_t* bgr /* F x rows x cols x 3 or NULL */,
+                         const int32_t* inst /* F x rows x cols or NULL: esl_render_map's inst_out or any labelling, < 0 = none */,
+                         esl_dense_add_result* out /* this call's counts; may be NULL */);
+
+typedef struct { int64_t n_samples; int32_t n_voxels, n_pairs, status, with_color, with_inst, pad; } esl_dense_info; /* 32 bytes */
+int esl_dense_info_get(esl_ctx* ctx, esl_dense_info* out);
+
+/* ESL_ERR_INVALID: null ctx or n_voxels, negative cap.  ESL_ERR_STATE: no esl_dense_begin before.  Any output may be NULL. */
+int esl_dense_extract(esl_ctx* ctx, int64_t cap, int32_t* key_out /* cap x 3 */, double* xyz_out /* cap x 3 */, int32_t* count_out /* cap */,
+                      uint8_t* bgr_out /* cap x 3 */, int32_t* inst_out /* cap */, int32_t* votes_out /* cap */, int64_t* n_voxels);
+int esl_dense_end(esl_ctx* ctx);   /* forget the map; the buffers stay (grow-only), esl_ctx_destroy frees them */
+/* The calls leave the resident graph, its states and the solver blobs alone, keep grow-only device buffers of their own (a warm call
+ * allocates nothing), run on this context's GPU only and issue no collective.  With esl_profile_enable(ctx, 2) their launches are
+ * bracketed as kernel class 4.  esl_debug_dense_allocs: the device allocations these calls have made on this context and the bytes
+ * their buffers hold (the owner has no value in esl_scratch_owner). */
+int esl_debug_dense_allocs(esl_ctx* ctx, int64_t* allocs_out, int64_t* bytes_out);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------*/
 /* Dense FP64-MFMA Cholesky factor + solve (the reduced-camera solver of SLAM mode) on a procedurally generated,

@@ -237,6 +237,57 @@ def render_argtypes(L):
     L.esl_render_map.restype = C.c_int
 
 
+class EslDenseParams(C.Structure):
+    """esl_dense_params: the voxel grid and the depth gate of the dense map (esl_dense_begin)."""
+    _fields_ = [("leaf", C.c_double), ("depth_scale", C.c_double), ("depth_min", C.c_double), ("depth_max", C.c_double),
+                ("stride", C.c_int32), ("max_voxels", C.c_int32)]
+
+
+class EslDenseAddResult(C.Structure):
+    """esl_dense_add_result: one esl_dense_add_frames call's counts; status 3 = the map went over its capacity."""
+    _fields_ = [("n_sampled", C.c_int64), ("n_zero", C.c_int64), ("n_depth_out", C.c_int64), ("n_key_out", C.c_int64),
+                ("n_used", C.c_int64), ("status", C.c_int32), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
+
+
+class EslDenseInfo(C.Structure):
+    """esl_dense_info: the dense map so far."""
+    _fields_ = [("n_samples", C.c_int64), ("n_voxels", C.c_int32), ("n_pairs", C.c_int32), ("status", C.c_int32),
+                ("with_color", C.c_int32), ("with_inst", C.c_int32), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
+
+
+def default_dense_params(**kw):
+    """esl_dense_params_default: the reference's 1 cm leaf and depth gate; stride and max_voxels are design choices (include/esl.h)."""
+    p = EslDenseParams(leaf=0.01, depth_scale=5000.0, depth_min=0.5, depth_max=6.0, stride=1, max_voxels=1048576)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def dense_argtypes(L):
+    """the esl_dense_* calls take nullable pointers: declared, so that None passes as NULL and a wrong type raises"""
+    dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    L.esl_dense_params_default.argtypes = [C.POINTER(EslDenseParams)]
+    L.esl_dense_params_default.restype = None
+    L.esl_dense_begin.argtypes = [C.c_void_p, C.POINTER(EslDenseParams), C.c_int32, C.c_int32]
+    L.esl_dense_add_frames.argtypes = [C.c_void_p, dp, C.c_int32, dp, C.c_int32, C.c_int32, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8),
+                                       ip, C.POINTER(EslDenseAddResult)]
+    L.esl_dense_info_get.argtypes = [C.c_void_p, C.POINTER(EslDenseInfo)]
+    L.esl_dense_extract.argtypes = [C.c_void_p, C.c_int64, ip, dp, ip, C.POINTER(C.c_uint8), ip, ip, lp]
+    L.esl_dense_end.argtypes = [C.c_void_p]
+    L.esl_debug_dense_allocs.argtypes = [C.c_void_p, lp, lp]
+    for f in (L.esl_dense_begin, L.esl_dense_add_frames, L.esl_dense_info_get, L.esl_dense_extract, L.esl_dense_end,
+              L.esl_debug_dense_allocs):
+        f.restype = C.c_int
+
+
 ROBUST_KINDS = {"none": 0, "huber": 1, "pseudo_huber": 2, "cauchy": 3, "tukey": 4}   # esl_robust_kind (include/esl.h)
 EDGE_CLASSES = {"bbox": 0, "e3d": 1, "grav": 2, "odom": 3}                         # esl_edge_class
 

@@ -182,6 +182,7 @@ int esl_ctx_destroy(esl_ctx* c) {
   assoc_release(c);
   merge_release(c);
   render_release(c);
+  dense_release(c);
   init_batch_release(c);
   for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
   if (c->host_part) (void)hipHostFree(c->host_part);

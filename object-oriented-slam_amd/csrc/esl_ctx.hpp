@@ -109,7 +109,7 @@ inline void robust_dispatch(bool on, F&& f) {
 
 struct HostImage;   // esl_graph.hip
 // the map-side calls' buffers, each defined by the translation unit named after it (InitBatchState: esl_init.hip)
-struct RelocState; struct AssocState; struct MergeState; struct RenderState; struct InitBatchState;
+struct RelocState; struct AssocState; struct MergeState; struct RenderState; struct InitBatchState; struct DenseState;
 struct LmState {
   bool begun = false;
   esl_lm_params p;
@@ -140,6 +140,7 @@ void reloc_release(esl_ctx* c);   // esl_reloc.hip
 void assoc_release(esl_ctx* c);   // esl_assoc.hip
 void merge_release(esl_ctx* c);   // esl_merge.hip
 void render_release(esl_ctx* c);  // esl_render.hip
+void dense_release(esl_ctx* c);   // esl_dense.hip
 void init_batch_release(esl_ctx* c);   // esl_init.hip
 // esl_debug_scratch_allocs: each owner's counters, written only when its state exists
 void reloc_scratch_stats(const esl_ctx* c, int64_t* allocs, int64_t* bytes);
@@ -147,6 +148,7 @@ void assoc_scratch_stats(const esl_ctx* c, int64_t* allocs, int64_t* bytes);
 void merge_scratch_stats(const esl_ctx* c, int64_t* allocs, int64_t* bytes);
 void render_scratch_stats(const esl_ctx* c, int64_t* allocs, int64_t* bytes);
 void init_scratch_stats(const esl_ctx* c, bool robust, int64_t* allocs, int64_t* bytes);
+void dense_scratch_stats(const esl_ctx* c, int64_t* allocs, int64_t* bytes);   // esl_debug_dense_allocs: no esl_scratch_owner of its own
 // all-gather the 8-double dev_scal block of every rank into c->dev_gather (device), ordered on the context's stream
 int comm_gather_scalars_device(esl_ctx* c);
 // SLAM mode: in-place sum over ranks of a device buffer (RCCL all-reduce); no-op without a communicator
@@ -247,6 +249,7 @@ struct esl_ctx {
   esl::AssocState* assoc = nullptr;                               // esl_predict_boxes / esl_associate_boxes: their buffers (esl_assoc.hip AssocState)
   esl::MergeState* merge = nullptr;                               // esl_map_overlaps / esl_map_merge: their buffers (esl_merge.hip MergeState)
   esl::RenderState* render = nullptr;                             // esl_render_map: its buffers (esl_render.hip RenderState)
+  esl::DenseState* dense = nullptr;                               // esl_dense_*: the map's tables and the calls' buffers (esl_dense.hip DenseState)
   esl::InitBatchState* init_batch = nullptr;                     // esl_init_quadrics: its buffers (esl_init.hip InitBatchState)
   void* fit_graph_cache = nullptr;                         // captured launch sequences (std::vector<FitGraphEntry>)
   bool parts_fresh = false;      // host_part holds the last trial's scalars already (slam_try_step fetched them with the solver's flag)

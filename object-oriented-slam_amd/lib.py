@@ -29,6 +29,8 @@ EXPORTS = [
     "esl_init_robust_params_default", "esl_init_quadrics_robust",
     "esl_merge_params_default", "esl_map_overlaps", "esl_map_merge",
     "esl_render_params_default", "esl_render_map", "esl_debug_render_allocs", "esl_debug_scratch_allocs",
+    "esl_dense_params_default", "esl_dense_begin", "esl_dense_add_frames", "esl_dense_info_get", "esl_dense_extract", "esl_dense_end",
+    "esl_debug_dense_allocs",
 ]
 
 
@@ -55,6 +57,7 @@ def load():
             if not hasattr(L, name):
                 raise EslError(f"libesl_hip.so does not export {name}")
         abi.render_argtypes(L)
+        abi.dense_argtypes(L)
         _lib = L
     return _lib
 
@@ -734,6 +737,86 @@ class Context:
         """esl_debug_render_allocs: (device allocations render_map has made on this context, bytes its buffers hold)"""
         n, b = C.c_int64(0), C.c_int64(0)
         _check(load().esl_debug_render_allocs(self._h, C.byref(n), C.byref(b)), "esl_debug_render_allocs")
+        return n.value, b.value
+
+    # ---- the dense map ---------------------------------------------------------------------------
+    DENSE_OUTPUTS = ("key", "xyz", "count", "bgr", "inst", "votes")
+
+    def dense_begin(self, params=None, with_color=True, with_inst=True):
+        """esl_dense_begin: start an empty voxel-fused map on this context (params: abi.default_dense_params(...))"""
+        p = params if params is not None else abi.default_dense_params()
+        _check(load().esl_dense_begin(self._h, C.byref(p), int(bool(with_color)), int(bool(with_inst))), "esl_dense_begin")
+
+    def dense_add_frames(self, cams, K, rows, cols, depth, bgr=None, inst=None):
+        """esl_dense_add_frames: add F frames.  cams (F, 7) Tcw or None for the resident camera states; depth (F, rows, cols) uint16,
+        bgr (F, rows, cols, 3) uint8, inst (F, rows, cols) int32 (< 0 = unlabelled).  Returns the call's counts as a dict."""
+        rows, cols = int(rows), int(cols)
+        if cams is None:
+            F, cp = self.graph_sizes()["n_cams"], None
+        else:
+            cams = np.ascontiguousarray(cams, dtype=np.float64).reshape(-1, 7)
+            F, cp = len(cams), (cams.ctypes.data_as(_dp) if len(cams) else None)
+
+        def img(a, dt, t, tail=()):
+            if a is None:
+                return None, None
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.shape != (F, rows, cols) + tail:
+                raise ValueError(f"an image array has shape {a.shape}, expected {(F, rows, cols) + tail}")
+            return a, a.ctypes.data_as(t)
+        depth, dptr = img(depth, np.uint16, C.POINTER(C.c_uint16))
+        bgr, bptr = img(bgr, np.uint8, C.POINTER(C.c_uint8), (3,))
+        inst, iptr = img(inst, np.int32, C.POINTER(C.c_int32))
+        Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(4)
+        res = abi.EslDenseAddResult()
+        t0 = time.perf_counter()
+        rc = load().esl_dense_add_frames(self._h, cp, F, Kc.ctypes.data_as(_dp), rows, cols, dptr, bptr, iptr, C.byref(res))
+        self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
+        _check(rc, "esl_dense_add_frames")
+        return res.as_dict()
+
+    def dense_info(self):
+        """esl_dense_info_get as a dict: n_samples, n_voxels, n_pairs, status, with_color, with_inst"""
+        info = abi.EslDenseInfo()
+        _check(load().esl_dense_info_get(self._h, C.byref(info)), "esl_dense_info_get")
+        return info.as_dict()
+
+    def dense_extract(self, cap=None, want=DENSE_OUTPUTS):
+        """esl_dense_extract: the voxels in ascending packed-key order.  cap None = all of them.  Returns a dict: n_voxels (all of the
+        map's, -1 when the map went over its capacity) and, per name of `want`, the first min(cap, n_voxels) rows: key (n, 3) int32,
+        xyz (n, 3) float64, count (n,) int32, bgr (n, 3) uint8, inst (n,) int32, votes (n,) int32."""
+        unknown = set(want) - set(self.DENSE_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        if cap is None:
+            cap = max(self.dense_info()["n_voxels"], 0)
+        cap = int(cap)
+        shapes = dict(key=((cap, 3), np.int32), xyz=((cap, 3), np.float64), count=((cap,), np.int32), bgr=((cap, 3), np.uint8),
+                      inst=((cap,), np.int32), votes=((cap,), np.int32))
+        types = dict(key=C.c_int32, xyz=C.c_double, count=C.c_int32, bgr=C.c_uint8, inst=C.c_int32, votes=C.c_int32)
+        out = {k: np.zeros(*shapes[k]) for k in self.DENSE_OUTPUTS if k in want}
+
+        def optr(k):
+            return out[k].ctypes.data_as(C.POINTER(types[k])) if k in out else None
+        n = C.c_int64(0)
+        t0 = time.perf_counter()
+        rc = load().esl_dense_extract(self._h, cap, optr("key"), optr("xyz"), optr("count"), optr("bgr"), optr("inst"), optr("votes"),
+                                      C.byref(n))
+        self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
+        _check(rc, "esl_dense_extract")
+        m = min(cap, max(n.value, 0))
+        res = {k: v[:m] for k, v in out.items()}
+        res["n_voxels"] = int(n.value)
+        return res
+
+    def dense_end(self):
+        """esl_dense_end: forget the map (the buffers stay with the context)"""
+        _check(load().esl_dense_end(self._h), "esl_dense_end")
+
+    def dense_allocs(self):
+        """esl_debug_dense_allocs: (device allocations the dense calls have made on this context, bytes their buffers hold)"""
+        n, b = C.c_int64(0), C.c_int64(0)
+        _check(load().esl_debug_dense_allocs(self._h, C.byref(n), C.byref(b)), "esl_debug_dense_allocs")
         return n.value, b.value
 
     def selftest_cholesky(self, n):

@@ -1,0 +1,91 @@
+// A stand-alone program over csrc/esl_dense_key.hpp (the host side of the header the kernels of esl_dense.hip compile too).
+//   no argument: self-checks of the key packing, the range test, the key order, the fixed-point conversion and the colour rounding;
+//                exit status 0 when all hold.
+//   "samples":   reads from stdin  leaf depth_scale depth_min depth_max  then  K(4)  then  n  and n lines  cam(7) raw col row ;
+//                prints per line  category packed_key fix_x fix_y fix_z  (zeros unless the sample is used): the CPU test compares them
+//                with the numpy statement.
+// Built and run by tests/test_dense_ref.py, also under -fsanitize=address,undefined.  Compile with -ffp-contract=off.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "../object-oriented-slam_amd/csrc/esl_dense_key.hpp"
+
+using namespace esl;
+
+static int fails = 0;
+#define CHECK(c) do { if (!(c)) { std::printf("FAILED line %d: %s\n", __LINE__, #c); ++fails; } } while (0)
+
+static void self_checks() {
+  const int edge[] = {-kDenseKeyMax, -kDenseKeyMax + 1, -2, -1, 0, 1, 2, kDenseKeyMax - 1, kDenseKeyMax};
+  const int n = (int)(sizeof(edge) / sizeof(edge[0]));
+  unsigned long long prev = 0;
+  bool first = true;
+  for (int a = 0; a < n; ++a) for (int b = 0; b < n; ++b) for (int c = 0; c < n; ++c) {   // ascending lexicographic order
+    const unsigned long long key = dense_pack(edge[a], edge[b], edge[c]);
+    int k[3];
+    dense_unpack(key, k);
+    CHECK(k[0] == edge[a] && k[1] == edge[b] && k[2] == edge[c]);
+    CHECK(key != kDenseEmpty && (key >> 63) == 0);
+    CHECK(dense_key_in_range(edge[a], edge[b], edge[c]));
+    if (!first) CHECK(key > prev);
+    prev = key; first = false;
+  }
+  CHECK(!dense_key_in_range(1 << 20, 0, 0) && !dense_key_in_range(0, -(1 << 20), 0) && !dense_key_in_range(0, 0, 1 << 20));
+  CHECK(dense_key_in_range(kDenseKeyMax, -kDenseKeyMax, 0));
+  {   // the range test on computed keys: leaf 1, the coordinate decides
+    int k[3];
+    const double in[3] = {1048575.5, -1048575.0, -0.25}, hi[3] = {1048576.0, 0, 0}, lo[3] = {0, -1048575.5, 0}, nan[3] = {0, std::nan(""), 0},
+                 inf[3] = {0, 0, -HUGE_VAL};
+    CHECK(dense_key(in, 1.0, k) && k[0] == 1048575 && k[1] == -1048575 && k[2] == -1);   // floor, not truncation
+    CHECK(!dense_key(hi, 1.0, k)); CHECK(!dense_key(lo, 1.0, k)); CHECK(!dense_key(nan, 1.0, k)); CHECK(!dense_key(inf, 1.0, k));
+  }
+  // fixed point: round to nearest, negative values included; 2^-31 is half a unit: ties go to even
+  CHECK(dense_fix(1.0) == (1ll << 30) && dense_fix(-1.0) == -(1ll << 30) && dense_fix(0.0) == 0);
+  CHECK(dense_fix(-0.75 / kDenseFix) == -1 && dense_fix(-0.25 / kDenseFix) == 0 && dense_fix(0.75 / kDenseFix) == 1);
+  CHECK(dense_fix(-1.5 / kDenseFix) == -2 && dense_fix(-2.5 / kDenseFix) == -2 && dense_fix(2.5 / kDenseFix) == 2);
+  CHECK(dense_fix(-2.0000000004) == -2147483648ll - 0);   // -2.0000000004 * 2^30 = -2147483648.43: rounds to -2147483648
+  CHECK(dense_mean(-3 * (1ll << 30), 2) == -1.5 && dense_mean(5, 1) == 5.0 / kDenseFix);
+  // colour: (2 sum + count) / (2 count): halves round up
+  CHECK(dense_color(3, 2) == 2 && dense_color(255, 1) == 255 && dense_color(0, 7) == 0 && dense_color(10, 4) == 3 && dense_color(9, 4) == 2);
+  CHECK(dense_color(255ull * 2147483647ull, 2147483647ull) == 255);
+  {   // poses
+    double P[kDensePose];
+    const double id[7] = {1, 2, 3, 0, 0, 0, 2.0}, zero[7] = {0, 0, 0, 0, 0, 0, 0}, bad[7] = {0, std::nan(""), 0, 0, 0, 0, 1};
+    CHECK(dense_pose(id, P) && P[0] == 1 && P[4] == 1 && P[8] == 1 && P[1] == 0 && P[9] == 1 && P[11] == 3);
+    CHECK(!dense_pose(zero, P)); CHECK(!dense_pose(bad, P));
+    const double huge[7] = {0, 0, 0, 1e200, 1e200, 0, 0};   // the norm overflows
+    CHECK(!dense_pose(huge, P));
+  }
+}
+
+static int samples() {
+  double leaf, scale, dmin, dmax, K[4];
+  int n;
+  if (std::scanf("%lf %lf %lf %lf %lf %lf %lf %lf %d", &leaf, &scale, &dmin, &dmax, &K[0], &K[1], &K[2], &K[3], &n) != 9) return 2;
+  for (int i = 0; i < n; ++i) {
+    double cam[7], P[kDensePose], pc[3], pw[3];
+    unsigned raw; int col, row, k[3];
+    for (int j = 0; j < 7; ++j) if (std::scanf("%lf", &cam[j]) != 1) return 2;
+    if (std::scanf("%u %d %d", &raw, &col, &row) != 3) return 2;
+    if (!dense_pose(cam, P)) { std::printf("-1 0 0 0 0\n"); continue; }
+    int cat = dense_sample(raw, col, row, K, scale, dmin, dmax, pc);
+    unsigned long long key = 0;
+    long long fx[3] = {0, 0, 0};
+    if (cat == DENSE_USED) {
+      dense_world(P, pc, pw);
+      if (dense_key(pw, leaf, k)) { key = dense_pack(k[0], k[1], k[2]); for (int a = 0; a < 3; ++a) fx[a] = dense_fix(pw[a]); }
+      else cat = DENSE_KEY_OUT;
+    }
+    std::printf("%d %llu %lld %lld %lld\n", cat, key, fx[0], fx[1], fx[2]);
+  }
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && !std::strcmp(argv[1], "samples")) return samples();
+  self_checks();
+  if (fails) return 1;
+  std::printf("dense_key ok\n");
+  return 0;
+}
