@@ -361,9 +361,12 @@ int esl_lm_commit(esl_ctx* ctx, int accept);
  * 0 before any SLAM-mode step */
 int esl_lm_solver_used(esl_ctx* ctx, int32_t* solver_out);
 /* shape of the camera-first elimination of the resident graph as the last trial step ran it (zeros when it did not):
- * stats[0] form of X: 0 dense rows, 1 sparse with stored per-segment products, 2 sparse, blocks of T straight from the slabs;
- * [1] dissection stride (0: plain chain), [2] separators, [3] segments, [4] flops of the per-segment products (lower block triangles, rows from a block row's first camera on),
- * [5] bytes of the stored products, [6] bytes of the compact slabs, [7] rows of the dense MFMA update (K, padded),
+ * stats[0] form of X: 0 dense rows, 1 sparse with stored per-segment products, 2 sparse, blocks of T straight from the slabs,
+ *     3 sparse, T's interior part assembled one-sided from the V records and the back-swept slabs Y (no product store; the form a
+ *     single rank runs when ESL_CF_SPARSE is unset);
+ * [1] dissection stride (0: plain chain), [2] separators, [3] segments, [4] flops of the per-segment products (lower block triangles, rows from a block row's first camera on;
+ *     form 3: of the assembly's 9 x 6 . 6 x 9 record products),
+ * [5] bytes of the stored products (form 3: of Y), [6] bytes of the compact slabs, [7] rows of the dense MFMA update (K, padded),
  * [8] flops that update executes when T's ellipsoids are ordered by first camera and the structurally zero rows above the
  *     staircase are skipped tile by tile (0: the closed form n (n + 1) K applies), [9] 1 if T is in that order. */
 #define ESL_SOLVER_STATS 10

@@ -1040,6 +1040,228 @@ static __global__ __launch_bounds__(256) void k_cf_T_gather(int N, int nw, const
   }
 }
 
+// ---- one-sided assembly of the interior part (form 3): no stored products --------------------------------------------------------------
+// For segment p with interior camera block G_p = L_p L_p^T and X = L_p^-1 W:
+//     X(:, o1)^T X(:, o2) = W(:, o1)^T (L_p^-T X(:, o2)) = sum over the list entries k of o1 at interior slots of p of W_k^T Z_slot(k)(o2),
+// Z = L_p^-T X.  W(:, o1) is non-zero only at the cameras with an edge to o1 (C4: 1.1 - 1.4 entries per live (ellipsoid, segment)),
+// and with Y_i = L_ii^T Z_i the records V_k = L_ii^-1 W_k that k_cf_edge_scale writes serve as they are: W_k^T Z_i = V_k^T Y_i.
+//   k_cf_seg_back    behind k_cf_forward<2>, same work list (segment, 64 compact columns), lane = column: the segment's own backward
+//                    sweep Y_i = X_i - G_i Z_{i+1}, Z_i = L_ii^-T Y_i from the last interior slot down (the coupling of the last slot to
+//                    the separator is not part of L_p).  One 432-byte record per (compact ellipsoid, interior slot), [b][a] like V:
+//                    Y[((seg_start[p] + i) 15 + pos) 54 + 6 b + a]; the right-hand side's column to Yr[6 slot + a].
+//   k_cf_T_onesided  ownership and order of k_cf_T_gather (one wave per block of T, lower triangle + the b row, the segments two
+//                    ellipsoids share, ascending); per segment o1's entries in list order, each a 9 x 6 . 6 x 9 product on
+//                    v_mfma_f64_16x16x4 with the block's pairs concatenated along K (zero padded to a multiple of four at the
+//                    block's end).  The b row walks o2's entries against Yr.  No atomics.
+constexpr int kCfSegInt = kCfFwdCh - 1;   // interior slots of a segment
+static __global__ __launch_bounds__(64) void k_cf_seg_back(int nf_all, const int* __restrict__ fwork, const int* __restrict__ seg_start,
+                                                           const long long* __restrict__ xoff, const int* __restrict__ xld,
+                                                           const double* __restrict__ Xc, const double* __restrict__ Linv,
+                                                           const double* __restrict__ Gfac, double* __restrict__ Y, double* __restrict__ Yr) {
+  __shared__ double sLi[kCfSegInt * 36], sG[kCfSegInt * 36];
+  const int lane = threadIdx.x;
+  const int p = fwork[2 * blockIdx.x], j = fwork[2 * blockIdx.x + 1] * 64 + lane;
+  const int ob = seg_start[p], m = 9 * (seg_start[p + 1] - ob);   // column m = the right-hand side
+  const int beg = p * kCfFwdCh;
+  const int len = (beg + kCfSegInt < nf_all ? beg + kCfSegInt : nf_all) - beg;
+  if (len <= 0) return;
+  {   // the segment's L_ii^-1 and G_i -> LDS (fixed trip count, clamped addresses: the loads go out together)
+    constexpr int kQ = (kCfSegInt * 36 + 63) / 64;
+    double tl[kQ], tg[kQ];
+#pragma unroll
+    for (int q = 0; q < kQ; ++q) {
+      const int idx = q * 64 + lane, cl = idx < len * 36 ? idx : 0;
+      tl[q] = Linv[(size_t)beg * 36 + cl]; tg[q] = Gfac[(size_t)beg * 36 + cl];
+    }
+#pragma unroll
+    for (int q = 0; q < kQ; ++q) if (q * 64 + lane < kCfSegInt * 36) { sLi[q * 64 + lane] = tl[q]; sG[q * 64 + lane] = tg[q]; }
+  }
+  const bool on = j <= m, rhs = j == m;
+  const size_t ld = (size_t)xld[p];
+  const double* X = Xc + (size_t)xoff[p] + (on ? j : 0);
+  double x[kCfSegInt * 6];   // the lane's column of the slab: all loads in flight together
+#pragma unroll
+  for (int q = 0; q < kCfSegInt * 6; ++q) x[q] = X[(size_t)(q < len * 6 ? q : 0) * ld];
+  __builtin_amdgcn_wave_barrier();
+  const int oi = rhs ? 0 : (on ? j / 9 : 0), b = on ? j - 9 * oi : 0;
+  double* dst = rhs ? Yr + (size_t)beg * 6 : Y + ((size_t)(ob + oi) * kCfSegInt) * 54 + b * 6;
+  const int dstep = rhs ? 6 : 54;
+  double z[6] = {0, 0, 0, 0, 0, 0};   // Z of the slot behind (nothing behind the last interior slot)
+#pragma unroll
+  for (int ii = kCfSegInt - 1; ii >= 0; --ii) {
+    if (ii >= len) continue;
+    double y[6];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+      double t = x[ii * 6 + a];
+#pragma unroll
+      for (int q = 0; q < 6; ++q) t -= sG[ii * 36 + a * 6 + q] * z[q];
+      y[a] = t;
+    }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+      double t = 0;
+#pragma unroll
+      for (int q = a; q < 6; ++q) t += sLi[ii * 36 + q * 6 + a] * y[q];
+      z[a] = t;
+    }
+    if (on) {
+#pragma unroll
+      for (int a = 0; a < 6; ++a) dst[(size_t)ii * dstep + a] = y[a];
+    }
+  }
+}
+
+// The pair list of a layout: which records a block of T multiplies does not change from trial to trial, so the lookups -- the AND of
+// the two segment bitmaps, the column map, the entry range of (o1, segment), the slot of every entry -- run once per layout
+// (k_cf_os_list, first counting then filling; the host turns the counts into offsets in between).  Block b = t1 (t1 + 1) / 2 + t2 of
+// the lower triangle (T's order), N (N + 1) / 2 + t2 for the b row; its pairs in the order they are added: shared segments
+// ascending, o1's entries of the segment in list order, entries of the separator's slot left out.
+// pair = (record of the A operand, record of the B operand): (list entry of o1, Y record of o2) -- b row: (slot, list entry of o2).
+template <bool FILL>
+static __global__ __launch_bounds__(256) void k_cf_os_list(int N, int nw, int n_chunks, const unsigned long long* __restrict__ mask,
+                                                           const int* __restrict__ cmap, const int* __restrict__ seg_start,
+                                                           const int* __restrict__ oe_cst, const int* __restrict__ oe_slot,
+                                                           const int* __restrict__ unrank, const long long* __restrict__ bstart,
+                                                           int* __restrict__ bcnt, int2* __restrict__ pairs) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int t1 = blockIdx.x;
+  const int o1 = (t1 == N || !unrank) ? t1 : unrank[t1];
+  const int N1 = N + 1;
+  const bool rhs = o1 == N;
+  for (int q = wave; q < kCfTPer; q += 4) {
+    const int t2 = (int)blockIdx.y * kCfTPer + q;
+    if (t2 > t1 || t2 >= N) continue;
+    const int o2 = unrank ? unrank[t2] : t2;
+    const long b = rhs ? (long)N * (N + 1) / 2 + t2 : (long)t1 * (t1 + 1) / 2 + t2;
+    const int* cst = oe_cst + (size_t)(rhs ? o2 : o1) * (n_chunks + 1);   // the ellipsoid whose list entries are walked
+    const long long w0 = FILL ? bstart[b] : 0;
+    int cnt = 0;
+    for (int wd = 0; wd < nw; ++wd) {
+      unsigned long long mk = mask[(size_t)o1 * nw + wd] & mask[(size_t)o2 * nw + wd];
+      if (!mk) continue;
+      // lane = bit: entry range and first Y record of all 64 segments of this word in one round trip
+      const int pl = wd * 64 + lane;
+      const bool mine = (mk >> lane) & 1ull;
+      const int kal = mine ? cst[pl] : 0, kbl = mine ? cst[pl + 1] : 0;
+      const int yrl = (mine && !rhs) ? (seg_start[pl] + (cmap[(size_t)pl * N1 + o2] & 0xFFFFFF)) * kCfSegInt : 0;
+      while (mk) {
+        const int bit = __builtin_ctzll(mk);
+        mk &= mk - 1;
+        const int p = wd * 64 + bit;
+        const int ka = __builtin_amdgcn_readlane(kal, bit), kb = __builtin_amdgcn_readlane(kbl, bit), yr = __builtin_amdgcn_readlane(yrl, bit);
+        for (int k0 = ka; k0 < kb; k0 += 64) {   // lane = entry: the prefix count keeps the list order
+          const int ent = k0 + lane;
+          const int pos = ent < kb ? oe_slot[ent] - p * kCfFwdCh : kCfFwdCh - 1;
+          const bool valid = pos != kCfFwdCh - 1;   // (the separator's entries are not the assembly's)
+          const unsigned long long vb = __ballot(valid);
+          if (FILL && valid) {
+            const int at = cnt + __builtin_popcountll(vb & ((1ull << lane) - 1ull));
+            pairs[w0 + at] = rhs ? make_int2(p * kCfFwdCh + pos, ent) : make_int2(ent, yr + pos);
+          }
+          cnt += __builtin_popcountll(vb);
+        }
+      }
+    }
+    if (!FILL && lane == 0) bcnt[b] = cnt;
+  }
+}
+
+constexpr int kCfOsBatch = 12;   // K-steps (of four rows) in flight: eight pairs
+static __global__ __launch_bounds__(256) void k_cf_T_onesided(int N, const int2* __restrict__ pairs, const long long* __restrict__ bstart,
+                                                              const int* __restrict__ bcnt, const double* __restrict__ V,
+                                                              const double* __restrict__ Y, const double* __restrict__ Yr,
+                                                              const double* __restrict__ Hoo, const double* __restrict__ bo, double lambda,
+                                                              double* __restrict__ T, long ldt, int o2_begin, int o2_end,
+                                                              const int* __restrict__ unrank, int accumulate) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int t1 = blockIdx.x;                    // block row of T (its order: unrank, null = ellipsoid order); N = the right-hand side (row 9 N of T)
+  const int o1 = (t1 == N || !unrank) ? t1 : unrank[t1];
+  const int r = lane & 15, kq = lane >> 4;
+  const long n_o = 9L * N;
+  const bool rhs = o1 == N;
+  // the MFMA's A operand (rows i of the block) comes from o1, its B operand (columns j) from o2: V of o1 against Y of o2, and for
+  // the b row Yr (six doubles per slot, row 0 alone) against V of o2.  The pairs of a block are concatenated along K.
+  const double* Asrc = rhs ? Yr : V;
+  const double* Bsrc = rhs ? V : Y;
+  const int astep = rhs ? 6 : 54, aoff = rhs ? 0 : r * 6;
+  const bool alane = rhs ? r == 0 : r < 9, blane = r < 9;
+  // the wave's blocks (kCfTPer / 4 of them): where their lists start and how long they are in ONE round trip (lane u = block u), and
+  // the first 64 pairs of the next block are loaded while this one's records are in flight
+  constexpr int kPerWave = kCfTPer / 4;
+  long long stl = 0;
+  int cnl = 0;
+  {
+    const int t2l = o2_begin + (int)blockIdx.y * kCfTPer + wave + 4 * (lane < kPerWave ? lane : 0);
+    if (lane < kPerWave && t2l < o2_end && t2l <= t1 && t2l < N) {
+      const long bl = rhs ? (long)N * (N + 1) / 2 + t2l : (long)t1 * (t1 + 1) / 2 + t2l;
+      stl = bstart[bl]; cnl = bcnt[bl];
+    }
+  }
+  auto first_pairs = [&](int u, int& px, int& py) {   // pairs [0, 64) of the wave's block u (nothing: u past the wave's blocks, an empty list)
+    px = 0; py = 0;
+    if (u >= kPerWave) return;
+    const long long st = ((long long)__builtin_amdgcn_readlane((int)(stl >> 32), u) << 32) | (unsigned)__builtin_amdgcn_readlane((int)stl, u);
+    if (lane < __builtin_amdgcn_readlane(cnl, u)) { const int2 pr = pairs[st + lane]; px = pr.x; py = pr.y; }
+  };
+  int nx = 0, ny = 0;
+  first_pairs(0, nx, ny);
+#pragma unroll
+  for (int u = 0; u < kPerWave; ++u) {
+    const int q = wave + 4 * u;
+    const int t2 = o2_begin + (int)blockIdx.y * kCfTPer + q;
+    const int px0 = nx, py0 = ny;
+    first_pairs(u + 1, nx, ny);
+    if (t2 >= o2_end || t2 > t1 || t2 >= N) continue;
+    const int o2 = unrank ? unrank[t2] : t2;
+    const long long start = ((long long)__builtin_amdgcn_readlane((int)(stl >> 32), u) << 32) | (unsigned)__builtin_amdgcn_readlane((int)stl, u);
+    const int n = __builtin_amdgcn_readlane(cnl, u);
+    cf_d4 acc = {0, 0, 0, 0};
+    for (int c0 = 0; c0 < n; c0 += 64) {   // 64 pairs = 96 whole K-steps: only a block's last step is padded with zero rows
+      const int m = n - c0 < 64 ? n - c0 : 64;
+      int px = px0, py = py0;
+      if (c0 > 0) { px = 0; py = 0; if (lane < m) { const int2 pr = pairs[start + c0 + lane]; px = pr.x; py = pr.y; } }
+      const int nst = (6 * m + 3) / 4;
+      for (int s0 = 0; s0 < nst; s0 += kCfOsBatch) {   // the loads of a batch of K-steps in flight together, then its MFMAs
+        double av[kCfOsBatch], bv[kCfOsBatch];
+#pragma unroll
+        for (int j = 0; j < kCfOsBatch; ++j) {
+          const int s = s0 + j;                                 // rows 4 s .. 4 s + 3 lie in pair e0 or e1
+          const int e0 = (4 * s) / 6 < 63 ? (4 * s) / 6 : 63, e1 = (4 * s + 3) / 6 < 63 ? (4 * s + 3) / 6 : 63;
+          const int x0 = __builtin_amdgcn_readlane(px, e0), x1 = __builtin_amdgcn_readlane(px, e1);
+          const int y0 = __builtin_amdgcn_readlane(py, e0), y1 = __builtin_amdgcn_readlane(py, e1);
+          const int kidx = 4 * s + kq;
+          const bool hi = kidx >= 6 * e1 && e1 != e0;
+          const int a = kidx - 6 * (hi ? e1 : e0);
+          const bool ok = (hi ? e1 : e0) < m && kidx < 6 * m;
+          const bool oka = ok && alane, okb = ok && blane;
+          const size_t ia = oka ? (size_t)(hi ? x1 : x0) * astep + aoff + a : 0, ib = okb ? (size_t)(hi ? y1 : y0) * 54 + r * 6 + a : 0;
+          const double va = Asrc[ia], vb = Bsrc[ib];
+          av[j] = oka ? va : 0.0; bv[j] = okb ? vb : 0.0;
+        }
+#pragma unroll
+        for (int j = 0; j < kCfOsBatch; ++j)
+          if (s0 + j < nst) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[j], bv[j], acc, 0, 0, 0);
+      }
+    }
+    // D: acc[g] = C(i = kq + 4 g, j = r); block (o1, o2) of T (column major), rows 9 t1 + i, columns 9 t2 + j
+    if (r < 9) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int i = kq + 4 * g;
+        if (rhs) {
+          if (i == 0) { double* tp = &T[n_o + (9L * t2 + r) * ldt]; const double v = bo[(size_t)o2 * 9 + r] - acc[g]; *tp = accumulate ? v + *tp : v; }
+        } else if (i < 9 && !(o1 == o2 && i < r)) {   // (above the diagonal: never stored, never read)
+          double base = 0;
+          if (o1 == o2) base = Hoo[(size_t)o1 * 45 + r * 9 - (r * (r - 1)) / 2 + (i - r)] + ((i == r) ? lambda : 0.0);
+          double* tp = &T[(9L * t1 + i) + (9L * t2 + r) * ldt];
+          const double v = base - acc[g];
+          *tp = accumulate ? v + *tp : v;
+        }
+      }
+    }
+  }
+}
 
 // x_o arrives from the solver in T's column order; everything else (trial states, the slabs' dot products, esl_lm_download) wants it
 // by ellipsoid

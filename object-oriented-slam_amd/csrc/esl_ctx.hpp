@@ -310,6 +310,17 @@ struct esl_ctx {
   int* cf_twork = nullptr;
   size_t cf_p_blocks = 0, cf_prhs_len = 0;
   double *cf_P = nullptr, *cf_Prhs = nullptr;
+  // cf_sp_form 3 = T's interior part assembled one-sided (k_cf_seg_back + k_cf_T_onesided: no P): Y = L_ii^T (L_p^-T X), one 54-double
+  // record per (segment, compact ellipsoid, interior slot), and the right-hand side's column per slot; cf_os_flops = 2 x the FMAs
+  // of the assembly's 9 x 6 . 6 x 9 products
+  double *cf_Y = nullptr, *cf_Yr = nullptr;
+  size_t cf_y_len = 0;
+  // the assembly's pair list, built once per layout (k_cf_os_list): per block of T's lower triangle and of the b row where its
+  // (A record, B record) pairs start and how many there are
+  long long* cf_os_start = nullptr;
+  int *cf_os_cnt = nullptr, *cf_os_pairs = nullptr;
+  size_t cf_os_npairs = 0;
+  double cf_os_flops = 0;
   // round 5: T's ellipsoids in the order of their first free camera (sparse form): column block cf_rank[o] of T / R / Xs belongs to
   // ellipsoid o; cf_kfirst[g] = first row of Xs that can be non-zero in columns [64 g, 64 g + 64) (the rank-K update skips the rest);
   // cf_xo_t = x_o as the solver returns it (T's order); cf_upd_flops = what the dense update executes with the staircase

@@ -4,6 +4,7 @@
 #include "esl_slam.hpp"
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -304,7 +305,8 @@ static void cf_forget(esl_ctx* c) {
   c->cf_Linv = c->cf_M = c->cf_N = c->cf_V = c->cf_B = c->cf_Lfac = c->cf_G = c->cf_vy = c->cf_z = nullptr;
   c->cf_T = c->cf_Linv_ws = c->cf_part = nullptr;
   c->cf_Zt = c->cf_Hs = c->cf_Bs = c->cf_LfacS = c->cf_GS = c->cf_LiS = c->cf_MS = c->cf_NS = c->cf_R = nullptr;
-  c->cf_Xc = c->cf_Xs = c->cf_P = c->cf_Prhs = c->cf_Xt = nullptr;
+  c->cf_Xc = c->cf_Xs = c->cf_P = c->cf_Prhs = c->cf_Xt = c->cf_Y = c->cf_Yr = nullptr;
+  c->cf_os_start = nullptr; c->cf_os_cnt = c->cf_os_pairs = nullptr;
   c->cf_rank = c->cf_unrank = c->cf_kfirst = nullptr; c->cf_xo_t = nullptr; c->cf_tperm = false; c->cf_upd_flops = 0;
   c->cf_ready = false; c->cf_sp_built = c->cf_sparse = false;
 }
@@ -413,6 +415,10 @@ static int cf_ensure_impl(esl_ctx* c) {
     const double need = 8.0 * (81.0 * (double)c->cf_p_blocks + (double)c->cf_xc_len + 2.0 * (double)c->cf_ldt * (double)n_o +
                                2.0 * 6.0 * n_sep * (double)c->cf_ldx /* Xs, R */ + 54.0 * (double)EU /* V */);
     c->cf_sp_form = (sw && sw[0] == '2') || need > 0.4 * (double)total_b ? 2 : 1;
+    // form 3 (esl_cf.hpp, "one-sided assembly"): no product store, so the memory rule above does not apply to it.  ESL_CF_SPARSE=3
+    // forces it; unset, it is the form wherever X is kept sparse on a single rank.  1 / 2 / 0 keep their paths and bits; a run
+    // with a communicator keeps its present form.
+    if ((!sw || sw[0] == '3') && !c->comm) c->cf_sp_form = 3;
     if (!c->cf_sparse) c->cf_sp_built = false;   // (none of the sparse-form tables are shipped)
   }
   const bool sp = c->cf_sparse;
@@ -472,6 +478,34 @@ static int cf_ensure_impl(esl_ctx* c) {
     }
   }
   c->cf_tperm = tperm; c->cf_upd_flops = upd_flops;
+  c->cf_y_len = 0; c->cf_os_flops = 0;
+  if (sp && c->cf_sp_form == 3) {
+    // what the one-sided assembly executes: per block (t1 >= t2) of T and shared segment, one 9 x 6 . 6 x 9 product per interior
+    // list entry of o1 in the segment; the b row one 6 x 9 . 6 product per interior entry.  (Segment, position in T's order,
+    // entries) of every incidence, by segment and position: the incidence at place q of its segment meets q + 1 partners.
+    std::vector<std::array<int, 3>> inc3;
+    inc3.reserve(n_inc);
+    double rhs_entries = 0;
+    for (int o = 0; o < N; ++o) {
+      int last_p = -1;
+      for (int k = start[o]; k < start[(size_t)o + 1]; ++k) {
+        const int sl = os[(size_t)k];
+        if (sl % kCfFwdCh == kCfFwdCh - 1) continue;
+        const int p = sl / kCfFwdCh;
+        if (p != last_p) { inc3.push_back({p, tperm ? h_rank[(size_t)o] : o, 0}); last_p = p; }
+        ++inc3.back()[2]; rhs_entries += 1;
+      }
+    }
+    std::sort(inc3.begin(), inc3.end());
+    double prod = 0;
+    for (size_t q = 0, q0 = 0; q < inc3.size(); ++q) {
+      if (inc3[q][0] != inc3[q0][0]) q0 = q;
+      prod += (double)inc3[q][2] * (double)(q - q0 + 1);
+    }
+    c->cf_os_flops = 2.0 * 6.0 * (81.0 * prod + 9.0 * rhs_entries);
+    c->cf_os_npairs = (size_t)(prod + rhs_entries);   // (record pairs of the assembly: the length of its list)
+    c->cf_y_len = std::max<size_t>(n_inc, 1) * kCfSegInt * 54 + std::max<size_t>(nf, 1) * 6;
+  }
   const double t1 = timing ? now_us() : 0;
   // ---- layout: what the host ships first, then the device-generated tables (esl_cf.hpp k_cf_make_*), then the buffers ----
   BlobStage st;
@@ -504,6 +538,11 @@ static int cf_ensure_impl(esl_ctx* c) {
     c->cf_kpad_s = (int64_t)((6 * (size_t)c->cf_n_sep + kKC - 1) / kKC * kKC);
     st.work(&c->cf_Xc, c->cf_xc_len); st.work(&c->cf_Xs, (size_t)c->cf_ldx * (size_t)c->cf_kpad_s);
     if (c->cf_sp_form == 1) { st.work(&c->cf_P, c->cf_p_blocks * 81); st.work(&c->cf_Prhs, c->cf_prhs_len); }
+    if (c->cf_sp_form == 3) {
+      const size_t nb = (size_t)N * (N + 1) / 2 + N;   // blocks of T's lower triangle + the b row
+      st.work(&c->cf_Y, std::max<size_t>(n_inc, 1) * kCfSegInt * 54); st.work(&c->cf_Yr, std::max<size_t>(nf, 1) * 6);
+      st.work(&c->cf_os_start, nb + 1); st.work(&c->cf_os_cnt, nb); st.work(&c->cf_os_pairs, 2 * std::max<size_t>(c->cf_os_npairs, 1));
+    }
   } else {
     st.work(&c->cf_Xt, (size_t)c->cf_ldx * (size_t)c->cf_kpad);
   }
@@ -545,6 +584,28 @@ static int cf_ensure_impl(esl_ctx* c) {
     hipLaunchKernelGGL(k_cf_make_work, dim3((unsigned)nseg), dim3(64), 0, c->stream, nseg, N, nw, c->cf_seg_start, d_fw_off, d_tw_off, c->cf_cmap, c->cf_mask,
                        c->cf_fwork, c->cf_twork);
   }
+  if (sp && c->cf_sp_form == 3) {
+    // the one-sided assembly's pair list (esl_cf.hpp): count per block, offsets on the host, fill.  Once per layout.
+    const size_t nb = (size_t)N * (N + 1) / 2 + N;
+    const dim3 grid((unsigned)(N + 1), (unsigned)((N + kCfTPer - 1) / kCfTPer));
+    ESL_HIP_TRY(hipMemsetAsync(c->cf_os_cnt, 0, nb * sizeof(int), c->stream));
+    hipLaunchKernelGGL(k_cf_os_list<false>, grid, dim3(256), 0, c->stream, N, nw, nch, c->cf_mask, c->cf_cmap, c->cf_seg_start, c->cf_oe_cst, c->cf_oe_slot,
+                       (const int*)c->cf_unrank, (const long long*)nullptr, c->cf_os_cnt, (int2*)nullptr);
+    std::vector<int> h_cnt(nb);
+    std::vector<long long> h_start(nb + 1);
+    ESL_HIP_TRY(hipMemcpyAsync(h_cnt.data(), c->cf_os_cnt, nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    ESL_HIP_TRY(hipStreamSynchronize(c->stream));
+    h_start[0] = 0;
+    for (size_t b = 0; b < nb; ++b) h_start[b + 1] = h_start[b] + h_cnt[b];
+    if ((size_t)h_start[nb] != c->cf_os_npairs) {
+      set_error("camera-first elimination: the one-sided assembly's pair list does not have the length the host counted");
+      return ESL_ERR_STATE;
+    }
+    ESL_HIP_TRY(hipMemcpyAsync(c->cf_os_start, h_start.data(), (nb + 1) * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_cf_os_list<true>, grid, dim3(256), 0, c->stream, N, nw, nch, c->cf_mask, c->cf_cmap, c->cf_seg_start, c->cf_oe_cst, c->cf_oe_slot,
+                       (const int*)c->cf_unrank, (const long long*)c->cf_os_start, c->cf_os_cnt, (int2*)c->cf_os_pairs);
+    ESL_HIP_TRY(hipStreamSynchronize(c->stream));   // (h_start is read by the copy until here)
+  }
   // ---- what must be zero ----
   if (nd) ESL_HIP_TRY(hipMemsetAsync(c->cf_Zt, 0, nf * 36 * sizeof(double), c->stream));
   if (sp) {
@@ -553,6 +614,10 @@ static int cf_ensure_impl(esl_ctx* c) {
     ESL_HIP_TRY(hipMemsetAsync(c->cf_Xc, 0, std::max<size_t>(c->cf_xc_len, 1) * sizeof(double), c->stream));
     ESL_HIP_TRY(hipMemsetAsync(c->cf_Xs, 0, (size_t)c->cf_ldx * (size_t)c->cf_kpad_s * sizeof(double), c->stream));
     ESL_HIP_TRY(hipMemsetAsync(c->cf_T, 0, (size_t)c->cf_ldt * n_o * sizeof(double), c->stream));
+    if (c->cf_sp_form == 3) {   // (the records of slots behind a short last segment's end are never written and never read)
+      ESL_HIP_TRY(hipMemsetAsync(c->cf_Y, 0, std::max<size_t>(n_inc, 1) * kCfSegInt * 54 * sizeof(double), c->stream));
+      ESL_HIP_TRY(hipMemsetAsync(c->cf_Yr, 0, std::max<size_t>(nf, 1) * 6 * sizeof(double), c->stream));
+    }
   } else {
     // rows 6 nf .. kpad of X (the K padding of the rank-K update) and the columns of never-written edges stay zero
     ESL_HIP_TRY(hipMemsetAsync(c->cf_Xt, 0, (size_t)c->cf_ldx * (size_t)c->cf_kpad * sizeof(double), c->stream));
@@ -601,12 +666,17 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
     // writes the slabs trial t's products read: the main stream has waited for trial t's cf_ev_p.  cf_ensure's relayout, esl_ctx_trim
     // and everything else on the main stream are covered the same way, because every way out of this function leaves the side
     // stream joined to the main one (CfSideJoin).
-    const bool side = c->sw_cf_overlap != 0 && nd && c->cf_sparse && c->cf_sp_form == 1 && !dist && Ks_ > 0 && rt.cf_overlap_init() == hipSuccess;
+    // Form 3 (one-sided assembly, esl_cf.hpp): the assembly needs Y alone, which exists straight behind k_cf_forward<2>, so with the
+    // switch on the WHOLE separator path -- chain, V and vy of the separator slots, k_cf_sep_rhs, k_cf_forward<1> -- runs on rt.cf_side
+    // beside k_cf_seg_back and the assembly, and the update (uncapped, in its accumulate form) waits for the assembly and Xs only.  One
+    // arithmetic order for T at every setting of the switch: T = D - sum (assign), then T -= Xs^T Xs.
+    const bool os = c->cf_sparse && c->cf_sp_form == 3;
+    const bool side = c->sw_cf_overlap != 0 && nd && c->cf_sparse && (c->cf_sp_form == 1 || os) && !dist && Ks_ > 0 && rt.cf_overlap_init() == hipSuccess;
     // with the update on its k_chol_update_v path (the one with an assign form) the products also run beside the UPDATE (round 6): it
     // ASSIGNS T = -Xs^T Xs instead of updating what the gather wrote, and the gather, which then comes last, adds its D - sum to that --
     // (D - sum) + (-acc) is the same double as (D - sum) - acc, so T has the same bits
-    const bool assign = side && chol_update_v_applies(rt.sw, ldt, (long)n_o + 1, 0, (long)n_o, true, ldx);
-    const bool side_chain = side && c->sw_cf_overlap != 3, early_products = side && c->sw_cf_overlap != 2;   // (each alone: A/B)
+    const bool assign = side && !os && chol_update_v_applies(rt.sw, ldt, (long)n_o + 1, 0, (long)n_o, true, ldx);
+    const bool side_chain = side && (os || c->sw_cf_overlap != 3), early_products = side && !os && c->sw_cf_overlap != 2;   // (each alone: A/B)
     struct CfSideJoin {   // side-stream work not yet waited for by the main stream when the function is left (an ESL_HIP_TRY failure): joined here
       CholRuntime& rt; hipStream_t main; bool armed;
       hipError_t wait(hipEvent_t ev) { const hipError_t e = hipStreamWaitEvent(main, ev, 0); armed = e != hipSuccess; return e; }
@@ -617,13 +687,13 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
     } join{rt, c->stream, false};
     // V = Li W, vy = Li b_c (cls: esl_cf.hpp -- 0 all list entries, 1 / 2 those of interior / separator slots); X dense: the same launch
     // writes the whole of T (D's lower blocks, b_o's row, zeros) -- nothing reads T before the rank-K update further down
-    auto launch_edge_scale = [&](int cls) {
+    auto launch_edge_scale = [&](int cls, hipStream_t st2) {
       const int nb_es = (int)((nt + 255) / 256);
       if (!c->cf_sparse)
         hipLaunchKernelGGL(k_cf_edge_scale_T, dim3((unsigned)(nb_es + (int)((ldt * (long)n_o + 255) / 256))), dim3(256), 0, c->stream, g, nb_es, c->cf_n_list, c->cf_oe_u,
                            c->cf_oe_slot, c->Wbb, c->cf_Linv, c->bc, c->cf_V, c->cf_vy, c->Hoo, c->bo, lambda, c->cf_T, ldt, (long)n_o);
       else
-        hipLaunchKernelGGL(k_cf_edge_scale, dim3((unsigned)nb_es), dim3(256), 0, c->stream, g, c->cf_n_list, c->cf_oe_u, c->cf_oe_slot, c->Wbb, c->cf_Linv, c->bc,
+        hipLaunchKernelGGL(k_cf_edge_scale, dim3((unsigned)nb_es), dim3(256), 0, st2, g, c->cf_n_list, c->cf_oe_u, c->cf_oe_slot, c->Wbb, c->cf_Linv, c->bc,
                            c->cf_V, c->cf_vy, cls, st);
     };
     auto launch_products = [&](hipStream_t st2) {
@@ -635,7 +705,7 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
     if (!nd) {
       hipLaunchKernelGGL(k_cf_chain, dim3(1), dim3(64), 0, c->stream, nf, c->Hcc, c->cf_B, lambda, c->cf_Lfac, c->cf_G, c->chol_info, nf, nf);
       hipLaunchKernelGGL(k_cf_factor_blocks, dim3((unsigned)((nf + 63) / 64)), dim3(64), 0, c->stream, nf, c->cf_Lfac, c->cf_G, c->cf_Linv, c->cf_M, c->cf_N, 0);
-      launch_edge_scale(0);
+      launch_edge_scale(0, c->stream);
       hipLaunchKernelGGL(k_cf_forward<0>, dim3(cg), dim3(64), 0, c->stream, nf, n_o, c->cf_n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V, c->cf_vy,
                          c->cf_M, c->cf_Xt, ldx, nf, nf, (const double*)nullptr, (double*)nullptr, 0, CfSegs{});
     } else {   // nested dissection (esl_cf.hpp): segments in parallel, then the separators' own short chain
@@ -655,10 +725,10 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
         join.armed = true;
         launch_sep_chain(rt.cf_side);
         ESL_HIP_TRY(hipEventRecord(rt.cf_ev_s, rt.cf_side));
-        launch_edge_scale(1);
+        launch_edge_scale(1, c->stream);
       } else {
         launch_sep_chain(c->stream);
-        launch_edge_scale(0);
+        launch_edge_scale(0, c->stream);
       }
       if (!c->cf_sparse) {
         hipLaunchKernelGGL(k_cf_forward<0>, dim3(cg, (unsigned)nseg), dim3(64), 0, c->stream, nf, n_o, c->cf_n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V,
@@ -671,16 +741,24 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
         const CfSegs sg{c->cf_fwork, c->cf_seg_start, c->cf_seg_obj, c->cf_xoff, c->cf_xld, c->cf_rank, c->cf_unrank};
         hipLaunchKernelGGL(k_cf_forward<2>, dim3((unsigned)c->cf_n_fwork), dim3(64), 0, c->stream, nf, n_o, c->cf_n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V,
                            c->cf_vy, c->cf_M, c->cf_Xc, ldx, st, st - 1, (const double*)c->cf_Zt, c->cf_R, st, sg);
-        if (side_chain) {   // the separators' chain is needed from here on: their V and vy, then the right-hand sides
+        // form 3 with the switch on: everything of the separators stays on the side stream, which waits for the slabs and the sums in R
+        const hipStream_t sst = (os && side) ? rt.cf_side : c->stream;
+        if (os && side) {
+          ESL_HIP_TRY(hipEventRecord(rt.cf_ev_x, c->stream));
+          ESL_HIP_TRY(hipStreamWaitEvent(rt.cf_side, rt.cf_ev_x, 0));
+          launch_edge_scale(2, sst);
+        } else if (side_chain) {   // the separators' chain is needed from here on: their V and vy, then the right-hand sides
           ESL_HIP_TRY(join.wait(rt.cf_ev_s));
-          launch_edge_scale(2);
+          launch_edge_scale(2, c->stream);
         }
-        hipLaunchKernelGGL(k_cf_sep_rhs, dim3(cg, (unsigned)ns), dim3(64), 0, c->stream, nf, n_o, st, c->cf_n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V, c->cf_vy,
+        hipLaunchKernelGGL(k_cf_sep_rhs, dim3(cg, (unsigned)ns), dim3(64), 0, sst, nf, n_o, st, c->cf_n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V, c->cf_vy,
                            c->cf_G, c->cf_LiS, c->cf_Xc, ldx, c->cf_R, (const int*)c->cf_cmap, sg);
         if (early_products) ESL_HIP_TRY(hipEventRecord(rt.cf_ev_x, c->stream));   // (the slabs were complete after k_cf_forward<2>; k_cf_sep_rhs only reads them)
-        hipLaunchKernelGGL(k_cf_forward<1>, dim3(cg), dim3(64), 0, c->stream, ns, n_o, c->cf_n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V, c->cf_vy,
+        hipLaunchKernelGGL(k_cf_forward<1>, dim3(cg), dim3(64), 0, sst, ns, n_o, c->cf_n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V, c->cf_vy,
                            c->cf_MS, c->cf_Xs, ldx, ns, ns, (const double*)nullptr, c->cf_R, 0, CfSegs{});
-        if (side) {   // the products behind k_cf_forward<1>'s 282 waves (C4), beside them.  Measured at C4: the products start 1.4 ms
+        if (os && side) {
+          ESL_HIP_TRY(hipEventRecord(rt.cf_ev_p, rt.cf_side));
+        } else if (side) {   // the products behind k_cf_forward<1>'s 282 waves (C4), beside them.  Measured at C4: the products start 1.4 ms
                       // earlier, k_cf_forward<1> stretches from 0.61 to 1.08 ms beside them, the update starts 0.32 ms earlier
           if (!early_products) ESL_HIP_TRY(hipEventRecord(rt.cf_ev_x, c->stream));
           ESL_HIP_TRY(hipStreamWaitEvent(rt.cf_side, rt.cf_ev_x, 0));
@@ -695,7 +773,10 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
         const long c_begin = dist ? (long)op * Wp * kNB : 0, c_end = dist ? std::min<long>((long)(op + 1) * Wp * kNB, (long)n_o) : (long)n_o;
         const int o2b = (int)(c_begin / 9), o2e = (int)((c_end + 8) / 9);   // (a block that straddles a panel boundary: on both sides)
         const dim3 grid((unsigned)(N + 1), (unsigned)((o2e - o2b + kCfTPer - 1) / kCfTPer));
-        if (c->cf_sp_form == 1)
+        if (c->cf_sp_form == 3)
+          hipLaunchKernelGGL(k_cf_T_onesided, grid, dim3(256), 0, c->stream, N, (const int2*)c->cf_os_pairs, (const long long*)c->cf_os_start,
+                             (const int*)c->cf_os_cnt, c->cf_V, c->cf_Y, c->cf_Yr, c->Hoo, c->bo, lambda, c->cf_T, ldt, o2b, o2e, (const int*)c->cf_unrank, accumulate);
+        else if (c->cf_sp_form == 1)
           hipLaunchKernelGGL(k_cf_T_gather, grid, dim3(256), 0, c->stream, N, c->cf_sp_nw, c->cf_mask, c->cf_cmap, c->cf_boff, c->cf_roff, c->cf_P, c->cf_Prhs,
                              c->Hoo, c->bo, lambda, c->cf_T, ldt, o2b, o2e, (const int*)c->cf_unrank, accumulate);
         else
@@ -716,7 +797,28 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
         chol_launch_update(rt.sw, c->cf_T, ldt, (long)n_o + 1, c->stream, 0, K, 0, (long)n_o, Xf, ldx, c->cf_part, c->cf_sparse ? c->cf_kfirst : nullptr);
       }
     };
-    if (assign) {
+    if (os) {   // Y behind the slabs, T = D - sum from V and Y; the update last, uncapped, with nothing beside it
+      // ESL_CF_OS_ORDER=1 (A/B, profiles/cf_onesided_c4.md): the update first in its assign form, the assembly adding D - sum behind
+      // it -- (D - sum) + (-acc), the same double as (D - sum) - acc
+      static const bool update_first = [] { const char* e = std::getenv("ESL_CF_OS_ORDER"); return e && e[0] == '1'; }();
+      const bool swap = update_first && chol_update_v_applies(rt.sw, ldt, (long)n_o + 1, 0, (long)n_o, true, ldx);
+      if (swap) {
+        if (side) ESL_HIP_TRY(join.wait(rt.cf_ev_p));
+        ProfScope pk(c, 7);
+        chol_launch_update(rt.sw, c->cf_T, ldt, (long)n_o + 1, c->stream, 0, Ks_, 0, (long)n_o, c->cf_Xs, ldx, nullptr, c->cf_kfirst, true, false);
+      }
+      {
+        ProfScope pk(c, 8);
+        hipLaunchKernelGGL(k_cf_seg_back, dim3((unsigned)c->cf_n_fwork), dim3(64), 0, c->stream, nf, c->cf_fwork, c->cf_seg_start, c->cf_xoff, c->cf_xld, c->cf_Xc,
+                           c->cf_Linv, c->cf_G, c->cf_Y, c->cf_Yr);
+        launch_gather(swap ? 1 : 0);
+      }
+      ESL_HIP_TRY(hipGetLastError());
+      if (!swap) {
+        if (side) ESL_HIP_TRY(join.wait(rt.cf_ev_p));
+        launch_update();
+      }
+    } else if (assign) {
       {
         // ESL_CF_OVERLAP=4 (default): the update CAPPED to one workgroup per CU (chol_launch_update's `cap`).  At its two workgroups
         // per CU (252 registers a lane) every slot that frees goes to the next update workgroup and the products' waves (240) are
@@ -1356,6 +1458,7 @@ extern "C" int esl_lm_solver_stats(esl_ctx* c, double* st) {
   if (c->cf_sparse) {
     st[4] = 2.0 * c->cf_sp_flops;   // (FMAs of the block lower triangles, rows from each block row's first camera on)
     st[5] = c->cf_sp_form == 1 ? 8.0 * 81.0 * (double)c->cf_p_blocks : 0.0;
+    if (c->cf_sp_form == 3) { st[4] = c->cf_os_flops; st[5] = 8.0 * (double)c->cf_y_len; }   // (the one-sided assembly's products; bytes of Y)
     st[6] = 8.0 * (double)c->cf_xc_len;
   }
   st[7] = (double)(c->cf_sparse ? c->cf_kpad_s : c->cf_kpad);
