@@ -1118,17 +1118,20 @@ static __global__ __launch_bounds__(64) void k_cf_seg_back(int nf_all, const int
 // the lower triangle (T's order), N (N + 1) / 2 + t2 for the b row; its pairs in the order they are added: shared segments
 // ascending, o1's entries of the segment in list order, entries of the separator's slot left out.
 // pair = (record of the A operand, record of the B operand): (list entry of o1, Y record of o2) -- b row: (slot, list entry of o2).
+// `offsets` != 0 (k_cf_T_onesided_lds): the pair holds what that kernel would multiply out, the records' first elements -- entry x 54,
+// Y record x 54, slot x 6; the host checked that they fit 32 bits (cf_ensure_impl).  0: record numbers (k_cf_T_onesided).
 template <bool FILL>
 static __global__ __launch_bounds__(256) void k_cf_os_list(int N, int nw, int n_chunks, const unsigned long long* __restrict__ mask,
                                                            const int* __restrict__ cmap, const int* __restrict__ seg_start,
                                                            const int* __restrict__ oe_cst, const int* __restrict__ oe_slot,
                                                            const int* __restrict__ unrank, const long long* __restrict__ bstart,
-                                                           int* __restrict__ bcnt, int2* __restrict__ pairs) {
+                                                           int* __restrict__ bcnt, int2* __restrict__ pairs, int offsets) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int t1 = blockIdx.x;
   const int o1 = (t1 == N || !unrank) ? t1 : unrank[t1];
   const int N1 = N + 1;
   const bool rhs = o1 == N;
+  const int m54 = offsets ? 54 : 1, m6 = offsets ? 6 : 1;
   for (int q = wave; q < kCfTPer; q += 4) {
     const int t2 = (int)blockIdx.y * kCfTPer + q;
     if (t2 > t1 || t2 >= N) continue;
@@ -1157,7 +1160,7 @@ static __global__ __launch_bounds__(256) void k_cf_os_list(int N, int nw, int n_
           const unsigned long long vb = __ballot(valid);
           if (FILL && valid) {
             const int at = cnt + __builtin_popcountll(vb & ((1ull << lane) - 1ull));
-            pairs[w0 + at] = rhs ? make_int2(p * kCfFwdCh + pos, ent) : make_int2(ent, yr + pos);
+            pairs[w0 + at] = rhs ? make_int2((p * kCfFwdCh + pos) * m6, ent * m54) : make_int2(ent * m54, (yr + pos) * m54);
           }
           cnt += __builtin_popcountll(vb);
         }
@@ -1242,6 +1245,178 @@ static __global__ __launch_bounds__(256) void k_cf_T_onesided(int N, const int2*
 #pragma unroll
         for (int j = 0; j < kCfOsBatch; ++j)
           if (s0 + j < nst) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[j], bv[j], acc, 0, 0, 0);
+      }
+    }
+    // D: acc[g] = C(i = kq + 4 g, j = r); block (o1, o2) of T (column major), rows 9 t1 + i, columns 9 t2 + j
+    if (r < 9) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int i = kq + 4 * g;
+        if (rhs) {
+          if (i == 0) { double* tp = &T[n_o + (9L * t2 + r) * ldt]; const double v = bo[(size_t)o2 * 9 + r] - acc[g]; *tp = accumulate ? v + *tp : v; }
+        } else if (i < 9 && !(o1 == o2 && i < r)) {   // (above the diagonal: never stored, never read)
+          double base = 0;
+          if (o1 == o2) base = Hoo[(size_t)o1 * 45 + r * 9 - (r * (r - 1)) / 2 + (i - r)] + ((i == r) ? lambda : 0.0);
+          double* tp = &T[(9L * t1 + i) + (9L * t2 + r) * ldt];
+          const double v = base - acc[g];
+          *tp = accumulate ? v + *tp : v;
+        }
+      }
+    }
+  }
+}
+
+// k_cf_T_onesided_lds: the same blocks, pairs, MFMAs and epilogue as k_cf_T_onesided -- bit for bit -- with the operands fed as whole
+// records through LDS (profiles/cf_onesided_gather_c4.md).  The list holds element offsets (k_cf_os_list, offsets = 1), so a record's
+// base is one readlane into a scalar register and the load is scalar base + lane: lane l < 54 fetches element l = 6 b + a of the
+// record, one instruction per record and no vector arithmetic.  Per wave and operand an image [row b = 0 .. 8, row 9 = zeros][k] of a
+// batch of E pairs, k = 6 e + a along the batch's concatenated K: the load lane writes b LDK + a (+ 6 e, immediate), the MFMA lane
+// (r, kq) of step s reads min(r, 9) LDK + kq (+ 4 s, immediate).  LDK (cf_og_ldk: 59 for eight pairs) puts the ten rows x two kq of a
+// ds_read_b64 group into distinct banks, is odd for the ds_read2_b64 the compiler pairs the steps into, and leaves a ds_write_b64 group
+// at most two lanes on a bank.  b row: the A image's row 0 from Yr, every other lane reads zeros.
+// A block's last batch writes one pair of zeros behind its last pair: the zero K rows of the block's last step.
+// The next batch's records are asked for before this batch's MFMAs.  The images belong to one wave: no barriers.
+constexpr bool cf_og_ldk_ok(int ldk, int mod) {   // ten rows x two kq of a read group in distinct banks of `mod` doubles
+  for (int i = 0; i < 20; ++i)
+    for (int j = 0; j < i; ++j)
+      if (((i / 2) * ldk + i % 2) % mod == ((j / 2) * ldk + j % 2) % mod) return false;
+  return true;
+}
+constexpr bool cf_og_ldk_wr_ok(int ldk) {   // the 16 lanes of a write group: at most two of them on one bank of 16 doubles
+  for (int g = 0; g < 4; ++g) {
+    int cnt[16] = {};
+    for (int l = 16 * g; l < 16 * g + 16 && l < 54; ++l)
+      if (++cnt[((l / 6) * ldk + l % 6) % 16] > 2) return false;
+  }
+  return true;
+}
+// odd: a ds_read2_b64's groups are 16 lanes of one kq on banks of 16 doubles -- ten rows apart by an odd stride
+constexpr int cf_og_ldk(int E) { int k = 6 * E + 1; while (!cf_og_ldk_ok(k, 32) || !cf_og_ldk_wr_ok(k)) k += 2; return k; }
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef __attribute__((address_space(1))) double cf_gdouble;   // (global memory: an address made from an integer loads as global, not flat)
+#else
+typedef double cf_gdouble;
+#endif
+constexpr int kCfOgBatch = 8;   // pairs per batch: 12 whole K-steps, 16 records in flight; the images of four workgroups fit a CU
+static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_cf_T_onesided_lds(int N, const int2* __restrict__ pairs, const long long* __restrict__ bstart,
+                                                                  const int* __restrict__ bcnt, const double* __restrict__ V,
+                                                                  const double* __restrict__ Y, const double* __restrict__ Yr,
+                                                                  const double* __restrict__ Hoo, const double* __restrict__ bo, double lambda,
+                                                                  double* __restrict__ T, long ldt, int o2_begin, int o2_end,
+                                                                  const int* __restrict__ unrank, int accumulate) {
+  constexpr int E = kCfOgBatch, LDK = cf_og_ldk(E), NST = 6 * E / 4, IMG = 10 * LDK;
+  static_assert(64 % E == 0 && (6 * E) % 4 == 0, "whole batches per 64 pairs, whole K-steps per batch");
+  __shared__ double sImg[4 * 2 * IMG];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int t1 = blockIdx.x;
+  const int o1 = (t1 == N || !unrank) ? t1 : unrank[t1];
+  const int r = lane & 15, kq = lane >> 4;
+  const long n_o = 9L * N;
+  const bool rhs = o1 == N;
+  const double* Asrc = rhs ? Yr : V;
+  const double* Bsrc = rhs ? V : Y;
+  double* sA = sImg + wave * 2 * IMG;
+  double* sB = sA + IMG;
+  for (int i = lane; i < LDK; i += 64) { sA[9 * LDK + i] = 0.0; sB[9 * LDK + i] = 0.0; }
+  // load lanes: element `lane` of the record (clamped inside it, the clamped lanes do not write); MFMA lanes: their row of the image
+  const bool wa = lane < (rhs ? 6 : 54), wb = lane < 54;
+  const unsigned la8 = wa ? 8u * lane : 0u, lb8 = wb ? 8u * lane : 0u;
+  double* wA = sA + (lane / 6) * LDK + lane % 6;
+  double* wB = sB + (lane / 6) * LDK + lane % 6;
+  const double* rA = sA + (rhs ? (r == 0 ? 0 : 9) : (r < 9 ? r : 9)) * LDK + kq;
+  const double* rB = sB + (r < 9 ? r : 9) * LDK + kq;
+  constexpr int kPerWave = kCfTPer / 4;
+  long long stl = 0;
+  int cnl = 0;
+  {
+    const int t2l = o2_begin + (int)blockIdx.y * kCfTPer + wave + 4 * (lane < kPerWave ? lane : 0);
+    if (lane < kPerWave && t2l < o2_end && t2l <= t1 && t2l < N) {
+      const long bl = rhs ? (long)N * (N + 1) / 2 + t2l : (long)t1 * (t1 + 1) / 2 + t2l;
+      stl = bstart[bl]; cnl = bcnt[bl];
+    }
+  }
+  auto first_pairs = [&](int u, int& px, int& py) {   // pairs [0, 64) of the wave's block u (nothing: u past the wave's blocks, an empty list)
+    px = 0; py = 0;
+    if (u >= kPerWave) return;
+    const long long st = ((long long)__builtin_amdgcn_readlane((int)(stl >> 32), u) << 32) | (unsigned)__builtin_amdgcn_readlane((int)stl, u);
+    if (lane < __builtin_amdgcn_readlane(cnl, u)) { const int2 pr = pairs[st + lane]; px = pr.x; py = pr.y; }
+  };
+  double ga[E], gb[E];
+  auto load = [&](const bool full, const int px, const int py, int e0, int m) __attribute__((always_inline)) {   // pairs e0 .. e0 + m - 1 of the 64 -> registers
+#pragma unroll
+    for (int e = 0; e < E; ++e)
+      if (full || e < m) {
+        const unsigned x = (unsigned)__builtin_amdgcn_readlane(px, e0 + e), y = (unsigned)__builtin_amdgcn_readlane(py, e0 + e);
+        unsigned long long pa = (unsigned long long)(Asrc + x), pb = (unsigned long long)(Bsrc + y);
+        unsigned oa = la8, ob = lb8;
+#if defined(__HIP_DEVICE_COMPILE__)
+        // (no instructions: the record's base stays in scalar registers and the lane's offset 32 bits wide next to its load, so
+        // that the load is scalar base + vector offset with no vector add)
+        asm("" : "+s"(pa)); asm("" : "+s"(pb)); asm("" : "+v"(oa)); asm("" : "+v"(ob));
+#endif
+        ga[e] = *(const cf_gdouble*)(pa + oa);
+        gb[e] = *(const cf_gdouble*)(pb + ob);
+      }
+  };
+  int nx = 0, ny = 0;
+  first_pairs(0, nx, ny);
+#pragma unroll
+  for (int u = 0; u < kPerWave; ++u) {
+    const int q = wave + 4 * u;
+    const int t2 = o2_begin + (int)blockIdx.y * kCfTPer + q;
+    const int px0 = nx, py0 = ny;
+    first_pairs(u + 1, nx, ny);
+    if (t2 >= o2_end || t2 > t1 || t2 >= N) continue;
+    const int o2 = unrank ? unrank[t2] : t2;
+    const long long start = ((long long)__builtin_amdgcn_readlane((int)(stl >> 32), u) << 32) | (unsigned)__builtin_amdgcn_readlane((int)stl, u);
+    const int n = __builtin_amdgcn_readlane(cnl, u);
+    cf_d4 acc = {0, 0, 0, 0};
+    for (int c0 = 0; c0 < n; c0 += 64) {   // 64 pairs = whole batches of whole K-steps: only a block's last step is padded with zero rows
+      const int m64 = n - c0 < 64 ? n - c0 : 64;
+      int px = px0, py = py0;
+      if (c0 > 0) { px = 0; py = 0; if (lane < m64) { const int2 pr = pairs[start + c0 + lane]; px = pr.x; py = pr.y; } }
+      auto store = [&](const bool full, int m) __attribute__((always_inline)) {   // registers -> the images; zeros behind a short batch
+        if (wa) {
+#pragma unroll
+          for (int e = 0; e < E; ++e)
+            if (full || e < m) wA[6 * e] = ga[e];
+          if (!full) wA[6 * m] = 0.0;   // (m < E)
+        }
+        if (wb) {
+#pragma unroll
+          for (int e = 0; e < E; ++e)
+            if (full || e < m) wB[6 * e] = gb[e];
+          if (!full) wB[6 * m] = 0.0;
+        }
+      };
+      auto steps = [&](const bool full, int m) __attribute__((always_inline)) {
+        const int nst = (6 * m + 3) / 4;
+        if (full) {   // all reads of the batch in flight, then its MFMAs
+          double av[NST], bv[NST];
+#pragma unroll
+          for (int j = 0; j < NST; ++j) { av[j] = rA[4 * j]; bv[j] = rB[4 * j]; }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int j = 0; j < NST; ++j) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[j], bv[j], acc, 0, 0, 0);
+        } else {
+#pragma unroll
+          for (int j = 0; j < NST; ++j)
+            if (j < nst) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(rA[4 * j], rB[4 * j], acc, 0, 0, 0);
+        }
+      };
+      int mb = m64 < E ? m64 : E;
+      if (mb == E) load(true, px, py, 0, E); else load(false, px, py, 0, mb);
+      for (int e0 = 0; e0 < m64; e0 += E) {
+        const int m = mb;
+        __builtin_amdgcn_wave_barrier();   // (the last batch's reads of the images stay in front of these stores)
+        if (m == E) store(true, E); else store(false, m);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const int e1 = e0 + E;
+        mb = m64 - e1 < E ? m64 - e1 : E;
+        if (mb == E) load(true, px, py, e1, E); else if (mb > 0) load(false, px, py, e1, mb);   // the next batch's records under this one's MFMAs
+        if (m == E) steps(true, E); else steps(false, m);
       }
     }
     // D: acc[g] = C(i = kq + 4 g, j = r); block (o1, o2) of T (column major), rows 9 t1 + i, columns 9 t2 + j

@@ -316,10 +316,13 @@ struct esl_ctx {
   double *cf_Y = nullptr, *cf_Yr = nullptr;
   size_t cf_y_len = 0;
   // the assembly's pair list, built once per layout (k_cf_os_list): per block of T's lower triangle and of the b row where its
-  // (A record, B record) pairs start and how many there are
+  // (A record, B record) pairs start and how many there are.  cf_os_offsets: a pair holds the two records' first elements (entry x 54,
+  // Y record x 54; b row: slot x 6, entry x 54) for k_cf_T_onesided_lds -- false: their numbers, for k_cf_T_onesided, which runs when
+  // sw_cf_os_kernel is 0 or an offset would not fit 32 bits
   long long* cf_os_start = nullptr;
   int *cf_os_cnt = nullptr, *cf_os_pairs = nullptr;
   size_t cf_os_npairs = 0;
+  bool cf_os_offsets = false;
   double cf_os_flops = 0;
   // round 5: T's ellipsoids in the order of their first free camera (sparse form): column block cf_rank[o] of T / R / Xs belongs to
   // ellipsoid o; cf_kfirst[g] = first row of Xs that can be non-zero in columns [64 g, 64 g + 64) (the rank-K update skips the rest);
@@ -371,4 +374,7 @@ struct esl_ctx {
   // both side-stream orders; 2: the separators' chain beside the interior rows only; 3: the products' early start only; 4 (default):
   // as 1, and the rank-K update capped to one workgroup per CU so that the products' waves are resident beside it (1: uncapped, A/B)
   int sw_cf_overlap = 4;
+  // ESL_CF_OS_KERNEL as read when the context was created (A/B and tests): 1 (default) the one-sided assembly feeds whole records
+  // through LDS (k_cf_T_onesided_lds), 0 the per-lane gather (k_cf_T_onesided).  Same bits either way.
+  int sw_cf_os_kernel = 1;
 };

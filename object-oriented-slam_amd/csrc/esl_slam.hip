@@ -588,9 +588,13 @@ static int cf_ensure_impl(esl_ctx* c) {
     // the one-sided assembly's pair list (esl_cf.hpp): count per block, offsets on the host, fill.  Once per layout.
     const size_t nb = (size_t)N * (N + 1) / 2 + N;
     const dim3 grid((unsigned)(N + 1), (unsigned)((N + kCfTPer - 1) / kCfTPer));
+    // element offsets for k_cf_T_onesided_lds where every record's first element fits the list's 32 bits (C4: 1.4e8), else record
+    // numbers and the per-lane gather
+    const size_t max_off = 54 * std::max<size_t>(EU, std::max<size_t>(n_inc, 1) * kCfSegInt);
+    c->cf_os_offsets = c->sw_cf_os_kernel != 0 && max_off <= (size_t)INT32_MAX;
     ESL_HIP_TRY(hipMemsetAsync(c->cf_os_cnt, 0, nb * sizeof(int), c->stream));
     hipLaunchKernelGGL(k_cf_os_list<false>, grid, dim3(256), 0, c->stream, N, nw, nch, c->cf_mask, c->cf_cmap, c->cf_seg_start, c->cf_oe_cst, c->cf_oe_slot,
-                       (const int*)c->cf_unrank, (const long long*)nullptr, c->cf_os_cnt, (int2*)nullptr);
+                       (const int*)c->cf_unrank, (const long long*)nullptr, c->cf_os_cnt, (int2*)nullptr, 0);
     std::vector<int> h_cnt(nb);
     std::vector<long long> h_start(nb + 1);
     ESL_HIP_TRY(hipMemcpyAsync(h_cnt.data(), c->cf_os_cnt, nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -603,7 +607,7 @@ static int cf_ensure_impl(esl_ctx* c) {
     }
     ESL_HIP_TRY(hipMemcpyAsync(c->cf_os_start, h_start.data(), (nb + 1) * sizeof(long long), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_cf_os_list<true>, grid, dim3(256), 0, c->stream, N, nw, nch, c->cf_mask, c->cf_cmap, c->cf_seg_start, c->cf_oe_cst, c->cf_oe_slot,
-                       (const int*)c->cf_unrank, (const long long*)c->cf_os_start, c->cf_os_cnt, (int2*)c->cf_os_pairs);
+                       (const int*)c->cf_unrank, (const long long*)c->cf_os_start, c->cf_os_cnt, (int2*)c->cf_os_pairs, c->cf_os_offsets ? 1 : 0);
     ESL_HIP_TRY(hipStreamSynchronize(c->stream));   // (h_start is read by the copy until here)
   }
   // ---- what must be zero ----
@@ -773,7 +777,10 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
         const long c_begin = dist ? (long)op * Wp * kNB : 0, c_end = dist ? std::min<long>((long)(op + 1) * Wp * kNB, (long)n_o) : (long)n_o;
         const int o2b = (int)(c_begin / 9), o2e = (int)((c_end + 8) / 9);   // (a block that straddles a panel boundary: on both sides)
         const dim3 grid((unsigned)(N + 1), (unsigned)((o2e - o2b + kCfTPer - 1) / kCfTPer));
-        if (c->cf_sp_form == 3)
+        if (c->cf_sp_form == 3 && c->cf_os_offsets) {
+          hipLaunchKernelGGL(k_cf_T_onesided_lds, grid, dim3(256), 0, c->stream, N, (const int2*)c->cf_os_pairs, (const long long*)c->cf_os_start,
+                             (const int*)c->cf_os_cnt, c->cf_V, c->cf_Y, c->cf_Yr, c->Hoo, c->bo, lambda, c->cf_T, ldt, o2b, o2e, (const int*)c->cf_unrank, accumulate);
+        } else if (c->cf_sp_form == 3)
           hipLaunchKernelGGL(k_cf_T_onesided, grid, dim3(256), 0, c->stream, N, (const int2*)c->cf_os_pairs, (const long long*)c->cf_os_start,
                              (const int*)c->cf_os_cnt, c->cf_V, c->cf_Y, c->cf_Yr, c->Hoo, c->bo, lambda, c->cf_T, ldt, o2b, o2e, (const int*)c->cf_unrank, accumulate);
         else if (c->cf_sp_form == 1)
