@@ -959,6 +959,11 @@ int esl_debug_chol_plan(int32_t n, int32_t W, int32_t filler, int32_t* tasks_out
  * (ext != 0: the operand is external, leading dimension ldp) run on the 128 x 128 tile kernel -- the one whose assign form lets the
  * camera-first trial run the segments' products beside the update?  Host code only; ESL_UPD_V=0 answers no everywhere. */
 int esl_debug_update_v_applies(int64_t lda, int64_t rows, int64_t base, int64_t col_limit, int32_t ext, int64_t ldp, int32_t* applies_out);
+/* test / debug: the camera segment length (16, 32 or 48) the camera-first trial's layout chooses for its one-sided assembly of T when
+ * ESL_CF_STRIDE is unset, from a graph's counts with segments of one, two and three chunks of 16 cameras: flops the separators' rank-K
+ * update executes, entry-products of the assembly, elements of the segments' slabs.  n_o = order of the reduced system (16 below
+ * 8,192).  ms_out (may be null): the cost model's milliseconds per trial for the three.  Host code only. */
+int esl_debug_cf_stride_choose(int64_t n_o, const double upd_flops[3], const double pairs[3], const double slab[3], int32_t* stride_out, double ms_out[3]);
 
 #ifdef __cplusplus
 }

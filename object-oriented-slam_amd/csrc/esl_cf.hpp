@@ -300,7 +300,8 @@ constexpr int kCfFwdCh = 16;
 //   not this kernel's (they fall outside [beg, end)).
 // MODE 1 (SEP): the same recurrence over the separators (nf = number of separators, M = the separator chain's blocks), V dense from
 //   R (k_cf_sep_rhs), rows written at the separators' slots k sep_stride + sep_stride - 1 (sep_stride = 0: at row block k).
-// MODE 2 (X is sparse, see "sparse interior rows" below): segments of kCfFwdCh slots, workgroup = entry of the work list
+// MODE 2 (X is sparse, see "sparse interior rows" below): segments of `stride` slots = one, two or three chunks (the chunk loop
+//   carries x over the chunk boundaries; the slab's rows run on through the segment), workgroup = entry of the work list
 //   (segment p, group of 64 COMPACT columns); compact column 9 i + b = column b of the i-th ellipsoid of the segment's list, the
 //   column after the last one = the right-hand side; rows go to the segment's slab Xc (xoff / xld), acc to R at the T column.
 constexpr int kCfSyT = 128;     // tile of the per-segment product kernel (compact columns)
@@ -753,8 +754,8 @@ __device__ __forceinline__ void cf_obj_update_one(const DevGraph& g, double lamb
 // Column o of X = G^-1 W is zero over segment p unless a camera INSIDE p sees ellipsoid o (the recurrence X_j = V_j - M_j X_{j-1}
 // starts from zero at every segment), and non-zero only from the first such camera on.  A camera sees ~20 ellipsoids (the
 // reference adds one bbox edge per detection, Optimizer.cpp:166-245), so over a 15-camera segment ~13 % of the C4 columns are
-// live: the dense rank-6(F-1) update T -= X^T X spends 98 % of its 1.9e13 flops on zeros.  With the dissection stride fixed at
-// kCfFwdCh = 16:
+// live: the dense rank-6(F-1) update T -= X^T X spends 98 % of its 1.9e13 flops on zeros.  With the dissection stride at
+// kCfFwdCh = 16 (forms 1 and 2; form 3 also runs segments of two and three chunks, "choosing the segment length" below):
 //   interior rows: compact slabs Xc_p [kCfSegRows][xld_p], columns = the segment's list (k_cf_forward<2>);
 //   T(o1, o2) = D(o1) [o1 == o2] - sum over the segments p that list BOTH (bitmap AND), rows from the later first camera on, of
 //               Xc_p(:, o1)^T Xc_p(:, o2)                                   k_cf_T_sparse: output stationary, one wave per 9 x 9 block,
@@ -837,12 +838,13 @@ static __global__ __launch_bounds__(256) void k_cf_T_sparse(int N, int nw, const
 // z = y - X x_o with the interior rows in the slabs: one workgroup per row (slot i, component a)
 // xo_t: x_o in T's column order (= xo unless T's ellipsoids are permuted, CfSegs::rank): what a separator's dense row meets
 static __global__ __launch_bounds__(256) void k_cf_z_sparse(int n_o, const double* __restrict__ Xs, long ldx, CfSegs sg, const double* __restrict__ Xc,
-                                                            const double* __restrict__ xo, const double* __restrict__ xo_t, double* __restrict__ z) {
+                                                            const double* __restrict__ xo, const double* __restrict__ xo_t, double* __restrict__ z,
+                                                            int stride) {
   __shared__ double red[4];
   const int t = blockIdx.x, i = t / 6, a = t - 6 * i;
-  const int p = i / kCfFwdCh, pos = i - p * kCfFwdCh;
+  const int p = i / stride, pos = i - p * stride;
   double s = 0, y;
-  if (pos == kCfFwdCh - 1) {   // separator p: a dense row
+  if (pos == stride - 1) {   // separator p: a dense row
     const double* row = Xs + (size_t)(6 * p + a) * (size_t)ldx;
     for (int o = threadIdx.x; o < n_o; o += 256) s += row[o] * xo_t[o];
     y = row[n_o];
@@ -1048,25 +1050,30 @@ static __global__ __launch_bounds__(256) void k_cf_T_gather(int N, int nw, const
 //   k_cf_seg_back    behind k_cf_forward<2>, same work list (segment, 64 compact columns), lane = column: the segment's own backward
 //                    sweep Y_i = X_i - G_i Z_{i+1}, Z_i = L_ii^-T Y_i from the last interior slot down (the coupling of the last slot to
 //                    the separator is not part of L_p).  One 432-byte record per (compact ellipsoid, interior slot), [b][a] like V:
-//                    Y[((seg_start[p] + i) 15 + pos) 54 + 6 b + a]; the right-hand side's column to Yr[6 slot + a].
+//                    Y[((seg_start[p] + i) (stride - 1) + pos) 54 + 6 b + a]; the right-hand side's column to Yr[6 slot + a].
 //   k_cf_T_onesided  ownership and order of k_cf_T_gather (one wave per block of T, lower triangle + the b row, the segments two
 //                    ellipsoids share, ascending); per segment o1's entries in list order, each a 9 x 6 . 6 x 9 product on
 //                    v_mfma_f64_16x16x4 with the block's pairs concatenated along K (zero padded to a multiple of four at the
 //                    block's end).  The b row walks o2's entries against Yr.  No atomics.
-constexpr int kCfSegInt = kCfFwdCh - 1;   // interior slots of a segment
+// A segment is M chunks of kCfFwdCh slots (M = 1, 2, 3: stride 16, 32, 48), its last slot the separator: 16 M - 1 interior slots.  The
+// lane's column does not fit registers beyond one chunk (M = 3: 282 doubles), so the sweep goes backward chunk by chunk -- a chunk's
+// rows in flight together, Z of the slot behind carried over the chunk boundary.  M = 1 is the one-chunk kernel as it was.
+template <int M>
 static __global__ __launch_bounds__(64) void k_cf_seg_back(int nf_all, const int* __restrict__ fwork, const int* __restrict__ seg_start,
                                                            const long long* __restrict__ xoff, const int* __restrict__ xld,
                                                            const double* __restrict__ Xc, const double* __restrict__ Linv,
                                                            const double* __restrict__ Gfac, double* __restrict__ Y, double* __restrict__ Yr) {
-  __shared__ double sLi[kCfSegInt * 36], sG[kCfSegInt * 36];
+  constexpr int SI = M * kCfFwdCh - 1;           // interior slots of a segment
+  constexpr int CL = M == 1 ? SI : kCfFwdCh;     // slots of a chunk (the last chunk of M > 1 has one less: the separator)
+  __shared__ double sLi[SI * 36], sG[SI * 36];
   const int lane = threadIdx.x;
   const int p = fwork[2 * blockIdx.x], j = fwork[2 * blockIdx.x + 1] * 64 + lane;
   const int ob = seg_start[p], m = 9 * (seg_start[p + 1] - ob);   // column m = the right-hand side
-  const int beg = p * kCfFwdCh;
-  const int len = (beg + kCfSegInt < nf_all ? beg + kCfSegInt : nf_all) - beg;
+  const int beg = p * (M * kCfFwdCh);
+  const int len = (beg + SI < nf_all ? beg + SI : nf_all) - beg;
   if (len <= 0) return;
   {   // the segment's L_ii^-1 and G_i -> LDS (fixed trip count, clamped addresses: the loads go out together)
-    constexpr int kQ = (kCfSegInt * 36 + 63) / 64;
+    constexpr int kQ = (SI * 36 + 63) / 64;
     double tl[kQ], tg[kQ];
 #pragma unroll
     for (int q = 0; q < kQ; ++q) {
@@ -1074,42 +1081,83 @@ static __global__ __launch_bounds__(64) void k_cf_seg_back(int nf_all, const int
       tl[q] = Linv[(size_t)beg * 36 + cl]; tg[q] = Gfac[(size_t)beg * 36 + cl];
     }
 #pragma unroll
-    for (int q = 0; q < kQ; ++q) if (q * 64 + lane < kCfSegInt * 36) { sLi[q * 64 + lane] = tl[q]; sG[q * 64 + lane] = tg[q]; }
+    for (int q = 0; q < kQ; ++q) if (q * 64 + lane < SI * 36) { sLi[q * 64 + lane] = tl[q]; sG[q * 64 + lane] = tg[q]; }
   }
   const bool on = j <= m, rhs = j == m;
   const size_t ld = (size_t)xld[p];
   const double* X = Xc + (size_t)xoff[p] + (on ? j : 0);
-  double x[kCfSegInt * 6];   // the lane's column of the slab: all loads in flight together
-#pragma unroll
-  for (int q = 0; q < kCfSegInt * 6; ++q) x[q] = X[(size_t)(q < len * 6 ? q : 0) * ld];
-  __builtin_amdgcn_wave_barrier();
   const int oi = rhs ? 0 : (on ? j / 9 : 0), b = on ? j - 9 * oi : 0;
-  double* dst = rhs ? Yr + (size_t)beg * 6 : Y + ((size_t)(ob + oi) * kCfSegInt) * 54 + b * 6;
+  double* dst = rhs ? Yr + (size_t)beg * 6 : Y + ((size_t)(ob + oi) * SI) * 54 + b * 6;
   const int dstep = rhs ? 6 : 54;
   double z[6] = {0, 0, 0, 0, 0, 0};   // Z of the slot behind (nothing behind the last interior slot)
 #pragma unroll
-  for (int ii = kCfSegInt - 1; ii >= 0; --ii) {
-    if (ii >= len) continue;
-    double y[6];
+  for (int c = M - 1; c >= 0; --c) {
+    const int s0 = c * kCfFwdCh;   // the chunk's first slot of the segment
+    if (s0 >= len && c < M - 1) continue;   // (a short last segment; the barrier below is the first pass's)
+    double x[CL * 6];   // the chunk's rows of the lane's column of the slab: all loads in flight together
 #pragma unroll
-    for (int a = 0; a < 6; ++a) {
-      double t = x[ii * 6 + a];
+    for (int q = 0; q < CL * 6; ++q) x[q] = X[(size_t)(s0 * 6 + q < len * 6 ? s0 * 6 + q : 0) * ld];
+    if (c == M - 1) __builtin_amdgcn_wave_barrier();
 #pragma unroll
-      for (int q = 0; q < 6; ++q) t -= sG[ii * 36 + a * 6 + q] * z[q];
-      y[a] = t;
-    }
+    for (int ii = CL - 1; ii >= 0; --ii) {
+      if (s0 + ii >= len) continue;
+      double y[6];
 #pragma unroll
-    for (int a = 0; a < 6; ++a) {
-      double t = 0;
+      for (int a = 0; a < 6; ++a) {
+        double t = x[ii * 6 + a];
 #pragma unroll
-      for (int q = a; q < 6; ++q) t += sLi[ii * 36 + q * 6 + a] * y[q];
-      z[a] = t;
-    }
-    if (on) {
+        for (int q = 0; q < 6; ++q) t -= sG[(s0 + ii) * 36 + a * 6 + q] * z[q];
+        y[a] = t;
+      }
 #pragma unroll
-      for (int a = 0; a < 6; ++a) dst[(size_t)ii * dstep + a] = y[a];
+      for (int a = 0; a < 6; ++a) {
+        double t = 0;
+#pragma unroll
+        for (int q = a; q < 6; ++q) t += sLi[(s0 + ii) * 36 + q * 6 + a] * y[q];
+        z[a] = t;
+      }
+      if (on) {
+#pragma unroll
+        for (int a = 0; a < 6; ++a) dst[(size_t)(s0 + ii) * dstep + a] = y[a];
+      }
     }
   }
+}
+
+// ---- choosing the segment length of form 3 -------------------------------------------------------------------------------------------
+// Every stride-th camera is a separator, and the separators' dense rows cost a rank-6 (F / stride) update of T: that shrinks as
+// 1 / stride, while the one-sided assembly's entry-products and the slabs grow with the segment (sublinearly: a wider segment sees
+// more ellipsoids, but not twice as many).  With no stored products nothing else depends on the stride, so per trial
+//     ms(stride) = update flops executed under the staircase / kCfUpdFlopsPerMs + entry-products x kCfPairMs + slab elements x kCfSlabMs
+// (+ what does not depend on the stride) from counts the layout takes on the host for 16, 32 and 48.  The update's and the slabs'
+// rates are the measured ones of the stride-16 form at 10k cameras and 2k ellipsoids (profiles/cf_onesided_gather_c4.md, sections
+// 3 and 4):
+//   k_chol_update_v        16.1 ms = 0.83 of the FP64 MFMA peak (79 TFLOP/s) on the flops it executes;
+//   k_cf_forward<2> + k_cf_seg_back   0.77 + 0.53 ms over slabs of 1.35e8 elements (165 k live (segment, ellipsoid) columns x 9 x 90 rows).
+// The assembly's 4.25 ms for 31.05 M entry-products there (0.137 ms per million) is an AVERAGE, and one point cannot tell what of
+// it grows with the pairs: measured at the three strides (profiles/cf_stride_c4.md: 4.21 / 6.32 / 7.82 ms for 31.05 / 57.57 / 77.35 M)
+// k_cf_T_onesided_lds takes 1.8 ms for its walk over T's 2 M blocks, whatever their lists hold, and 0.078 ms per million
+// entry-products on top.  The marginal rate is the one a comparison of strides needs.
+// A wider stride must win by kCfStrideMargin of the stride-16 figure: the rates move with the shapes (the update's C tile weighs more
+// against a shorter K loop), and below that the choice is within what the model can tell.  Ties go to the narrower stride.
+constexpr double kCfUpdFlopsPerMs = 0.83 * 79.0e9;
+constexpr double kCfPairMs = (7.82 - 4.21) / (77.35e6 - 31.05e6);
+constexpr double kCfSlabMs = 1.30 / 1.35e8;
+constexpr double kCfStrideMargin = 0.05;
+inline double cf_stride_cost(double upd_flops, double pairs, double slab) {
+  return upd_flops / kCfUpdFlopsPerMs + pairs * kCfPairMs + slab * kCfSlabMs;
+}
+// upd_flops / pairs / slab [m - 1]: the counts with segments of m chunks.  n_o = order of the reduced system.
+inline int cf_stride_choose(long n_o, const double* upd_flops, const double* pairs, const double* slab) {
+  if (n_o < 8192) return kCfFwdCh;   // (below: the update is not the launch that carries the build)
+  const double base = cf_stride_cost(upd_flops[0], pairs[0], slab[0]);
+  int best = 1;
+  double best_ms = base * (1.0 - kCfStrideMargin);
+  for (int m = 2; m <= 3; ++m) {
+    const double ms = cf_stride_cost(upd_flops[m - 1], pairs[m - 1], slab[m - 1]);
+    if (ms < best_ms) { best = m; best_ms = ms; }
+  }
+  return best * kCfFwdCh;
 }
 
 // The pair list of a layout: which records a block of T multiplies does not change from trial to trial, so the lookups -- the AND of
@@ -1121,7 +1169,7 @@ static __global__ __launch_bounds__(64) void k_cf_seg_back(int nf_all, const int
 // `offsets` != 0 (k_cf_T_onesided_lds): the pair holds what that kernel would multiply out, the records' first elements -- entry x 54,
 // Y record x 54, slot x 6; the host checked that they fit 32 bits (cf_ensure_impl).  0: record numbers (k_cf_T_onesided).
 template <bool FILL>
-static __global__ __launch_bounds__(256) void k_cf_os_list(int N, int nw, int n_chunks, const unsigned long long* __restrict__ mask,
+static __global__ __launch_bounds__(256) void k_cf_os_list(int N, int nw, int n_chunks, int seg_chunks, const unsigned long long* __restrict__ mask,
                                                            const int* __restrict__ cmap, const int* __restrict__ seg_start,
                                                            const int* __restrict__ oe_cst, const int* __restrict__ oe_slot,
                                                            const int* __restrict__ unrank, const long long* __restrict__ bstart,
@@ -1132,6 +1180,7 @@ static __global__ __launch_bounds__(256) void k_cf_os_list(int N, int nw, int n_
   const int N1 = N + 1;
   const bool rhs = o1 == N;
   const int m54 = offsets ? 54 : 1, m6 = offsets ? 6 : 1;
+  const int stride = seg_chunks * kCfFwdCh;   // segment p = chunks [seg_chunks p, seg_chunks p + seg_chunks) of the entry-range table
   for (int q = wave; q < kCfTPer; q += 4) {
     const int t2 = (int)blockIdx.y * kCfTPer + q;
     if (t2 > t1 || t2 >= N) continue;
@@ -1146,8 +1195,9 @@ static __global__ __launch_bounds__(256) void k_cf_os_list(int N, int nw, int n_
       // lane = bit: entry range and first Y record of all 64 segments of this word in one round trip
       const int pl = wd * 64 + lane;
       const bool mine = (mk >> lane) & 1ull;
-      const int kal = mine ? cst[pl] : 0, kbl = mine ? cst[pl + 1] : 0;
-      const int yrl = (mine && !rhs) ? (seg_start[pl] + (cmap[(size_t)pl * N1 + o2] & 0xFFFFFF)) * kCfSegInt : 0;
+      const int che = seg_chunks * (pl + 1) < n_chunks ? seg_chunks * (pl + 1) : n_chunks;   // (a short last segment)
+      const int kal = mine ? cst[seg_chunks * pl] : 0, kbl = mine ? cst[che] : 0;
+      const int yrl = (mine && !rhs) ? (seg_start[pl] + (cmap[(size_t)pl * N1 + o2] & 0xFFFFFF)) * (stride - 1) : 0;
       while (mk) {
         const int bit = __builtin_ctzll(mk);
         mk &= mk - 1;
@@ -1155,12 +1205,12 @@ static __global__ __launch_bounds__(256) void k_cf_os_list(int N, int nw, int n_
         const int ka = __builtin_amdgcn_readlane(kal, bit), kb = __builtin_amdgcn_readlane(kbl, bit), yr = __builtin_amdgcn_readlane(yrl, bit);
         for (int k0 = ka; k0 < kb; k0 += 64) {   // lane = entry: the prefix count keeps the list order
           const int ent = k0 + lane;
-          const int pos = ent < kb ? oe_slot[ent] - p * kCfFwdCh : kCfFwdCh - 1;
-          const bool valid = pos != kCfFwdCh - 1;   // (the separator's entries are not the assembly's)
+          const int pos = ent < kb ? oe_slot[ent] - p * stride : stride - 1;
+          const bool valid = pos != stride - 1;   // (the separator's entries are not the assembly's)
           const unsigned long long vb = __ballot(valid);
           if (FILL && valid) {
             const int at = cnt + __builtin_popcountll(vb & ((1ull << lane) - 1ull));
-            pairs[w0 + at] = rhs ? make_int2((p * kCfFwdCh + pos) * m6, ent * m54) : make_int2(ent * m54, (yr + pos) * m54);
+            pairs[w0 + at] = rhs ? make_int2((p * stride + pos) * m6, ent * m54) : make_int2(ent * m54, (yr + pos) * m54);
           }
           cnt += __builtin_popcountll(vb);
         }

@@ -289,7 +289,8 @@ struct esl_ctx {
          *cf_NS = nullptr, *cf_R = nullptr;
   double *cf_Xt = nullptr, *cf_T = nullptr, *cf_Linv_ws = nullptr, *cf_part = nullptr;
   int64_t cf_ldx = 0, cf_kpad = 0, cf_ldt = 0;
-  // sparse interior rows of X (esl_cf.hpp, "X is sparse"): segments of kCfFwdCh slots; per segment the sorted list of ellipsoids
+  // sparse interior rows of X (esl_cf.hpp, "X is sparse"): segments of cf_stride slots (kCfFwdCh; form 3: one, two or three chunks
+  // of kCfFwdCh); per segment the sorted list of ellipsoids
   // with an edge at one of its interior cameras (seg_start / seg_obj), the column map cmap[p (N + 1) + o] = first << 24 | index
   // (-1: column o of X is zero over segment p; entry N = the right-hand side), per ellipsoid the bitmap of its segments, the
   // compact slabs Xc (xoff / xld) and the separators' dense rows Xs
@@ -377,4 +378,7 @@ struct esl_ctx {
   // ESL_CF_OS_KERNEL as read when the context was created (A/B and tests): 1 (default) the one-sided assembly feeds whole records
   // through LDS (k_cf_T_onesided_lds), 0 the per-lane gather (k_cf_T_onesided).  Same bits either way.
   int sw_cf_os_kernel = 1;
+  // ESL_CF_STRIDE as read when the context was created: 16, 32 or 48 forces the segment length of the sparse form where T is
+  // assembled one-sided (form 3); 0 (unset) = chosen at layout time from the graph's counts (esl_cf.hpp, cf_stride_cost)
+  int sw_cf_stride = 0;
 };

@@ -325,7 +325,8 @@ static int cf_ensure(esl_ctx* c) {
 // camera system, or that is sharded over ranks, never pays for them):
 //   - every ellipsoid's free-camera edges sorted by (slot, u), and the entry range of every (ellipsoid, chunk of kCfFwdCh slots) in
 //     those lists: the forward substitution's gather phase;
-//   - when X = L^-1 W is kept SPARSE over runs of cameras (esl_cf.hpp): per segment of kCfFwdCh slots (the last one the separator)
+//   - when X = L^-1 W is kept SPARSE over runs of cameras (esl_cf.hpp): per segment of S slots (the last one the separator; S = kCfFwdCh,
+//     or with the one-sided assembly what cf_stride_choose / ESL_CF_STRIDE says)
 //     the ellipsoids seen by its interior cameras, where each one's column starts, per ellipsoid the bitmap of its segments, the
 //     work lists of the per-segment kernels;
 //   - the factor of the camera block, V, X (slabs or dense), T and its solver workspace.
@@ -353,40 +354,46 @@ static int cf_ensure_impl(esl_ctx* c) {
   // ellipsoid) -- the compact column order of a segment's slab (upper-trapezoidal: column c is zero above row 6 first(c); a tile of
   // the segment's product starts at the first camera of its first column) -- with no sort at all.
   const bool want_sp = c->cf_chain_ok && nfi >= 256 && N > 0 && (size_t)nch * (size_t)(N + 1) <= ((size_t)1 << 28) && !std::getenv("ESL_CF_NO_ND");
-  const int nseg = nch, nw = (nseg + 63) / 64, N1 = N + 1;
+  // S = segment length of the sparse form: kCfFwdCh, or with the one-sided assembly (form 3) two or three chunks (chosen below)
+  int S = kCfFwdCh, nseg = nch, nw = (nseg + 63) / 64;
+  const int N1 = N + 1;
   std::vector<int> os(nue), ou(nue);
   std::vector<int> inc_p, inc_o, inc_first;
   std::vector<int> seg_start, xld, fw_off;
   std::vector<long long> xoff, boff, roff, tw_off;
-  size_t n_fwork = 0, n_twork = 0;
-  double fl = 0;
-  {
+  size_t n_fwork = 0, n_twork = 0, n_inc = 0;
+  // the walk and the segments' tables for segments of S slots
+  auto walk = [&](int sS) {
+    S = sS; nseg = (nfi + S - 1) / S; nw = (nseg + 63) / 64;
+    inc_p.clear(); inc_o.clear(); inc_first.clear();
     std::vector<int> cur(start.begin(), start.end() - 1), last_seg(want_sp ? (size_t)N : 0, -1);
     const int* cstart = c->h_cu_start; const int* cobj = c->h_cu_obj; const int* cid = c->h_cu_id;
     if (want_sp) { inc_p.reserve(nue / 4 + 16); inc_o.reserve(nue / 4 + 16); inc_first.reserve(nue / 4 + 16); }
     for (int sl = 0; sl < nfi; ++sl) {
-      const int p = sl / kCfFwdCh, pos = sl - p * kCfFwdCh;
-      const bool interior = want_sp && pos != kCfFwdCh - 1;   // (the last slot of a segment is its separator)
+      const int p = sl / S, pos = sl - p * S;
+      const bool interior = want_sp && pos != S - 1;   // (the last slot of a segment is its separator)
       for (int q = cstart[sl]; q < cstart[sl + 1]; ++q) {
         const int o = cobj[q], at = cur[o]++;
         os[at] = sl; ou[at] = cid[q];
         if (interior && last_seg[o] != p) { last_seg[o] = p; inc_p.push_back(p); inc_o.push_back(o); inc_first.push_back(pos); }
       }
     }
-  }
-  const size_t n_inc = inc_p.size();
-  if (want_sp) {
+    n_inc = inc_p.size();
+    if (!want_sp) return;
+    double fl = 0;
+    // rows of a slab: the padded kCfSegRows of the one-chunk forms' kernels, else the segment's interior rows as they are
+    const long long rows = S == kCfFwdCh ? kCfSegRows : 6 * (S - 1);
     seg_start.assign((size_t)nseg + 1, 0); xld.assign((size_t)nseg, 0); fw_off.assign((size_t)nseg + 1, 0);
     xoff.assign((size_t)nseg + 1, 0); boff.assign((size_t)nseg + 1, 0); roff.assign((size_t)nseg + 1, 0); tw_off.assign((size_t)nseg + 1, 0);
     for (size_t q = 0; q < n_inc; ++q) ++seg_start[(size_t)inc_p[q] + 1];
     for (int p = 0; p < nseg; ++p) seg_start[(size_t)p + 1] += seg_start[p];
     for (size_t q = 0; q < n_inc; ++q)    // block row k of the product: k + 1 blocks, rows from its first camera on
-      fl += 81.0 * (double)(q - (size_t)seg_start[inc_p[q]] + 1) * (6.0 * (kCfFwdCh - 1 - inc_first[q]));
+      fl += 81.0 * (double)(q - (size_t)seg_start[inc_p[q]] + 1) * (6.0 * (S - 1 - inc_first[q]));
     for (int p = 0; p < nseg; ++p) {
       const int cnt = seg_start[(size_t)p + 1] - seg_start[p];
       const int m = 9 * cnt + 1;
       xld[p] = (m + 15) / 16 * 16 + 16;                          // + 16: the T kernel reads 16 columns from any column start
-      xoff[(size_t)p + 1] = xoff[p] + (long long)kCfSegRows * xld[p];
+      xoff[(size_t)p + 1] = xoff[p] + rows * xld[p];
       fw_off[(size_t)p + 1] = fw_off[p] + (m + 63) / 64;
       boff[(size_t)p + 1] = boff[p] + (long long)cnt * (cnt + 1) / 2;
       roff[(size_t)p + 1] = roff[p] + 9LL * cnt;
@@ -398,6 +405,9 @@ static int cf_ensure_impl(esl_ctx* c) {
     c->cf_xc_len = (size_t)xoff[nseg] + 2 * kCfSyT;   // (+: the product kernel's last tile reads past the last slab's columns)
     c->cf_n_twork = (int)n_twork; c->cf_p_blocks = (size_t)boff[nseg]; c->cf_prhs_len = (size_t)roff[nseg];
     c->cf_sp_built = true;
+  };
+  walk(kCfFwdCh);
+  if (want_sp) {
     // X sparse or dense (esl_cf.hpp, "sparse interior rows"): flops of the dense rank-6 nf update against the separators' dense
     // rows plus the per-segment products at a quarter of the MFMA rate; ESL_CF_SPARSE=1 / 0 forces it (A/B and the parity tests)
     const double dense = (double)n_o * (double)n_o * 6.0 * (double)nf;
@@ -422,48 +432,37 @@ static int cf_ensure_impl(esl_ctx* c) {
     if (!c->cf_sparse) c->cf_sp_built = false;   // (none of the sparse-form tables are shipped)
   }
   const bool sp = c->cf_sparse;
-  // nested dissection of the camera chain from 48 free cameras on: stride = 16 x round(sqrt(nf) / 16) in [16, 128] (a multiple
-  // of the forward substitution's chunk, so that segments start on chunk boundaries), kCfFwdCh when X is kept sparse;
-  // ESL_CF_NO_ND=1 keeps the plain chain (A/B)
-  c->cf_stride = 0; c->cf_n_sep = 0; c->cf_n_seg = 1;
-  // (ESL_CF_ND_MIN: first free-camera count that is dissected -- default 48, three segments; 128 until round 6: at 119 free cameras the
-  //  plain chain's two serial sweeps, k_cf_chain 72 us + k_cf_forward 69 us, were a quarter of a streaming-size trial)
-  static const size_t nd_min = [] { const char* e = std::getenv("ESL_CF_ND_MIN"); const int v = e ? std::atoi(e) : 48; return (size_t)std::max(v, 2 * kCfFwdCh); }();
-  const bool nd = nf >= nd_min && !std::getenv("ESL_CF_NO_ND");
-  if (nd) {
-    int sd = 16 * (int)std::max(1.0, std::floor(std::sqrt((double)nf) / 16.0 + 0.5));
-    sd = std::min(sd, kCfMaxStride);
-    if (sp) sd = kCfFwdCh;
-    c->cf_stride = sd; c->cf_n_sep = (int)(nf / sd); c->cf_n_seg = (int)((nf + sd - 1) / sd);
-  }
   // T's ellipsoids by first free camera (sparse form; ESL_CF_TPERM=0: ellipsoid order, A/B): rank by a counting sort over the
-  // first slot of every ellipsoid's (slot-sorted) list, ellipsoids without a free-camera edge last; kfirst per 64 columns of T: the
-  // first separator whose right-hand side R(k) can hold the column's ellipsoid is the one in FRONT of the segment of its first
-  // camera (an interior camera's segment hands its sum to the separator before it; conservative for a separator camera itself),
-  // and the right-hand side's ROW (row n_o of T, X^T y) is dense from the start
-  std::vector<int> h_rank, h_unrank, h_kfirst;
-  double upd_flops = 0;
+  // first slot of every ellipsoid's (slot-sorted) list, ellipsoids without a free-camera edge last
+  std::vector<int> h_rank, h_unrank, h_kfirst, first;
   const bool tperm = sp && N > 0 && !(std::getenv("ESL_CF_TPERM") && std::getenv("ESL_CF_TPERM")[0] == '0');
   if (tperm) {
-    std::vector<int> first((size_t)N, nfi), cnt((size_t)nfi + 2, 0);
+    std::vector<int> cnt((size_t)nfi + 2, 0);
+    first.assign((size_t)N, nfi);
     for (int o = 0; o < N; ++o) if (start[(size_t)o + 1] > start[o]) first[o] = os[(size_t)start[o]];
     for (int o = 0; o < N; ++o) ++cnt[(size_t)first[o] + 1];
     for (int s2 = 0; s2 <= nfi; ++s2) cnt[(size_t)s2 + 1] += cnt[s2];
     h_rank.assign((size_t)N, 0); h_unrank.assign((size_t)N, 0);
     for (int o = 0; o < N; ++o) { const int t = cnt[first[o]]++; h_rank[o] = t; h_unrank[t] = o; }
-    const int Ks = (int)((6 * (size_t)c->cf_n_sep + kKC - 1) / kKC * kKC);
+  }
+  // kfirst per 64 columns of T for segments of sS slots: the first separator whose right-hand side R(k) can hold the column's
+  // ellipsoid is the one in FRONT of the segment of its first camera (an interior camera's segment hands its sum to the separator
+  // before it; conservative for a separator camera itself), and the right-hand side's ROW (row n_o of T, X^T y) is dense from the
+  // start.  Returns the flops the update executes (k_chol_update_v, the default tile of the big launches): per 128 x 128 tile of the
+  // lower triangle, K from the later of the tile's two earliest rows on, rounded down to a chunk pair as the kernel does; a tile on
+  // the diagonal counts its lower triangle.  (The 256 x 128 tile of ESL_UPD_V=0 starts a little earlier: it executes ~1 % more.)
+  auto staircase = [&](int sS) {
+    double upd_flops = 0;
+    const int Ks = (int)((6 * (nf / (size_t)sS) + kKC - 1) / kKC * kKC);
     const size_t ng = (n_o + 1 + 256) / 64 + 8;
     h_kfirst.assign(ng, Ks);
     for (size_t col = 0; col < n_o; ++col) {
       const int o = h_unrank[col / 9];
-      const int k0 = std::max(0, first[o] / kCfFwdCh - 1);
+      const int k0 = std::max(0, first[o] / sS - 1);
       const int row = std::min(6 * k0, Ks);
       h_kfirst[col / 64] = std::min(h_kfirst[col / 64], row);
     }
     h_kfirst[n_o / 64] = 0;   // the right-hand side's row
-    // flops the update executes (k_chol_update_v, the default tile of the big launches): per 128 x 128 tile of the lower triangle, K from
-    // the later of the tile's two earliest rows on, rounded down to a chunk pair as the kernel does; a tile on the diagonal counts its
-    // lower triangle.  (The 256 x 128 tile of ESL_UPD_V=0 starts a little earlier: it executes ~1 % more.)
     const long nti = ((long)n_o + 1 + 127) / 128;
     for (long ti = 0; ti < nti; ++ti) {
       const int ka = std::min(h_kfirst[(size_t)(ti * 2)], h_kfirst[(size_t)(ti * 2 + 1)]);
@@ -476,35 +475,74 @@ static int cf_ensure_impl(esl_ctx* c) {
         upd_flops += 2.0 * rows_t * cols_t * (double)(Ks - ks) * in_triangle;
       }
     }
-  }
-  c->cf_tperm = tperm; c->cf_upd_flops = upd_flops;
-  c->cf_y_len = 0; c->cf_os_flops = 0;
-  if (sp && c->cf_sp_form == 3) {
-    // what the one-sided assembly executes: per block (t1 >= t2) of T and shared segment, one 9 x 6 . 6 x 9 product per interior
-    // list entry of o1 in the segment; the b row one 6 x 9 . 6 product per interior entry.  (Segment, position in T's order,
-    // entries) of every incidence, by segment and position: the incidence at place q of its segment meets q + 1 partners.
+    return upd_flops;
+  };
+  // what the one-sided assembly executes with segments of sS slots: per block (t1 >= t2) of T and shared segment, one 9 x 6 . 6 x 9
+  // product per interior list entry of o1 in the segment; the b row one 6 x 9 . 6 product per interior entry.  (Segment, position in
+  // T's order, entries) of every incidence, by segment and position: the incidence at place q of its segment meets q + 1 partners.
+  auto os_counts = [&](int sS, double& prod, double& rhs_entries) {
     std::vector<std::array<int, 3>> inc3;
     inc3.reserve(n_inc);
-    double rhs_entries = 0;
+    prod = 0; rhs_entries = 0;
     for (int o = 0; o < N; ++o) {
       int last_p = -1;
       for (int k = start[o]; k < start[(size_t)o + 1]; ++k) {
         const int sl = os[(size_t)k];
-        if (sl % kCfFwdCh == kCfFwdCh - 1) continue;
-        const int p = sl / kCfFwdCh;
+        if (sl % sS == sS - 1) continue;
+        const int p = sl / sS;
         if (p != last_p) { inc3.push_back({p, tperm ? h_rank[(size_t)o] : o, 0}); last_p = p; }
         ++inc3.back()[2]; rhs_entries += 1;
       }
     }
     std::sort(inc3.begin(), inc3.end());
-    double prod = 0;
     for (size_t q = 0, q0 = 0; q < inc3.size(); ++q) {
       if (inc3[q][0] != inc3[q0][0]) q0 = q;
       prod += (double)inc3[q][2] * (double)(q - q0 + 1);
     }
+  };
+  // The segment length of form 3 (esl_cf.hpp, "choosing the segment length"): ESL_CF_STRIDE as read when the context was created, else
+  // kCfFwdCh unless the reduced system is large enough for the separators' update to carry the launch (9 N >= 8192: k_chol_update_v),
+  // and then what cf_stride_choose makes of this graph's counts.  Every other form, and a run with a communicator, keeps kCfFwdCh.
+  if (sp && c->cf_sp_form == 3 && !c->comm) {
+    int want = c->sw_cf_stride;
+    if (!want && tperm && n_o >= 8192) {
+      double upd[3], pairs[3], slab[3];
+      for (int m = 1; m <= 3; ++m) {
+        double prod, rhs_entries;
+        walk(m * kCfFwdCh);
+        os_counts(S, prod, rhs_entries);
+        long long cols = 0;
+        for (int p = 0; p < nseg; ++p) cols += xld[p];
+        upd[m - 1] = staircase(S); pairs[m - 1] = prod + rhs_entries; slab[m - 1] = 6.0 * (S - 1) * (double)cols;
+      }
+      want = cf_stride_choose((long)n_o, upd, pairs, slab);
+    }
+    if (!want) want = kCfFwdCh;
+    if (want != S) walk(want);
+  }
+  // nested dissection of the camera chain from 48 free cameras on: stride = 16 x round(sqrt(nf) / 16) in [16, 128] (a multiple
+  // of the forward substitution's chunk, so that segments start on chunk boundaries), the segment length S when X is kept sparse;
+  // ESL_CF_NO_ND=1 keeps the plain chain (A/B)
+  c->cf_stride = 0; c->cf_n_sep = 0; c->cf_n_seg = 1;
+  // (ESL_CF_ND_MIN: first free-camera count that is dissected -- default 48, three segments; 128 until round 6: at 119 free cameras the
+  //  plain chain's two serial sweeps, k_cf_chain 72 us + k_cf_forward 69 us, were a quarter of a streaming-size trial)
+  static const size_t nd_min = [] { const char* e = std::getenv("ESL_CF_ND_MIN"); const int v = e ? std::atoi(e) : 48; return (size_t)std::max(v, 2 * kCfFwdCh); }();
+  const bool nd = nf >= nd_min && !std::getenv("ESL_CF_NO_ND");
+  if (nd) {
+    int sd = 16 * (int)std::max(1.0, std::floor(std::sqrt((double)nf) / 16.0 + 0.5));
+    sd = std::min(sd, kCfMaxStride);
+    if (sp) sd = S;
+    c->cf_stride = sd; c->cf_n_sep = (int)(nf / sd); c->cf_n_seg = (int)((nf + sd - 1) / sd);
+  }
+  const double upd_flops = tperm ? staircase(S) : 0.0;
+  c->cf_tperm = tperm; c->cf_upd_flops = upd_flops;
+  c->cf_y_len = 0; c->cf_os_flops = 0;
+  if (sp && c->cf_sp_form == 3) {
+    double prod, rhs_entries;
+    os_counts(S, prod, rhs_entries);
     c->cf_os_flops = 2.0 * 6.0 * (81.0 * prod + 9.0 * rhs_entries);
     c->cf_os_npairs = (size_t)(prod + rhs_entries);   // (record pairs of the assembly: the length of its list)
-    c->cf_y_len = std::max<size_t>(n_inc, 1) * kCfSegInt * 54 + std::max<size_t>(nf, 1) * 6;
+    c->cf_y_len = std::max<size_t>(n_inc, 1) * (size_t)(S - 1) * 54 + std::max<size_t>(nf, 1) * 6;
   }
   const double t1 = timing ? now_us() : 0;
   // ---- layout: what the host ships first, then the device-generated tables (esl_cf.hpp k_cf_make_*), then the buffers ----
@@ -540,7 +578,7 @@ static int cf_ensure_impl(esl_ctx* c) {
     if (c->cf_sp_form == 1) { st.work(&c->cf_P, c->cf_p_blocks * 81); st.work(&c->cf_Prhs, c->cf_prhs_len); }
     if (c->cf_sp_form == 3) {
       const size_t nb = (size_t)N * (N + 1) / 2 + N;   // blocks of T's lower triangle + the b row
-      st.work(&c->cf_Y, std::max<size_t>(n_inc, 1) * kCfSegInt * 54); st.work(&c->cf_Yr, std::max<size_t>(nf, 1) * 6);
+      st.work(&c->cf_Y, std::max<size_t>(n_inc, 1) * (size_t)(S - 1) * 54); st.work(&c->cf_Yr, std::max<size_t>(nf, 1) * 6);
       st.work(&c->cf_os_start, nb + 1); st.work(&c->cf_os_cnt, nb); st.work(&c->cf_os_pairs, 2 * std::max<size_t>(c->cf_os_npairs, 1));
     }
   } else {
@@ -590,10 +628,10 @@ static int cf_ensure_impl(esl_ctx* c) {
     const dim3 grid((unsigned)(N + 1), (unsigned)((N + kCfTPer - 1) / kCfTPer));
     // element offsets for k_cf_T_onesided_lds where every record's first element fits the list's 32 bits (C4: 1.4e8), else record
     // numbers and the per-lane gather
-    const size_t max_off = 54 * std::max<size_t>(EU, std::max<size_t>(n_inc, 1) * kCfSegInt);
+    const size_t max_off = 54 * std::max<size_t>(EU, std::max<size_t>(n_inc, 1) * (size_t)(S - 1));
     c->cf_os_offsets = c->sw_cf_os_kernel != 0 && max_off <= (size_t)INT32_MAX;
     ESL_HIP_TRY(hipMemsetAsync(c->cf_os_cnt, 0, nb * sizeof(int), c->stream));
-    hipLaunchKernelGGL(k_cf_os_list<false>, grid, dim3(256), 0, c->stream, N, nw, nch, c->cf_mask, c->cf_cmap, c->cf_seg_start, c->cf_oe_cst, c->cf_oe_slot,
+    hipLaunchKernelGGL(k_cf_os_list<false>, grid, dim3(256), 0, c->stream, N, nw, nch, S / kCfFwdCh, c->cf_mask, c->cf_cmap, c->cf_seg_start, c->cf_oe_cst, c->cf_oe_slot,
                        (const int*)c->cf_unrank, (const long long*)nullptr, c->cf_os_cnt, (int2*)nullptr, 0);
     std::vector<int> h_cnt(nb);
     std::vector<long long> h_start(nb + 1);
@@ -606,7 +644,7 @@ static int cf_ensure_impl(esl_ctx* c) {
       return ESL_ERR_STATE;
     }
     ESL_HIP_TRY(hipMemcpyAsync(c->cf_os_start, h_start.data(), (nb + 1) * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_cf_os_list<true>, grid, dim3(256), 0, c->stream, N, nw, nch, c->cf_mask, c->cf_cmap, c->cf_seg_start, c->cf_oe_cst, c->cf_oe_slot,
+    hipLaunchKernelGGL(k_cf_os_list<true>, grid, dim3(256), 0, c->stream, N, nw, nch, S / kCfFwdCh, c->cf_mask, c->cf_cmap, c->cf_seg_start, c->cf_oe_cst, c->cf_oe_slot,
                        (const int*)c->cf_unrank, (const long long*)c->cf_os_start, c->cf_os_cnt, (int2*)c->cf_os_pairs, c->cf_os_offsets ? 1 : 0);
     ESL_HIP_TRY(hipStreamSynchronize(c->stream));   // (h_start is read by the copy until here)
   }
@@ -619,7 +657,7 @@ static int cf_ensure_impl(esl_ctx* c) {
     ESL_HIP_TRY(hipMemsetAsync(c->cf_Xs, 0, (size_t)c->cf_ldx * (size_t)c->cf_kpad_s * sizeof(double), c->stream));
     ESL_HIP_TRY(hipMemsetAsync(c->cf_T, 0, (size_t)c->cf_ldt * n_o * sizeof(double), c->stream));
     if (c->cf_sp_form == 3) {   // (the records of slots behind a short last segment's end are never written and never read)
-      ESL_HIP_TRY(hipMemsetAsync(c->cf_Y, 0, std::max<size_t>(n_inc, 1) * kCfSegInt * 54 * sizeof(double), c->stream));
+      ESL_HIP_TRY(hipMemsetAsync(c->cf_Y, 0, std::max<size_t>(n_inc, 1) * (size_t)(S - 1) * 54 * sizeof(double), c->stream));
       ESL_HIP_TRY(hipMemsetAsync(c->cf_Yr, 0, std::max<size_t>(nf, 1) * 6 * sizeof(double), c->stream));
     }
   } else {
@@ -816,8 +854,13 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
       }
       {
         ProfScope pk(c, 8);
-        hipLaunchKernelGGL(k_cf_seg_back, dim3((unsigned)c->cf_n_fwork), dim3(64), 0, c->stream, nf, c->cf_fwork, c->cf_seg_start, c->cf_xoff, c->cf_xld, c->cf_Xc,
-                           c->cf_Linv, c->cf_G, c->cf_Y, c->cf_Yr);
+        auto seg_back = [&](auto mch) {   // (the segment's chunks: the kernel's register arrays want a compile-time length)
+          hipLaunchKernelGGL(k_cf_seg_back<decltype(mch)::value>, dim3((unsigned)c->cf_n_fwork), dim3(64), 0, c->stream, nf, c->cf_fwork, c->cf_seg_start, c->cf_xoff,
+                             c->cf_xld, c->cf_Xc, c->cf_Linv, c->cf_G, c->cf_Y, c->cf_Yr);
+        };
+        if (st == 3 * kCfFwdCh) seg_back(std::integral_constant<int, 3>{});
+        else if (st == 2 * kCfFwdCh) seg_back(std::integral_constant<int, 2>{});
+        else seg_back(std::integral_constant<int, 1>{});
         launch_gather(swap ? 1 : 0);
       }
       ESL_HIP_TRY(hipGetLastError());
@@ -872,7 +915,8 @@ static int slam_try_step_cf(esl_ctx* c, double lambda) {
     if (xsol != c->xo) hipLaunchKernelGGL(k_cf_xo_unpermute, dim3((unsigned)((n_o + 255) / 256)), dim3(256), 0, c->stream, N, c->cf_rank, xsol, c->xo);
     if (c->cf_sparse)
       hipLaunchKernelGGL(k_cf_z_sparse, dim3((unsigned)(6 * nf)), dim3(256), 0, c->stream, n_o, c->cf_Xs, ldx,
-                         CfSegs{c->cf_fwork, c->cf_seg_start, c->cf_seg_obj, c->cf_xoff, c->cf_xld, c->cf_rank, c->cf_unrank}, c->cf_Xc, c->xo, xsol, c->cf_z);
+                         CfSegs{c->cf_fwork, c->cf_seg_start, c->cf_seg_obj, c->cf_xoff, c->cf_xld, c->cf_rank, c->cf_unrank}, c->cf_Xc, c->xo, xsol, c->cf_z,
+                         c->cf_stride);
     else
       hipLaunchKernelGGL(k_cf_z, dim3((unsigned)(6 * nf)), dim3(256), 0, c->stream, c->cf_Xt, ldx, n_o, c->xo, c->cf_z);
     if (c->cf_stride > 0 && c->cf_n_sep > 0) {
@@ -1518,5 +1562,15 @@ extern "C" int esl_debug_chol_plan(int32_t n, int32_t W, int32_t filler, int32_t
 extern "C" int esl_debug_update_v_applies(int64_t lda, int64_t rows, int64_t base, int64_t col_limit, int32_t ext, int64_t ldp, int32_t* applies_out) {
   if (!applies_out) return ESL_ERR_INVALID;
   *applies_out = esl::chol_update_v_applies(esl::chol_switches_from_env(), (long)lda, (long)rows, (long)base, (long)col_limit, ext != 0, (long)ldp) ? 1 : 0;
+  return ESL_OK;
+}
+
+// test / debug: the segment length the layout would choose for form 3 from these counts (esl_cf.hpp, cf_stride_choose), and the
+// model's ms per stride.  A pure host function
+extern "C" int esl_debug_cf_stride_choose(int64_t n_o, const double upd_flops[3], const double pairs[3], const double slab[3], int32_t* stride_out,
+                                          double ms_out[3]) {
+  if (!upd_flops || !pairs || !slab || !stride_out) return ESL_ERR_INVALID;
+  *stride_out = esl::cf_stride_choose((long)n_o, upd_flops, pairs, slab);
+  if (ms_out) for (int m = 0; m < 3; ++m) ms_out[m] = esl::cf_stride_cost(upd_flops[m], pairs[m], slab[m]);
   return ESL_OK;
 }

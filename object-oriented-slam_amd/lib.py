@@ -22,7 +22,7 @@ EXPORTS = [
     "esl_abi_version", "esl_last_error", "esl_device_count", "esl_ctx_create", "esl_ctx_destroy",
     "esl_ctx_synchronize", "esl_ctx_trim", "esl_lm_params_default", "esl_optimize", "esl_optimize_fixed", "esl_graph_upload", "esl_graph_upload_fixed", "esl_graph_obj_fixed", "esl_graph_append", "esl_graph_sizes", "esl_states_upload",
     "esl_states_download", "esl_optimize_resident", "esl_states_snapshot", "esl_states_restore", "esl_profile_enable", "esl_profile_get", "esl_lm_begin", "esl_lm_linearize", "esl_lm_reduced_system", "esl_lm_reduced_residual",
-    "esl_lm_try_step", "esl_lm_commit", "esl_lm_solver_used", "esl_lm_solver_stats", "esl_lm_download", "esl_lm_set_robust", "esl_edge_chi2", "esl_pcg_params_default", "esl_lm_set_pcg", "esl_lm_pcg_stats", "esl_comm_unique_id", "esl_comm_init", "esl_comm_init_host", "esl_comm_set_replicated", "esl_comm_destroy", "esl_partition_objects", "esl_fit_params_default", "esl_fit_frame", "esl_fit_frame_debug", "esl_fit_frame_ex", "esl_selftest_cholesky", "esl_debug_chol_plan", "esl_debug_update_v_applies",
+    "esl_lm_try_step", "esl_lm_commit", "esl_lm_solver_used", "esl_lm_solver_stats", "esl_lm_download", "esl_lm_set_robust", "esl_edge_chi2", "esl_pcg_params_default", "esl_lm_set_pcg", "esl_lm_pcg_stats", "esl_comm_unique_id", "esl_comm_init", "esl_comm_init_host", "esl_comm_set_replicated", "esl_comm_destroy", "esl_partition_objects", "esl_fit_params_default", "esl_fit_frame", "esl_fit_frame_debug", "esl_fit_frame_ex", "esl_selftest_cholesky", "esl_debug_chol_plan", "esl_debug_update_v_applies", "esl_debug_cf_stride_choose",
     "esl_init_quadric", "esl_init_from_qstar", "esl_init_plane_error", "esl_init_quadrics", "esl_plane_params_default", "esl_extract_ground_plane", "esl_extract_planes",
     "esl_reloc_params_default", "esl_reloc_set_map", "esl_relocalize",
     "esl_assoc_params_default", "esl_predict_boxes", "esl_associate_boxes",
@@ -904,6 +904,15 @@ def update_v_applies(lda, rows, base, col_limit, ext=True, ldp=None):
     _check(load().esl_debug_update_v_applies(C.c_int64(lda), C.c_int64(rows), C.c_int64(base), C.c_int64(col_limit), C.c_int32(1 if ext else 0),
                                              C.c_int64(lda if ldp is None else ldp), C.byref(out)), "esl_debug_update_v_applies")
     return bool(out.value)
+
+
+def cf_stride_choose(n_o, upd_flops, pairs, slab):
+    """The camera segment length (16, 32 or 48) the camera-first layout chooses for its one-sided assembly of T from a graph's counts
+    at the three lengths, and the cost model's ms per trial for each (esl_debug_cf_stride_choose; host only)."""
+    arr = lambda v: (C.c_double * 3)(*[float(x) for x in v])
+    out, ms = C.c_int32(0), (C.c_double * 3)()
+    _check(load().esl_debug_cf_stride_choose(C.c_int64(n_o), arr(upd_flops), arr(pairs), arr(slab), C.byref(out), ms), "esl_debug_cf_stride_choose")
+    return int(out.value), [float(x) for x in ms]
 
 
 def partition_objects(graph, n_parts):
