@@ -962,7 +962,8 @@ int esl_debug_update_v_applies(int64_t lda, int64_t rows, int64_t base, int64_t 
 /* test / debug: the camera segment length (16, 32 or 48) the camera-first trial's layout chooses for its one-sided assembly of T when
  * ESL_CF_STRIDE is unset, from a graph's counts with segments of one, two and three chunks of 16 cameras: flops the separators' rank-K
  * update executes, entry-products of the assembly, elements of the segments' slabs.  n_o = order of the reduced system (16 below
- * 8,192).  ms_out (may be null): the cost model's milliseconds per trial for the three.  Host code only. */
+ * 8,192).  ms_out (may be null): the cost model's milliseconds per trial for the three.  Host code only: the rule, like every other
+ * decision of that layout, is in csrc/esl_cf_plan.hpp (cf_stride_choose, cf_plan_build), which tests/cf_plan_main.cpp prints on the CPU. */
 int esl_debug_cf_stride_choose(int64_t n_o, const double upd_flops[3], const double pairs[3], const double slab[3], int32_t* stride_out, double ms_out[3]);
 
 #ifdef __cplusplus

@@ -28,7 +28,11 @@
 // Applicable when every odometry edge joins two cameras whose free-camera slots differ by one (the reference's chain); across GPUs
 // with the replicated-graph communicator (esl_comm_set_replicated: the ranks divide T by outer panels); esl_lm_params::linear_solver
 // selects (include/esl.h).
+//
+// The layout decisions (dense or sparse X, form, segment length, T's order, every table's offsets; kCfFwdCh and the other layout
+// constants) are host-only code in esl_cf_plan.hpp; esl_slam.hip ships the plan (cf_ensure_impl) and enqueues one schedule per form.
 #pragma once
+#include "esl_cf_plan.hpp"   // the layout decisions: kCfFwdCh, kCfSyT, kCfSegRows, kCfMaxStride, cf_stride_choose
 #include "esl_kernels_map.hpp"
 
 namespace esl {
@@ -293,7 +297,6 @@ static __global__ __launch_bounds__(256) void k_cf_edge_scale(DevGraph g, int n_
 //       the MFMA rank-K update wants for its factor.
 // History: list walk inside the loop with the next record prefetched: 1.08 us per camera (a store and a dependent load per step:
 // the compiler's s_waitcnt vmcnt(0) at the loop head made every step wait for the previous step's stores); this form 0.2 us.
-constexpr int kCfFwdCh = 16;
 // MODE 0: blockIdx.y = segment p (cameras [p stride, p stride + seglen); one segment = the plain chain).  With nested
 //   dissection (Zt != null) the lane also accumulates acc = sum_j Zt_j^T X_j over its segment -- the segment's contribution to the
 //   right-hand side of the separator in FRONT of it -- into R[column + (6 (p - 1) + a) ldx]; list entries of separator slots are
@@ -304,8 +307,6 @@ constexpr int kCfFwdCh = 16;
 //   carries x over the chunk boundaries; the slab's rows run on through the segment), workgroup = entry of the work list
 //   (segment p, group of 64 COMPACT columns); compact column 9 i + b = column b of the i-th ellipsoid of the segment's list, the
 //   column after the last one = the right-hand side; rows go to the segment's slab Xc (xoff / xld), acc to R at the T column.
-constexpr int kCfSyT = 128;     // tile of the per-segment product kernel (compact columns)
-constexpr int kCfSegRows = 96;   // rows of a slab: 6 (kCfFwdCh - 1) = 90, padded with zero rows to a multiple of the T kernel's row batch
 // rank / unrank (round 5, null = identity): T's ellipsoids in the order of their FIRST free camera -- column block rank[o] of T, R, Xs
 // belongs to ellipsoid o.  The separators' rows of X are then zero above a staircase (an ellipsoid no camera has seen yet has no
 // entry in any R(k)), and the dense rank-K update skips them tile by tile (esl_chol.hpp, kfirst).
@@ -477,7 +478,6 @@ static __global__ __launch_bounds__(64) void k_cf_forward(int nf_all, int n_o, i
 // kernel on the separator chain).  T = D - X^T X does not care about the row order.  x_c = G^-T z : separators first (backward
 // chain), then z_j -= Zt_j x_s(front) + [j last] G_j x_s(behind) and the per-segment backward recurrences.
 // Serial length: stride - 1 + (F - 1) / stride steps instead of F - 1 (C4: 199 instead of 9,999; C3: 46 instead of 499).
-constexpr int kCfMaxStride = 128;
 // Zt of segment p >= 1 (workgroup p, lanes 0..5 = the six columns)
 static __global__ __launch_bounds__(64) void k_cf_zt(int nf, int stride, const double* __restrict__ Linv, const double* __restrict__ Mm,
                                                      const double* __restrict__ B, double* __restrict__ Zt) {
@@ -1124,42 +1124,6 @@ static __global__ __launch_bounds__(64) void k_cf_seg_back(int nf_all, const int
   }
 }
 
-// ---- choosing the segment length of form 3 -------------------------------------------------------------------------------------------
-// Every stride-th camera is a separator, and the separators' dense rows cost a rank-6 (F / stride) update of T: that shrinks as
-// 1 / stride, while the one-sided assembly's entry-products and the slabs grow with the segment (sublinearly: a wider segment sees
-// more ellipsoids, but not twice as many).  With no stored products nothing else depends on the stride, so per trial
-//     ms(stride) = update flops executed under the staircase / kCfUpdFlopsPerMs + entry-products x kCfPairMs + slab elements x kCfSlabMs
-// (+ what does not depend on the stride) from counts the layout takes on the host for 16, 32 and 48.  The update's and the slabs'
-// rates are the measured ones of the stride-16 form at 10k cameras and 2k ellipsoids (profiles/cf_onesided_gather_c4.md, sections
-// 3 and 4):
-//   k_chol_update_v        16.1 ms = 0.83 of the FP64 MFMA peak (79 TFLOP/s) on the flops it executes;
-//   k_cf_forward<2> + k_cf_seg_back   0.77 + 0.53 ms over slabs of 1.35e8 elements (165 k live (segment, ellipsoid) columns x 9 x 90 rows).
-// The assembly's 4.25 ms for 31.05 M entry-products there (0.137 ms per million) is an AVERAGE, and one point cannot tell what of
-// it grows with the pairs: measured at the three strides (profiles/cf_stride_c4.md: 4.21 / 6.32 / 7.82 ms for 31.05 / 57.57 / 77.35 M)
-// k_cf_T_onesided_lds takes 1.8 ms for its walk over T's 2 M blocks, whatever their lists hold, and 0.078 ms per million
-// entry-products on top.  The marginal rate is the one a comparison of strides needs.
-// A wider stride must win by kCfStrideMargin of the stride-16 figure: the rates move with the shapes (the update's C tile weighs more
-// against a shorter K loop), and below that the choice is within what the model can tell.  Ties go to the narrower stride.
-constexpr double kCfUpdFlopsPerMs = 0.83 * 79.0e9;
-constexpr double kCfPairMs = (7.82 - 4.21) / (77.35e6 - 31.05e6);
-constexpr double kCfSlabMs = 1.30 / 1.35e8;
-constexpr double kCfStrideMargin = 0.05;
-inline double cf_stride_cost(double upd_flops, double pairs, double slab) {
-  return upd_flops / kCfUpdFlopsPerMs + pairs * kCfPairMs + slab * kCfSlabMs;
-}
-// upd_flops / pairs / slab [m - 1]: the counts with segments of m chunks.  n_o = order of the reduced system.
-inline int cf_stride_choose(long n_o, const double* upd_flops, const double* pairs, const double* slab) {
-  if (n_o < 8192) return kCfFwdCh;   // (below: the update is not the launch that carries the build)
-  const double base = cf_stride_cost(upd_flops[0], pairs[0], slab[0]);
-  int best = 1;
-  double best_ms = base * (1.0 - kCfStrideMargin);
-  for (int m = 2; m <= 3; ++m) {
-    const double ms = cf_stride_cost(upd_flops[m - 1], pairs[m - 1], slab[m - 1]);
-    if (ms < best_ms) { best = m; best_ms = ms; }
-  }
-  return best * kCfFwdCh;
-}
-
 // The pair list of a layout: which records a block of T multiplies does not change from trial to trial, so the lookups -- the AND of
 // the two segment bitmaps, the column map, the entry range of (o1, segment), the slot of every entry -- run once per layout
 // (k_cf_os_list, first counting then filling; the host turns the counts into offsets in between).  Block b = t1 (t1 + 1) / 2 + t2 of
@@ -1167,7 +1131,7 @@ inline int cf_stride_choose(long n_o, const double* upd_flops, const double* pai
 // ascending, o1's entries of the segment in list order, entries of the separator's slot left out.
 // pair = (record of the A operand, record of the B operand): (list entry of o1, Y record of o2) -- b row: (slot, list entry of o2).
 // `offsets` != 0 (k_cf_T_onesided_lds): the pair holds what that kernel would multiply out, the records' first elements -- entry x 54,
-// Y record x 54, slot x 6; the host checked that they fit 32 bits (cf_ensure_impl).  0: record numbers (k_cf_T_onesided).
+// Y record x 54, slot x 6; the plan checked that they fit 32 bits (esl_cf_plan.hpp, os_offsets).  0: record numbers (k_cf_T_onesided).
 template <bool FILL>
 static __global__ __launch_bounds__(256) void k_cf_os_list(int N, int nw, int n_chunks, int seg_chunks, const unsigned long long* __restrict__ mask,
                                                            const int* __restrict__ cmap, const int* __restrict__ seg_start,
@@ -1499,8 +1463,8 @@ static __global__ __launch_bounds__(256) void k_cf_xo_unpermute(int N, const int
 }
 
 // ---- the camera-first form's index tables, generated on the device (round 4) ---------------------------------------------------
-// The host ships only what it takes a sort to know (esl_slam.hip cf_ensure_impl): the per-ellipsoid lists in (slot, u) order and
-// the (segment, ellipsoid) incidences with their rank inside the segment.  The dense tables -- N x (chunks + 1) entry ranges,
+// The host ships only what it takes a sort to know (esl_cf_plan.hpp cf_plan_build, shipped by esl_slam.hip cf_ensure_impl): the
+// per-ellipsoid lists in (slot, u) order and the (segment, ellipsoid) incidences with their rank inside the segment.  The dense tables -- N x (chunks + 1) entry ranges,
 // segments x (N + 1) column map, the tile lists -- were 15 MB built by one host core at BASELINE configs[3]; here they are a few
 // microseconds of scatter.
 // oe_cst[o][chk] = first entry of ellipsoid o's list whose slot is >= chk * kCfFwdCh

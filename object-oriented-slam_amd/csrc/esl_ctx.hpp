@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/esl.h"
+#include "esl_cf_plan.hpp"   // CfPlan (host only)
 #include "esl_math.hpp"
 
 namespace esl {
@@ -279,59 +280,27 @@ struct esl_ctx {
   bool cf_chain_ok = false;
   bool cf_ready = false;         // every buffer of cf_ensure exists and is initialised (esl_slam.hip)
   bool cf_unavailable = false;   // ESL_SOLVER_AUTO: the camera-first buffers did not fit; this graph runs the reduced camera system
+  // every decision and length of the layout, member by member in esl_cf_plan.hpp; below, the device arrays it is shipped into
+  // (interior pointers of arena_solve, named after the plan's members and the kernels' arguments: esl_cf.hpp)
+  esl::CfPlan cf_plan;
   int *cf_oe_start = nullptr, *cf_oe_u = nullptr, *cf_oe_slot = nullptr, *cf_od_start = nullptr, *cf_od_edge = nullptr, *cf_oe_cst = nullptr;
-  int cf_n_list = 0, cf_n_chunks = 0;
   double *cf_Linv = nullptr, *cf_M = nullptr, *cf_N = nullptr, *cf_V = nullptr, *cf_vy = nullptr, *cf_z = nullptr;
   double *cf_B = nullptr, *cf_Lfac = nullptr, *cf_G = nullptr;
-  // nested dissection of the camera chain (esl_cf.hpp): every cf_stride-th slot is a separator (0 = plain chain)
-  int cf_stride = 0, cf_n_sep = 0, cf_n_seg = 1;
   double *cf_Zt = nullptr, *cf_Hs = nullptr, *cf_Bs = nullptr, *cf_LfacS = nullptr, *cf_GS = nullptr, *cf_LiS = nullptr, *cf_MS = nullptr,
-         *cf_NS = nullptr, *cf_R = nullptr;
+         *cf_NS = nullptr, *cf_R = nullptr;   // nested dissection: the separators' system
   double *cf_Xt = nullptr, *cf_T = nullptr, *cf_Linv_ws = nullptr, *cf_part = nullptr;
-  int64_t cf_ldx = 0, cf_kpad = 0, cf_ldt = 0;
-  // sparse interior rows of X (esl_cf.hpp, "X is sparse"): segments of cf_stride slots (kCfFwdCh; form 3: one, two or three chunks
-  // of kCfFwdCh); per segment the sorted list of ellipsoids
-  // with an edge at one of its interior cameras (seg_start / seg_obj), the column map cmap[p (N + 1) + o] = first << 24 | index
-  // (-1: column o of X is zero over segment p; entry N = the right-hand side), per ellipsoid the bitmap of its segments, the
-  // compact slabs Xc (xoff / xld) and the separators' dense rows Xs
-  bool cf_sp_built = false, cf_sparse = false;
-  int cf_sp_nseg = 0, cf_sp_nw = 0, cf_n_fwork = 0;
-  double cf_sp_flops = 0;   // FMAs of the per-segment products: block lower triangles, rows from each block row's first camera on
-  int *cf_seg_start = nullptr, *cf_seg_obj = nullptr, *cf_seg_first = nullptr, *cf_cmap = nullptr, *cf_xld = nullptr, *cf_fwork = nullptr;
+  // sparse interior rows of X: the column map cmap[p (N + 1) + o] = first << 24 | index (-1: column o of X is zero over segment p;
+  // entry N = the right-hand side), per ellipsoid the bitmap of its segments, the compact slabs Xc and the separators' dense rows Xs
+  int *cf_seg_start = nullptr, *cf_seg_obj = nullptr, *cf_seg_first = nullptr, *cf_cmap = nullptr, *cf_xld = nullptr, *cf_fwork = nullptr, *cf_twork = nullptr;
   unsigned long long* cf_mask = nullptr;
-  long long* cf_xoff = nullptr;
-  size_t cf_xc_len = 0;
-  double *cf_Xc = nullptr, *cf_Xs = nullptr;
-  int64_t cf_kpad_s = 0;
-  // per-segment products P_p = Xc_p^T Xc_p in 9 x 9 blocks (block (i1, i2), i1 >= i2, of segment p at boff[p] + i1 (i1 + 1) / 2 + i2),
-  // the right-hand side's row of every product (roff), the tile list of the product kernel; cf_sp_form: 1 = products stored and
-  // gathered (k_cf_seg_syrk + k_cf_T_gather), 2 = blocks of T computed from the slabs directly (k_cf_T_sparse: no P, more traffic)
-  int cf_sp_form = 0, cf_n_twork = 0;
-  long long *cf_boff = nullptr, *cf_roff = nullptr;
-  int* cf_twork = nullptr;
-  size_t cf_p_blocks = 0, cf_prhs_len = 0;
-  double *cf_P = nullptr, *cf_Prhs = nullptr;
-  // cf_sp_form 3 = T's interior part assembled one-sided (k_cf_seg_back + k_cf_T_onesided: no P): Y = L_ii^T (L_p^-T X), one 54-double
-  // record per (segment, compact ellipsoid, interior slot), and the right-hand side's column per slot; cf_os_flops = 2 x the FMAs
-  // of the assembly's 9 x 6 . 6 x 9 products
-  double *cf_Y = nullptr, *cf_Yr = nullptr;
-  size_t cf_y_len = 0;
-  // the assembly's pair list, built once per layout (k_cf_os_list): per block of T's lower triangle and of the b row where its
-  // (A record, B record) pairs start and how many there are.  cf_os_offsets: a pair holds the two records' first elements (entry x 54,
-  // Y record x 54; b row: slot x 6, entry x 54) for k_cf_T_onesided_lds -- false: their numbers, for k_cf_T_onesided, which runs when
-  // sw_cf_os_kernel is 0 or an offset would not fit 32 bits
+  long long *cf_xoff = nullptr, *cf_boff = nullptr, *cf_roff = nullptr;
+  double *cf_Xc = nullptr, *cf_Xs = nullptr, *cf_P = nullptr, *cf_Prhs = nullptr, *cf_Y = nullptr, *cf_Yr = nullptr;
+  // the one-sided assembly's pair list (k_cf_os_list): per block of T's lower triangle and of the b row where its (A record, B record)
+  // pairs start and how many there are
   long long* cf_os_start = nullptr;
   int *cf_os_cnt = nullptr, *cf_os_pairs = nullptr;
-  size_t cf_os_npairs = 0;
-  bool cf_os_offsets = false;
-  double cf_os_flops = 0;
-  // round 5: T's ellipsoids in the order of their first free camera (sparse form): column block cf_rank[o] of T / R / Xs belongs to
-  // ellipsoid o; cf_kfirst[g] = first row of Xs that can be non-zero in columns [64 g, 64 g + 64) (the rank-K update skips the rest);
-  // cf_xo_t = x_o as the solver returns it (T's order); cf_upd_flops = what the dense update executes with the staircase
-  bool cf_tperm = false;
   int *cf_rank = nullptr, *cf_unrank = nullptr, *cf_kfirst = nullptr;
-  double* cf_xo_t = nullptr;
-  double cf_upd_flops = 0;
+  double* cf_xo_t = nullptr;   // x_o as the solver returns it (T's order)
   int lm_solver_used = 0;   // esl_linear_solver the last trial step ran with (1 reduced camera system, 2 reduced ellipsoid system, 3 camera chain)
   // fixed ellipsoids (esl_graph_upload_fixed, esl_fixed.hpp).  fx_on: the resident graph was uploaded with at least one flag set;
   // everything below is empty / unused otherwise and no kernel of esl_fixed.hpp runs
@@ -371,14 +340,14 @@ struct esl_ctx {
   int sw_chol_dist = -1;
   bool sw_chol_overlap = true;   // the distributed factorisation's messages on their own stream under the trailing updates
   // ESL_CF_OVERLAP as read when the CONTEXT was created (A/B; a serial and an overlapped context can live in one process): the
-  // side-stream orders of slam_try_step_cf (esl_slam.hip).  0: every launch of a camera-first trial in stream order; 1 (default):
-  // both side-stream orders; 2: the separators' chain beside the interior rows only; 3: the products' early start only; 4 (default):
+  // side-stream orders of slam_try_step_cf (esl_slam.hip).  0: every launch of a camera-first trial in stream order; 1: both
+  // side-stream orders; 2: the separators' chain beside the interior rows only; 3: the products' early start only; 4 (default):
   // as 1, and the rank-K update capped to one workgroup per CU so that the products' waves are resident beside it (1: uncapped, A/B)
   int sw_cf_overlap = 4;
   // ESL_CF_OS_KERNEL as read when the context was created (A/B and tests): 1 (default) the one-sided assembly feeds whole records
   // through LDS (k_cf_T_onesided_lds), 0 the per-lane gather (k_cf_T_onesided).  Same bits either way.
   int sw_cf_os_kernel = 1;
   // ESL_CF_STRIDE as read when the context was created: 16, 32 or 48 forces the segment length of the sparse form where T is
-  // assembled one-sided (form 3); 0 (unset) = chosen at layout time from the graph's counts (esl_cf.hpp, cf_stride_cost)
+  // assembled one-sided (form 3); 0 (unset) = chosen at layout time from the graph's counts (esl_cf_plan.hpp, cf_stride_cost)
   int sw_cf_stride = 0;
 };

@@ -295,9 +295,7 @@ static int slam_pick_solver(const esl_ctx* c) {
   const double nc = (double)c->S_n, no = 9.0 * c->g.n_objs;
   return (no * no * nc + no * no * no / 3.0 < nc * nc * nc / 3.0) ? ESL_SOLVER_REDUCED_ELLIPSOID : ESL_SOLVER_REDUCED_CAMERA;
 }
-template <class T>
-static void fr(T** p) { if (*p) { (void)hipFree(*p); *p = nullptr; } }
-// everything cf_ensure hands out (interior pointers of the solver arena: forgotten, not freed)
+// everything cf_ensure hands out (interior pointers of the solver arena: forgotten, not freed), and the plan they were laid out by
 static void cf_forget(esl_ctx* c) {
   c->cf_oe_start = c->cf_oe_u = c->cf_oe_slot = c->cf_oe_cst = nullptr;
   c->cf_seg_start = c->cf_seg_obj = c->cf_seg_first = c->cf_cmap = c->cf_xld = c->cf_fwork = c->cf_twork = nullptr;
@@ -307,8 +305,9 @@ static void cf_forget(esl_ctx* c) {
   c->cf_Zt = c->cf_Hs = c->cf_Bs = c->cf_LfacS = c->cf_GS = c->cf_LiS = c->cf_MS = c->cf_NS = c->cf_R = nullptr;
   c->cf_Xc = c->cf_Xs = c->cf_P = c->cf_Prhs = c->cf_Xt = c->cf_Y = c->cf_Yr = nullptr;
   c->cf_os_start = nullptr; c->cf_os_cnt = c->cf_os_pairs = nullptr;
-  c->cf_rank = c->cf_unrank = c->cf_kfirst = nullptr; c->cf_xo_t = nullptr; c->cf_tperm = false; c->cf_upd_flops = 0;
-  c->cf_ready = false; c->cf_sp_built = c->cf_sparse = false;
+  c->cf_rank = c->cf_unrank = c->cf_kfirst = nullptr; c->cf_xo_t = nullptr;
+  c->cf_plan = CfPlan{};
+  c->cf_ready = false;
 }
 static int cf_ensure_impl(esl_ctx* c);
 // The tables and buffers of the camera-first form exist and are initialised <=> cf_ready.  A failed allocation (dense X alone is
@@ -321,292 +320,84 @@ static int cf_ensure(esl_ctx* c) {
   c->cf_ready = true;
   return ESL_OK;
 }
+static_assert(kCfKC == kKC, "esl_cf_plan.hpp pads K to the rank-K update's chunk");
 // Built by the FIRST trial step that picks the camera-first form -- not at upload (a graph whose trials run the reduced
-// camera system, or that is sharded over ranks, never pays for them):
-//   - every ellipsoid's free-camera edges sorted by (slot, u), and the entry range of every (ellipsoid, chunk of kCfFwdCh slots) in
-//     those lists: the forward substitution's gather phase;
-//   - when X = L^-1 W is kept SPARSE over runs of cameras (esl_cf.hpp): per segment of S slots (the last one the separator; S = kCfFwdCh,
-//     or with the one-sided assembly what cf_stride_choose / ESL_CF_STRIDE says)
-//     the ellipsoids seen by its interior cameras, where each one's column starts, per ellipsoid the bitmap of its segments, the
-//     work lists of the per-segment kernels;
-//   - the factor of the camera block, V, X (slabs or dense), T and its solver workspace.
-// No comparison sort on the host, and the dense index tables (entry ranges, column map, tile lists) are generated on the device.
+// camera system, or that is sharded over ranks, never pays for them).  What is built and why is the plan's (esl_cf_plan.hpp,
+// cf_plan_build: every ellipsoid's free-camera edges sorted by (slot, u); with X kept SPARSE over runs of cameras the segments'
+// tables; T's order and staircase); here the plan is staged and shipped, the dense index tables (entry ranges, column map, tile
+// lists, the one-sided assembly's pair list) are generated on the device, and what must be zero is zeroed.
 static int cf_ensure_impl(esl_ctx* c) {
   const DevGraph& g = c->g;
   const int N = g.n_objs, nfi = g.n_free_cams;
   const size_t nf = (size_t)nfi, EU = (size_t)g.n_bbox + g.n_e3d, n_o = (size_t)9 * N;
   const bool timing = std::getenv("ESL_UPLOAD_HOST_TIMING") != nullptr;
   const double t0 = timing ? now_us() : 0;
-  c->cf_ldx = (int64_t)((n_o + 1 + 127) / 128 * 128);   // (whole 128-row tiles: the update tiles read the pad rows instead of guarding their last tile row, chol_update_tile_v)
-  c->cf_kpad = (int64_t)((6 * nf + kKC - 1) / kKC * kKC);
-  c->cf_ldt = c->cf_ldx;
-  const std::vector<int>& start = c->h_ue_start;
-  const size_t nue = c->h_ue_id.size();
-  const int nch = (nfi + kCfFwdCh - 1) / kCfFwdCh;
-  c->cf_n_list = (int)nue; c->cf_n_chunks = nch;
-  if ((size_t)std::max(N, 1) * (size_t)(nch + 1) > ((size_t)1 << 28)) {
+  // the switches: three read at every layout (the tests set them between uploads), ESL_CF_ND_MIN once per process, two with the context
+  CfSwitches sw;
+  { const char* e = std::getenv("ESL_CF_SPARSE"); sw.sparse = e ? (int)(unsigned char)e[0] : -1; }
+  { const char* e = std::getenv("ESL_CF_TPERM"); sw.tperm_off = e && e[0] == '0'; }
+  sw.no_nd = std::getenv("ESL_CF_NO_ND") != nullptr;
+  static const int nd_min = [] { const char* e = std::getenv("ESL_CF_ND_MIN"); return e ? std::atoi(e) : 48; }();
+  sw.nd_min = nd_min; sw.stride = c->sw_cf_stride; sw.os_kernel = c->sw_cf_os_kernel;
+  size_t free_b = 0, total_b = 0;   // (the TOTAL decides between forms 1 and 2, never what happens to be free)
+  if (nfi >= kCfSparseMinCams) ESL_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  CfPlan& pl = c->cf_plan;
+  if (!cf_plan_build(N, nfi, EU, c->h_ue_start, c->h_cu_start, c->h_cu_obj, c->h_cu_id, c->cf_chain_ok, c->comm != nullptr, total_b, sw, pl)) {
     set_error("camera-first elimination: the (ellipsoid, camera chunk) range table of this graph exceeds 1 GB");
     return ESL_ERR_ALLOC;
   }
-  // (slot, u) order per ellipsoid = the per-camera lists of slam_alloc (ellipsoids, then u, ascending inside a slot) walked in slot
-  // order and dealt to the ellipsoids.  The same walk meets, for the sparse form, every (segment, ellipsoid) pair first at the
-  // ellipsoid's FIRST interior camera of the segment, slot by slot: the incidences come out sorted by (segment, first camera,
-  // ellipsoid) -- the compact column order of a segment's slab (upper-trapezoidal: column c is zero above row 6 first(c); a tile of
-  // the segment's product starts at the first camera of its first column) -- with no sort at all.
-  const bool want_sp = c->cf_chain_ok && nfi >= 256 && N > 0 && (size_t)nch * (size_t)(N + 1) <= ((size_t)1 << 28) && !std::getenv("ESL_CF_NO_ND");
-  // S = segment length of the sparse form: kCfFwdCh, or with the one-sided assembly (form 3) two or three chunks (chosen below)
-  int S = kCfFwdCh, nseg = nch, nw = (nseg + 63) / 64;
-  const int N1 = N + 1;
-  std::vector<int> os(nue), ou(nue);
-  std::vector<int> inc_p, inc_o, inc_first;
-  std::vector<int> seg_start, xld, fw_off;
-  std::vector<long long> xoff, boff, roff, tw_off;
-  size_t n_fwork = 0, n_twork = 0, n_inc = 0;
-  // the walk and the segments' tables for segments of S slots
-  auto walk = [&](int sS) {
-    S = sS; nseg = (nfi + S - 1) / S; nw = (nseg + 63) / 64;
-    inc_p.clear(); inc_o.clear(); inc_first.clear();
-    std::vector<int> cur(start.begin(), start.end() - 1), last_seg(want_sp ? (size_t)N : 0, -1);
-    const int* cstart = c->h_cu_start; const int* cobj = c->h_cu_obj; const int* cid = c->h_cu_id;
-    if (want_sp) { inc_p.reserve(nue / 4 + 16); inc_o.reserve(nue / 4 + 16); inc_first.reserve(nue / 4 + 16); }
-    for (int sl = 0; sl < nfi; ++sl) {
-      const int p = sl / S, pos = sl - p * S;
-      const bool interior = want_sp && pos != S - 1;   // (the last slot of a segment is its separator)
-      for (int q = cstart[sl]; q < cstart[sl + 1]; ++q) {
-        const int o = cobj[q], at = cur[o]++;
-        os[at] = sl; ou[at] = cid[q];
-        if (interior && last_seg[o] != p) { last_seg[o] = p; inc_p.push_back(p); inc_o.push_back(o); inc_first.push_back(pos); }
-      }
-    }
-    n_inc = inc_p.size();
-    if (!want_sp) return;
-    double fl = 0;
-    // rows of a slab: the padded kCfSegRows of the one-chunk forms' kernels, else the segment's interior rows as they are
-    const long long rows = S == kCfFwdCh ? kCfSegRows : 6 * (S - 1);
-    seg_start.assign((size_t)nseg + 1, 0); xld.assign((size_t)nseg, 0); fw_off.assign((size_t)nseg + 1, 0);
-    xoff.assign((size_t)nseg + 1, 0); boff.assign((size_t)nseg + 1, 0); roff.assign((size_t)nseg + 1, 0); tw_off.assign((size_t)nseg + 1, 0);
-    for (size_t q = 0; q < n_inc; ++q) ++seg_start[(size_t)inc_p[q] + 1];
-    for (int p = 0; p < nseg; ++p) seg_start[(size_t)p + 1] += seg_start[p];
-    for (size_t q = 0; q < n_inc; ++q)    // block row k of the product: k + 1 blocks, rows from its first camera on
-      fl += 81.0 * (double)(q - (size_t)seg_start[inc_p[q]] + 1) * (6.0 * (S - 1 - inc_first[q]));
-    for (int p = 0; p < nseg; ++p) {
-      const int cnt = seg_start[(size_t)p + 1] - seg_start[p];
-      const int m = 9 * cnt + 1;
-      xld[p] = (m + 15) / 16 * 16 + 16;                          // + 16: the T kernel reads 16 columns from any column start
-      xoff[(size_t)p + 1] = xoff[p] + rows * xld[p];
-      fw_off[(size_t)p + 1] = fw_off[p] + (m + 63) / 64;
-      boff[(size_t)p + 1] = boff[p] + (long long)cnt * (cnt + 1) / 2;
-      roff[(size_t)p + 1] = roff[p] + 9LL * cnt;
-      const long long nt = (9 * cnt + kCfSyT - 1) / kCfSyT;
-      tw_off[(size_t)p + 1] = tw_off[p] + nt * (nt + 1) / 2;     // tiles of the product on and below the diagonal (ellipsoid columns only)
-    }
-    n_fwork = (size_t)fw_off[nseg]; n_twork = (size_t)tw_off[nseg];
-    c->cf_sp_nseg = nseg; c->cf_sp_nw = nw; c->cf_n_fwork = (int)n_fwork; c->cf_sp_flops = fl;
-    c->cf_xc_len = (size_t)xoff[nseg] + 2 * kCfSyT;   // (+: the product kernel's last tile reads past the last slab's columns)
-    c->cf_n_twork = (int)n_twork; c->cf_p_blocks = (size_t)boff[nseg]; c->cf_prhs_len = (size_t)roff[nseg];
-    c->cf_sp_built = true;
-  };
-  walk(kCfFwdCh);
-  if (want_sp) {
-    // X sparse or dense (esl_cf.hpp, "sparse interior rows"): flops of the dense rank-6 nf update against the separators' dense
-    // rows plus the per-segment products at a quarter of the MFMA rate; ESL_CF_SPARSE=1 / 0 forces it (A/B and the parity tests)
-    const double dense = (double)n_o * (double)n_o * 6.0 * (double)nf;
-    const double sparse = (double)n_o * (double)n_o * 6.0 * (double)(nf / kCfFwdCh) + 24.0 * c->cf_sp_flops;   // (cf_sp_flops: FMAs of the products' lower triangles)
-    const char* sw = std::getenv("ESL_CF_SPARSE");
-    c->cf_sparse = sw ? sw[0] != '0' : (n_o >= 2048 && sparse < 0.5 * dense);
-    // the per-segment products are stored when they fit beside everything else (C4: 14 GB); else (or ESL_CF_SPARSE=2) the blocks
-    // of T come straight from the slabs (k_cf_T_sparse).  Decided from the graph's size against the device's TOTAL memory, not from
-    // what happens to be free at the first trial: the two forms add in different orders, so the bits of T must not depend on what
-    // else occupies the GPU; every rank of a replicated run takes the same decision by construction.
-    // esl_lm_solver_stats reports the form.
-    size_t free_b = 0, total_b = 0;
-    ESL_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    const double n_sep = (double)(nf / kCfFwdCh);
-    const double need = 8.0 * (81.0 * (double)c->cf_p_blocks + (double)c->cf_xc_len + 2.0 * (double)c->cf_ldt * (double)n_o +
-                               2.0 * 6.0 * n_sep * (double)c->cf_ldx /* Xs, R */ + 54.0 * (double)EU /* V */);
-    c->cf_sp_form = (sw && sw[0] == '2') || need > 0.4 * (double)total_b ? 2 : 1;
-    // form 3 (esl_cf.hpp, "one-sided assembly"): no product store, so the memory rule above does not apply to it.  ESL_CF_SPARSE=3
-    // forces it; unset, it is the form wherever X is kept sparse on a single rank.  1 / 2 / 0 keep their paths and bits; a run
-    // with a communicator keeps its present form.
-    if ((!sw || sw[0] == '3') && !c->comm) c->cf_sp_form = 3;
-    if (!c->cf_sparse) c->cf_sp_built = false;   // (none of the sparse-form tables are shipped)
-  }
-  const bool sp = c->cf_sparse;
-  // T's ellipsoids by first free camera (sparse form; ESL_CF_TPERM=0: ellipsoid order, A/B): rank by a counting sort over the
-  // first slot of every ellipsoid's (slot-sorted) list, ellipsoids without a free-camera edge last
-  std::vector<int> h_rank, h_unrank, h_kfirst, first;
-  const bool tperm = sp && N > 0 && !(std::getenv("ESL_CF_TPERM") && std::getenv("ESL_CF_TPERM")[0] == '0');
-  if (tperm) {
-    std::vector<int> cnt((size_t)nfi + 2, 0);
-    first.assign((size_t)N, nfi);
-    for (int o = 0; o < N; ++o) if (start[(size_t)o + 1] > start[o]) first[o] = os[(size_t)start[o]];
-    for (int o = 0; o < N; ++o) ++cnt[(size_t)first[o] + 1];
-    for (int s2 = 0; s2 <= nfi; ++s2) cnt[(size_t)s2 + 1] += cnt[s2];
-    h_rank.assign((size_t)N, 0); h_unrank.assign((size_t)N, 0);
-    for (int o = 0; o < N; ++o) { const int t = cnt[first[o]]++; h_rank[o] = t; h_unrank[t] = o; }
-  }
-  // kfirst per 64 columns of T for segments of sS slots: the first separator whose right-hand side R(k) can hold the column's
-  // ellipsoid is the one in FRONT of the segment of its first camera (an interior camera's segment hands its sum to the separator
-  // before it; conservative for a separator camera itself), and the right-hand side's ROW (row n_o of T, X^T y) is dense from the
-  // start.  Returns the flops the update executes (k_chol_update_v, the default tile of the big launches): per 128 x 128 tile of the
-  // lower triangle, K from the later of the tile's two earliest rows on, rounded down to a chunk pair as the kernel does; a tile on
-  // the diagonal counts its lower triangle.  (The 256 x 128 tile of ESL_UPD_V=0 starts a little earlier: it executes ~1 % more.)
-  auto staircase = [&](int sS) {
-    double upd_flops = 0;
-    const int Ks = (int)((6 * (nf / (size_t)sS) + kKC - 1) / kKC * kKC);
-    const size_t ng = (n_o + 1 + 256) / 64 + 8;
-    h_kfirst.assign(ng, Ks);
-    for (size_t col = 0; col < n_o; ++col) {
-      const int o = h_unrank[col / 9];
-      const int k0 = std::max(0, first[o] / sS - 1);
-      const int row = std::min(6 * k0, Ks);
-      h_kfirst[col / 64] = std::min(h_kfirst[col / 64], row);
-    }
-    h_kfirst[n_o / 64] = 0;   // the right-hand side's row
-    const long nti = ((long)n_o + 1 + 127) / 128;
-    for (long ti = 0; ti < nti; ++ti) {
-      const int ka = std::min(h_kfirst[(size_t)(ti * 2)], h_kfirst[(size_t)(ti * 2 + 1)]);
-      for (long tj = 0; tj <= ti && tj * 128 < (long)n_o; ++tj) {
-        const int kb = std::min(h_kfirst[(size_t)(tj * 2)], h_kfirst[(size_t)(tj * 2 + 1)]);
-        int ks = std::min(std::max(ka, kb), Ks) & ~(kKC - 1);
-        if (((Ks - ks) & kKC) != 0 && ks >= kKC) ks -= kKC;
-        const double rows_t = (double)std::min<long>(128, (long)n_o + 1 - ti * 128), cols_t = (double)std::min<long>(128, (long)n_o - tj * 128);
-        const double in_triangle = tj < ti ? 1.0 : 0.5 * (cols_t + 1.0) / cols_t;
-        upd_flops += 2.0 * rows_t * cols_t * (double)(Ks - ks) * in_triangle;
-      }
-    }
-    return upd_flops;
-  };
-  // what the one-sided assembly executes with segments of sS slots: per block (t1 >= t2) of T and shared segment, one 9 x 6 . 6 x 9
-  // product per interior list entry of o1 in the segment; the b row one 6 x 9 . 6 product per interior entry.  (Segment, position in
-  // T's order, entries) of every incidence, by segment and position: the incidence at place q of its segment meets q + 1 partners.
-  auto os_counts = [&](int sS, double& prod, double& rhs_entries) {
-    std::vector<std::array<int, 3>> inc3;
-    inc3.reserve(n_inc);
-    prod = 0; rhs_entries = 0;
-    for (int o = 0; o < N; ++o) {
-      int last_p = -1;
-      for (int k = start[o]; k < start[(size_t)o + 1]; ++k) {
-        const int sl = os[(size_t)k];
-        if (sl % sS == sS - 1) continue;
-        const int p = sl / sS;
-        if (p != last_p) { inc3.push_back({p, tperm ? h_rank[(size_t)o] : o, 0}); last_p = p; }
-        ++inc3.back()[2]; rhs_entries += 1;
-      }
-    }
-    std::sort(inc3.begin(), inc3.end());
-    for (size_t q = 0, q0 = 0; q < inc3.size(); ++q) {
-      if (inc3[q][0] != inc3[q0][0]) q0 = q;
-      prod += (double)inc3[q][2] * (double)(q - q0 + 1);
-    }
-  };
-  // The segment length of form 3 (esl_cf.hpp, "choosing the segment length"): ESL_CF_STRIDE as read when the context was created, else
-  // kCfFwdCh unless the reduced system is large enough for the separators' update to carry the launch (9 N >= 8192: k_chol_update_v),
-  // and then what cf_stride_choose makes of this graph's counts.  Every other form, and a run with a communicator, keeps kCfFwdCh.
-  if (sp && c->cf_sp_form == 3 && !c->comm) {
-    int want = c->sw_cf_stride;
-    if (!want && tperm && n_o >= 8192) {
-      double upd[3], pairs[3], slab[3];
-      for (int m = 1; m <= 3; ++m) {
-        double prod, rhs_entries;
-        walk(m * kCfFwdCh);
-        os_counts(S, prod, rhs_entries);
-        long long cols = 0;
-        for (int p = 0; p < nseg; ++p) cols += xld[p];
-        upd[m - 1] = staircase(S); pairs[m - 1] = prod + rhs_entries; slab[m - 1] = 6.0 * (S - 1) * (double)cols;
-      }
-      want = cf_stride_choose((long)n_o, upd, pairs, slab);
-    }
-    if (!want) want = kCfFwdCh;
-    if (want != S) walk(want);
-  }
-  // nested dissection of the camera chain from 48 free cameras on: stride = 16 x round(sqrt(nf) / 16) in [16, 128] (a multiple
-  // of the forward substitution's chunk, so that segments start on chunk boundaries), the segment length S when X is kept sparse;
-  // ESL_CF_NO_ND=1 keeps the plain chain (A/B)
-  c->cf_stride = 0; c->cf_n_sep = 0; c->cf_n_seg = 1;
-  // (ESL_CF_ND_MIN: first free-camera count that is dissected -- default 48, three segments; 128 until round 6: at 119 free cameras the
-  //  plain chain's two serial sweeps, k_cf_chain 72 us + k_cf_forward 69 us, were a quarter of a streaming-size trial)
-  static const size_t nd_min = [] { const char* e = std::getenv("ESL_CF_ND_MIN"); const int v = e ? std::atoi(e) : 48; return (size_t)std::max(v, 2 * kCfFwdCh); }();
-  const bool nd = nf >= nd_min && !std::getenv("ESL_CF_NO_ND");
-  if (nd) {
-    int sd = 16 * (int)std::max(1.0, std::floor(std::sqrt((double)nf) / 16.0 + 0.5));
-    sd = std::min(sd, kCfMaxStride);
-    if (sp) sd = S;
-    c->cf_stride = sd; c->cf_n_sep = (int)(nf / sd); c->cf_n_seg = (int)((nf + sd - 1) / sd);
-  }
-  const double upd_flops = tperm ? staircase(S) : 0.0;
-  c->cf_tperm = tperm; c->cf_upd_flops = upd_flops;
-  c->cf_y_len = 0; c->cf_os_flops = 0;
-  if (sp && c->cf_sp_form == 3) {
-    double prod, rhs_entries;
-    os_counts(S, prod, rhs_entries);
-    c->cf_os_flops = 2.0 * 6.0 * (81.0 * prod + 9.0 * rhs_entries);
-    c->cf_os_npairs = (size_t)(prod + rhs_entries);   // (record pairs of the assembly: the length of its list)
-    c->cf_y_len = std::max<size_t>(n_inc, 1) * (size_t)(S - 1) * 54 + std::max<size_t>(nf, 1) * 6;
-  }
+  const bool sp = pl.sparse, os3 = sp && pl.form == 3;
+  const int nch = pl.n_chunks, nseg = pl.nseg, nw = pl.nw, N1 = N + 1;
+  const size_t n_inc = pl.p.size();
+  const size_t y_recs = std::max<size_t>(n_inc, 1) * (size_t)(pl.S - 1), nb = (size_t)N * (N + 1) / 2 + N;   // (Y's records; blocks of T's lower triangle + the b row)
   const double t1 = timing ? now_us() : 0;
   // ---- layout: what the host ships first, then the device-generated tables (esl_cf.hpp k_cf_make_*), then the buffers ----
   BlobStage st;
-  const int i_st = st.up(&c->cf_oe_start, start.size()), i_ou = st.up(&c->cf_oe_u, nue), i_os = st.up(&c->cf_oe_slot, nue);
+  struct Up { int item; const void* src; size_t bytes; };
+  std::vector<Up> ups;   // the plan's vectors, copied into the staging blob once it is reserved
+  auto ship = [&](auto** dst, const auto& v) { ups.push_back({st.up(dst, v.size()), v.data(), v.size() * sizeof(v[0])}); };
+  ship(&c->cf_oe_start, c->h_ue_start); ship(&c->cf_oe_u, pl.ou); ship(&c->cf_oe_slot, pl.os);
   int* d_inc = nullptr; int* d_fw_off = nullptr; long long* d_tw_off = nullptr;
-  int i_inc = -1, i_ss = -1, i_xld = -1, i_xoff = -1, i_boff = -1, i_roff = -1, i_fwo = -1, i_two = -1, i_rk = -1, i_ur = -1, i_kf = -1;
-  if (tperm) { i_rk = st.up(&c->cf_rank, h_rank.size()); i_ur = st.up(&c->cf_unrank, h_unrank.size()); i_kf = st.up(&c->cf_kfirst, h_kfirst.size()); }
+  int i_inc = -1;
+  if (pl.tperm) { ship(&c->cf_rank, pl.rank); ship(&c->cf_unrank, pl.unrank); ship(&c->cf_kfirst, pl.kfirst); }
   if (sp) {
-    i_inc = st.up(&d_inc, 4 * n_inc); i_ss = st.up(&c->cf_seg_start, (size_t)nseg + 1); i_xld = st.up(&c->cf_xld, (size_t)nseg);
-    i_xoff = st.up(&c->cf_xoff, (size_t)nseg + 1); i_boff = st.up(&c->cf_boff, (size_t)nseg + 1); i_roff = st.up(&c->cf_roff, (size_t)nseg + 1);
-    i_fwo = st.up(&d_fw_off, (size_t)nseg + 1); i_two = st.up(&d_tw_off, (size_t)nseg + 1);
+    i_inc = st.up(&d_inc, 4 * n_inc); ship(&c->cf_seg_start, pl.seg_start); ship(&c->cf_xld, pl.xld);
+    ship(&c->cf_xoff, pl.xoff); ship(&c->cf_boff, pl.boff); ship(&c->cf_roff, pl.roff); ship(&d_fw_off, pl.fw_off); ship(&d_tw_off, pl.tw_off);
   }
   st.work(&c->cf_oe_cst, (size_t)std::max(N, 1) * (nch + 1));
   if (sp) {
     st.work(&c->cf_cmap, (size_t)nseg * N1); st.work(&c->cf_mask, (size_t)N1 * nw); st.work(&c->cf_seg_obj, n_inc); st.work(&c->cf_seg_first, n_inc);
-    st.work(&c->cf_fwork, 2 * n_fwork); st.work(&c->cf_twork, 3 * n_twork);
+    st.work(&c->cf_fwork, 2 * (size_t)pl.n_fwork); st.work(&c->cf_twork, 3 * (size_t)pl.n_twork);
   }
   st.work(&c->cf_Linv, nf * 36); st.work(&c->cf_M, nf * 36); st.work(&c->cf_N, nf * 36); st.work(&c->cf_V, EU * 54);
   st.work(&c->cf_B, nf * 36); st.work(&c->cf_Lfac, nf * 21); st.work(&c->cf_G, nf * 36); st.work(&c->cf_vy, nf * 6); st.work(&c->cf_z, nf * 6);
-  st.work(&c->cf_T, (size_t)c->cf_ldt * n_o); st.work(&c->cf_Linv_ws, ((n_o + kNB - 1) / kNB) * kNB * kNB);
-  if (tperm) st.work(&c->cf_xo_t, n_o);
-  if (n_o <= 1024) st.work(&c->cf_part, (size_t)kCholMaxSplit * (size_t)c->cf_ldt * n_o);   // split-K workspace of small systems
-  if (nd) {
-    const size_t ns = (size_t)std::max(c->cf_n_sep, 1);
+  st.work(&c->cf_T, (size_t)pl.ldt * n_o); st.work(&c->cf_Linv_ws, ((n_o + kNB - 1) / kNB) * kNB * kNB);
+  if (pl.tperm) st.work(&c->cf_xo_t, n_o);
+  if (n_o <= 1024) st.work(&c->cf_part, (size_t)kCholMaxSplit * (size_t)pl.ldt * n_o);   // split-K workspace of small systems
+  if (pl.nd) {
+    const size_t ns = (size_t)std::max(pl.n_sep, 1);
     st.work(&c->cf_Zt, nf * 36); st.work(&c->cf_Hs, ns * 36); st.work(&c->cf_Bs, ns * 36); st.work(&c->cf_LfacS, ns * 21);
     st.work(&c->cf_GS, ns * 36); st.work(&c->cf_LiS, ns * 36); st.work(&c->cf_MS, ns * 36); st.work(&c->cf_NS, ns * 36);
-    st.work(&c->cf_R, ns * 6 * (size_t)c->cf_ldx);
+    st.work(&c->cf_R, ns * 6 * (size_t)pl.ldx);
   }
   if (sp) {
-    c->cf_kpad_s = (int64_t)((6 * (size_t)c->cf_n_sep + kKC - 1) / kKC * kKC);
-    st.work(&c->cf_Xc, c->cf_xc_len); st.work(&c->cf_Xs, (size_t)c->cf_ldx * (size_t)c->cf_kpad_s);
-    if (c->cf_sp_form == 1) { st.work(&c->cf_P, c->cf_p_blocks * 81); st.work(&c->cf_Prhs, c->cf_prhs_len); }
-    if (c->cf_sp_form == 3) {
-      const size_t nb = (size_t)N * (N + 1) / 2 + N;   // blocks of T's lower triangle + the b row
-      st.work(&c->cf_Y, std::max<size_t>(n_inc, 1) * (size_t)(S - 1) * 54); st.work(&c->cf_Yr, std::max<size_t>(nf, 1) * 6);
-      st.work(&c->cf_os_start, nb + 1); st.work(&c->cf_os_cnt, nb); st.work(&c->cf_os_pairs, 2 * std::max<size_t>(c->cf_os_npairs, 1));
+    st.work(&c->cf_Xc, pl.xc_len); st.work(&c->cf_Xs, (size_t)pl.ldx * (size_t)pl.kpad_s);
+    if (pl.form == 1) { st.work(&c->cf_P, pl.p_blocks * 81); st.work(&c->cf_Prhs, pl.prhs_len); }
+    if (pl.form == 3) {
+      st.work(&c->cf_Y, y_recs * 54); st.work(&c->cf_Yr, std::max<size_t>(nf, 1) * 6);
+      st.work(&c->cf_os_start, nb + 1); st.work(&c->cf_os_cnt, nb); st.work(&c->cf_os_pairs, 2 * std::max<size_t>(pl.os_npairs, 1));
     }
   } else {
-    st.work(&c->cf_Xt, (size_t)c->cf_ldx * (size_t)c->cf_kpad);
+    st.work(&c->cf_Xt, (size_t)pl.ldx * (size_t)pl.kpad);
   }
   if (int rc = st.reserve(c->arena_solve)) return rc;
   // ---- fill the staging blob, ship it, generate the dense tables ----
-  std::memcpy(st.host<int>(i_st), start.data(), start.size() * sizeof(int));
-  if (nue) { std::memcpy(st.host<int>(i_ou), ou.data(), nue * sizeof(int)); std::memcpy(st.host<int>(i_os), os.data(), nue * sizeof(int)); }
-  if (tperm) {
-    std::memcpy(st.host<int>(i_rk), h_rank.data(), h_rank.size() * sizeof(int));
-    std::memcpy(st.host<int>(i_ur), h_unrank.data(), h_unrank.size() * sizeof(int));
-    std::memcpy(st.host<int>(i_kf), h_kfirst.data(), h_kfirst.size() * sizeof(int));
-  }
-  if (sp) {
-    int* inc = st.host<int>(i_inc);
-    if (n_inc) {
-      std::memcpy(inc, inc_p.data(), n_inc * sizeof(int)); std::memcpy(inc + n_inc, inc_o.data(), n_inc * sizeof(int));
-      std::memcpy(inc + 2 * n_inc, inc_first.data(), n_inc * sizeof(int));
-      for (size_t q = 0; q < n_inc; ++q) inc[3 * n_inc + q] = (int)q;   // (already in column order)
-    }
-    std::memcpy(st.host<int>(i_ss), seg_start.data(), seg_start.size() * sizeof(int));
-    std::memcpy(st.host<int>(i_xld), xld.data(), xld.size() * sizeof(int));
-    std::memcpy(st.host<int>(i_fwo), fw_off.data(), fw_off.size() * sizeof(int));
-    std::memcpy(st.host<long long>(i_xoff), xoff.data(), xoff.size() * sizeof(long long));
-    std::memcpy(st.host<long long>(i_boff), boff.data(), boff.size() * sizeof(long long));
-    std::memcpy(st.host<long long>(i_roff), roff.data(), roff.size() * sizeof(long long));
-    std::memcpy(st.host<long long>(i_two), tw_off.data(), tw_off.size() * sizeof(long long));
+  for (const Up& u : ups) if (u.bytes) std::memcpy(st.host<char>(u.item), u.src, u.bytes);
+  if (sp && n_inc) {
+    int* inc = st.host<int>(i_inc);   // the incidences: segment, ellipsoid, first camera, place in the column order (they are in it already)
+    std::memcpy(inc, pl.p.data(), n_inc * sizeof(int)); std::memcpy(inc + n_inc, pl.o.data(), n_inc * sizeof(int));
+    std::memcpy(inc + 2 * n_inc, pl.first.data(), n_inc * sizeof(int));
+    for (size_t q = 0; q < n_inc; ++q) inc[3 * n_inc + q] = (int)q;
   }
   if (int rc = st.ship(c->stream)) return rc;
   if (N > 0) {
@@ -622,16 +413,11 @@ static int cf_ensure_impl(esl_ctx* c) {
     hipLaunchKernelGGL(k_cf_make_work, dim3((unsigned)nseg), dim3(64), 0, c->stream, nseg, N, nw, c->cf_seg_start, d_fw_off, d_tw_off, c->cf_cmap, c->cf_mask,
                        c->cf_fwork, c->cf_twork);
   }
-  if (sp && c->cf_sp_form == 3) {
+  if (os3) {
     // the one-sided assembly's pair list (esl_cf.hpp): count per block, offsets on the host, fill.  Once per layout.
-    const size_t nb = (size_t)N * (N + 1) / 2 + N;
     const dim3 grid((unsigned)(N + 1), (unsigned)((N + kCfTPer - 1) / kCfTPer));
-    // element offsets for k_cf_T_onesided_lds where every record's first element fits the list's 32 bits (C4: 1.4e8), else record
-    // numbers and the per-lane gather
-    const size_t max_off = 54 * std::max<size_t>(EU, std::max<size_t>(n_inc, 1) * (size_t)(S - 1));
-    c->cf_os_offsets = c->sw_cf_os_kernel != 0 && max_off <= (size_t)INT32_MAX;
     ESL_HIP_TRY(hipMemsetAsync(c->cf_os_cnt, 0, nb * sizeof(int), c->stream));
-    hipLaunchKernelGGL(k_cf_os_list<false>, grid, dim3(256), 0, c->stream, N, nw, nch, S / kCfFwdCh, c->cf_mask, c->cf_cmap, c->cf_seg_start, c->cf_oe_cst, c->cf_oe_slot,
+    hipLaunchKernelGGL(k_cf_os_list<false>, grid, dim3(256), 0, c->stream, N, nw, nch, pl.S / kCfFwdCh, c->cf_mask, c->cf_cmap, c->cf_seg_start, c->cf_oe_cst, c->cf_oe_slot,
                        (const int*)c->cf_unrank, (const long long*)nullptr, c->cf_os_cnt, (int2*)nullptr, 0);
     std::vector<int> h_cnt(nb);
     std::vector<long long> h_start(nb + 1);
@@ -639,309 +425,360 @@ static int cf_ensure_impl(esl_ctx* c) {
     ESL_HIP_TRY(hipStreamSynchronize(c->stream));
     h_start[0] = 0;
     for (size_t b = 0; b < nb; ++b) h_start[b + 1] = h_start[b] + h_cnt[b];
-    if ((size_t)h_start[nb] != c->cf_os_npairs) {
+    if ((size_t)h_start[nb] != pl.os_npairs) {
       set_error("camera-first elimination: the one-sided assembly's pair list does not have the length the host counted");
       return ESL_ERR_STATE;
     }
     ESL_HIP_TRY(hipMemcpyAsync(c->cf_os_start, h_start.data(), (nb + 1) * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_cf_os_list<true>, grid, dim3(256), 0, c->stream, N, nw, nch, S / kCfFwdCh, c->cf_mask, c->cf_cmap, c->cf_seg_start, c->cf_oe_cst, c->cf_oe_slot,
-                       (const int*)c->cf_unrank, (const long long*)c->cf_os_start, c->cf_os_cnt, (int2*)c->cf_os_pairs, c->cf_os_offsets ? 1 : 0);
+    hipLaunchKernelGGL(k_cf_os_list<true>, grid, dim3(256), 0, c->stream, N, nw, nch, pl.S / kCfFwdCh, c->cf_mask, c->cf_cmap, c->cf_seg_start, c->cf_oe_cst, c->cf_oe_slot,
+                       (const int*)c->cf_unrank, (const long long*)c->cf_os_start, c->cf_os_cnt, (int2*)c->cf_os_pairs, pl.os_offsets ? 1 : 0);
     ESL_HIP_TRY(hipStreamSynchronize(c->stream));   // (h_start is read by the copy until here)
   }
   // ---- what must be zero ----
-  if (nd) ESL_HIP_TRY(hipMemsetAsync(c->cf_Zt, 0, nf * 36 * sizeof(double), c->stream));
+  if (pl.nd) ESL_HIP_TRY(hipMemsetAsync(c->cf_Zt, 0, nf * 36 * sizeof(double), c->stream));
   if (sp) {
     // slabs: pad columns and rows 90 .. 95 stay zero; Xs: rows 6 n_sep .. kpad_s (the K padding of the rank-K update) stay zero;
     // T: the blocks above the diagonal are never written
-    ESL_HIP_TRY(hipMemsetAsync(c->cf_Xc, 0, std::max<size_t>(c->cf_xc_len, 1) * sizeof(double), c->stream));
-    ESL_HIP_TRY(hipMemsetAsync(c->cf_Xs, 0, (size_t)c->cf_ldx * (size_t)c->cf_kpad_s * sizeof(double), c->stream));
-    ESL_HIP_TRY(hipMemsetAsync(c->cf_T, 0, (size_t)c->cf_ldt * n_o * sizeof(double), c->stream));
-    if (c->cf_sp_form == 3) {   // (the records of slots behind a short last segment's end are never written and never read)
-      ESL_HIP_TRY(hipMemsetAsync(c->cf_Y, 0, std::max<size_t>(n_inc, 1) * (size_t)(S - 1) * 54 * sizeof(double), c->stream));
+    ESL_HIP_TRY(hipMemsetAsync(c->cf_Xc, 0, std::max<size_t>(pl.xc_len, 1) * sizeof(double), c->stream));
+    ESL_HIP_TRY(hipMemsetAsync(c->cf_Xs, 0, (size_t)pl.ldx * (size_t)pl.kpad_s * sizeof(double), c->stream));
+    ESL_HIP_TRY(hipMemsetAsync(c->cf_T, 0, (size_t)pl.ldt * n_o * sizeof(double), c->stream));
+    if (pl.form == 3) {   // (the records of slots behind a short last segment's end are never written and never read)
+      ESL_HIP_TRY(hipMemsetAsync(c->cf_Y, 0, y_recs * 54 * sizeof(double), c->stream));
       ESL_HIP_TRY(hipMemsetAsync(c->cf_Yr, 0, std::max<size_t>(nf, 1) * 6 * sizeof(double), c->stream));
     }
   } else {
     // rows 6 nf .. kpad of X (the K padding of the rank-K update) and the columns of never-written edges stay zero
-    ESL_HIP_TRY(hipMemsetAsync(c->cf_Xt, 0, (size_t)c->cf_ldx * (size_t)c->cf_kpad * sizeof(double), c->stream));
+    ESL_HIP_TRY(hipMemsetAsync(c->cf_Xt, 0, (size_t)pl.ldx * (size_t)pl.kpad * sizeof(double), c->stream));
   }
   ESL_HIP_TRY(hipMemsetAsync(c->cf_V, 0, std::max<size_t>(EU, 1) * 54 * sizeof(double), c->stream));
   if (timing)
     fprintf(stderr, "[cf_ensure host, us] sorts + structure %.0f  layout + tables + enqueue %.0f  (blob %.1f MB uploaded, %.1f MB in all; sparse %d form %d)\n",
-            t1 - t0, now_us() - t1, st.up_end / 1e6, st.total / 1e6, (int)sp, c->cf_sp_form);
+            t1 - t0, now_us() - t1, st.up_end / 1e6, st.total / 1e6, (int)sp, pl.form);
   return ESL_OK;
 }
-// One LM trial with the cameras eliminated first: x_c, x_o, trial states, chi2 of the trial (same outputs as the other form)
-static int slam_try_step_cf(esl_ctx* c, double lambda) {
-  const DevGraph& g = c->g;
-  const int N = g.n_objs, F = g.n_cams, nf = g.n_free_cams;
-  const int n_o = 9 * N;
-  int rc = cf_ensure(c);
-  if (rc) return rc;
-  const long ldx = (long)c->cf_ldx, ldt = (long)c->cf_ldt;
-  CholRuntime& rt = chol_rt(c);
-  {
-    ProfScope ps(c, 2);   // "reduced-system build": factor of the camera block, X = L^-1 [W | b_c], T = D - X^T X
-    ESL_HIP_TRY(hipMemsetAsync(c->chol_info, 0, sizeof(int), c->stream));
-    hipLaunchKernelGGL(k_cf_gather_B, dim3((unsigned)(((long)nf * 36 + 255) / 256)), dim3(256), 0, c->stream, nf, c->Aod, c->cf_od_start, c->cf_od_edge, c->cf_B);
-    const int st = c->cf_stride, ns = c->cf_n_sep, nseg = c->cf_n_seg;
-    const bool nd = st > 0 && ns > 0;
-    const unsigned cg = (unsigned)((n_o + 1 + 63) / 64);
-    const long nt = (long)c->cf_n_list * 9 + nf;
-    // this rank's columns of T: everything, or with the replicated-graph communicator its outer panels (dealt cyclically, as the
-    // distributed factorisation below expects them)
+
+// ---- one LM trial with the cameras eliminated first: x_c, x_o, trial states, chi2 of the trial (same outputs as the other form) ----
+namespace {
+// side-stream work not yet waited for by the main stream when the trial is left (an ESL_HIP_TRY failure): joined here, so that EVERY
+// way out of a trial leaves the side stream joined to the main one
+struct CfSideJoin {
+  CholRuntime& rt; hipStream_t main; bool armed;
+  hipError_t wait(hipEvent_t ev) { const hipError_t e = hipStreamWaitEvent(main, ev, 0); armed = e != hipSuccess; return e; }
+  ~CfSideJoin() {
+    if (!armed) return;
+    if (hipEventRecord(rt.cf_ev_p, rt.cf_side) != hipSuccess || hipStreamWaitEvent(main, rt.cf_ev_p, 0) != hipSuccess) (void)hipStreamSynchronize(rt.cf_side);
+  }
+};
+// What the schedules of one trial share: the context, the plan, the dimensions and the launches that more than one of them enqueues.
+// A schedule (build_*) is the reduced-system build of one form -- factor of the camera block, X = L^-1 [W | b_c], T = D - X^T X --
+// written top to bottom in the order it enqueues; back_substitute is the same for all of them.
+struct CfTrial {
+  esl_ctx* c; CholRuntime& rt; const CfPlan& pl; const DevGraph& g; const double lambda;
+  const int N, nf, n_o; const long ldx, ldt;
+  const int st, ns, nseg;   // dissection: stride, separators, segments
+  const bool nd, dist;      // dist: replicated-graph communicator, this rank builds its outer panels of T only
+  const unsigned cg;        // groups of 64 columns of [X | y]
+  const hipStream_t main;
+  CfSideJoin join;
+  CfTrial(esl_ctx* c_, CholRuntime& rt_, double lambda_)
+      : c(c_), rt(rt_), pl(c_->cf_plan), g(c_->g), lambda(lambda_), N(g.n_objs), nf(g.n_free_cams), n_o(9 * N), ldx((long)pl.ldx), ldt((long)pl.ldt),
+        st(pl.stride), ns(pl.n_sep), nseg(pl.n_seg), nd(st > 0 && ns > 0), dist(cf_dist(c_)), cg((unsigned)((n_o + 1 + 63) / 64)), main(c_->stream),
+        join{rt_, c_->stream, false} {}
+  CfSegs segs() const { return CfSegs{c->cf_fwork, c->cf_seg_start, c->cf_seg_obj, c->cf_xoff, c->cf_xld, c->cf_rank, c->cf_unrank}; }
+  int edge_blocks() const { return (int)(((long)pl.n_list * 9 + nf + 255) / 256); }
+  // this rank's columns of T: everything, or with the replicated-graph communicator its outer panels (dealt cyclically, as the
+  // distributed factorisation expects them)
+  template <class F> void my_columns(F f) const {
+    if (!dist) { f(0L, (long)n_o); return; }
     const int Wp = chol_outer_panels(n_o), n_outer = ((n_o + kNB - 1) / kNB + Wp - 1) / Wp;
-    const bool dist = cf_dist(c);
-    const int Ks_ = (int)c->cf_kpad_s;
-    ESL_HIP_TRY(chol_set_attributes(rt));   // (fills rt.sw)
-    // The side-stream order (single rank, nested dissection, X kept sparse with stored products; ESL_CF_OVERLAP=0 when the context was
-    // created: everything below in stream order).  Two dependent chains meet only at k_cf_sep_rhs:
-    //   interior    k_cf_edge_scale (interior slots) -> k_cf_forward<2> -> the segments' products (k_cf_seg_syrk, k_cf_seg_rhs)
-    //   separators  k_cf_chain (one wave, n_sep steps) -> k_cf_factor_blocks -> V, vy of the separator slots -> [k_cf_forward<2>'s slabs
-    //               and sums] -> k_cf_sep_rhs -> k_cf_forward<1> (one wave per 64 columns) -> the rank-K update
-    // so (1) the separators' chain and its blocks run on rt.cf_side beside the interior pipeline -- enqueued FIRST: a small grid is
-    // resident at once and a full grid on the other stream fills the rest of the GPU (two full grids do not share it: esl_chol.hpp,
-    // cf_overlap_init) -- and (2) the products, which need the slabs alone, run on rt.cf_side beside k_cf_forward<1> and the update.
-    // No arithmetic and no address changes, so every array has the bits of the serial order.
-    // Across trials: the side chain of trial t + 1 writes cf_LfacS, cf_GS, cf_LiS, cf_MS, cf_NS and the separators' slots of cf_Linv,
-    // which trial t's k_cf_edge_scale (separator slots), k_cf_sep_rhs, k_cf_forward<1>, k_cf_tridiag_back and k_cf_back_prep read: all of
-    // them are on the main stream in front of trial t + 1's cf_ev_a, which the side chain waits for.  Trial t + 1's k_cf_forward<2>
-    // writes the slabs trial t's products read: the main stream has waited for trial t's cf_ev_p.  cf_ensure's relayout, esl_ctx_trim
-    // and everything else on the main stream are covered the same way, because every way out of this function leaves the side
-    // stream joined to the main one (CfSideJoin).
-    // Form 3 (one-sided assembly, esl_cf.hpp): the assembly needs Y alone, which exists straight behind k_cf_forward<2>, so with the
-    // switch on the WHOLE separator path -- chain, V and vy of the separator slots, k_cf_sep_rhs, k_cf_forward<1> -- runs on rt.cf_side
-    // beside k_cf_seg_back and the assembly, and the update (uncapped, in its accumulate form) waits for the assembly and Xs only.  One
-    // arithmetic order for T at every setting of the switch: T = D - sum (assign), then T -= Xs^T Xs.
-    const bool os = c->cf_sparse && c->cf_sp_form == 3;
-    const bool side = c->sw_cf_overlap != 0 && nd && c->cf_sparse && (c->cf_sp_form == 1 || os) && !dist && Ks_ > 0 && rt.cf_overlap_init() == hipSuccess;
-    // with the update on its k_chol_update_v path (the one with an assign form) the products also run beside the UPDATE (round 6): it
-    // ASSIGNS T = -Xs^T Xs instead of updating what the gather wrote, and the gather, which then comes last, adds its D - sum to that --
-    // (D - sum) + (-acc) is the same double as (D - sum) - acc, so T has the same bits
-    const bool assign = side && !os && chol_update_v_applies(rt.sw, ldt, (long)n_o + 1, 0, (long)n_o, true, ldx);
-    const bool side_chain = side && (os || c->sw_cf_overlap != 3), early_products = side && !os && c->sw_cf_overlap != 2;   // (each alone: A/B)
-    struct CfSideJoin {   // side-stream work not yet waited for by the main stream when the function is left (an ESL_HIP_TRY failure): joined here
-      CholRuntime& rt; hipStream_t main; bool armed;
-      hipError_t wait(hipEvent_t ev) { const hipError_t e = hipStreamWaitEvent(main, ev, 0); armed = e != hipSuccess; return e; }
-      ~CfSideJoin() {
-        if (!armed) return;
-        if (hipEventRecord(rt.cf_ev_p, rt.cf_side) != hipSuccess || hipStreamWaitEvent(main, rt.cf_ev_p, 0) != hipSuccess) (void)hipStreamSynchronize(rt.cf_side);
-      }
-    } join{rt, c->stream, false};
-    // V = Li W, vy = Li b_c (cls: esl_cf.hpp -- 0 all list entries, 1 / 2 those of interior / separator slots); X dense: the same launch
-    // writes the whole of T (D's lower blocks, b_o's row, zeros) -- nothing reads T before the rank-K update further down
-    auto launch_edge_scale = [&](int cls, hipStream_t st2) {
-      const int nb_es = (int)((nt + 255) / 256);
-      if (!c->cf_sparse)
-        hipLaunchKernelGGL(k_cf_edge_scale_T, dim3((unsigned)(nb_es + (int)((ldt * (long)n_o + 255) / 256))), dim3(256), 0, c->stream, g, nb_es, c->cf_n_list, c->cf_oe_u,
-                           c->cf_oe_slot, c->Wbb, c->cf_Linv, c->bc, c->cf_V, c->cf_vy, c->Hoo, c->bo, lambda, c->cf_T, ldt, (long)n_o);
-      else
-        hipLaunchKernelGGL(k_cf_edge_scale, dim3((unsigned)nb_es), dim3(256), 0, st2, g, c->cf_n_list, c->cf_oe_u, c->cf_oe_slot, c->Wbb, c->cf_Linv, c->bc,
-                           c->cf_V, c->cf_vy, cls, st);
-    };
-    auto launch_products = [&](hipStream_t st2) {
-      hipLaunchKernelGGL(k_cf_seg_syrk, dim3((unsigned)c->cf_n_twork), dim3(256), 0, st2, c->cf_twork, c->cf_seg_start, c->cf_seg_first, c->cf_xoff,
-                         c->cf_xld, c->cf_Xc, c->cf_boff, c->cf_P);
-      hipLaunchKernelGGL(k_cf_seg_rhs, dim3((unsigned)c->cf_n_fwork), dim3(64), 0, st2, c->cf_fwork, c->cf_seg_start, c->cf_xoff, c->cf_xld, c->cf_Xc,
-                         c->cf_roff, c->cf_Prhs);
+    for (int op = c->comm_rank; op < n_outer; op += c->comm_ranks) f((long)op * Wp * kNB, std::min<long>((long)(op + 1) * Wp * kNB, (long)n_o));
+  }
+  // grid of a T-block kernel over the ellipsoids [o2b, o2e) of these columns (a block that straddles a panel boundary: on both sides)
+  dim3 block_grid(long c_begin, long c_end, int& o2b, int& o2e) const {
+    o2b = (int)(c_begin / 9); o2e = (int)((c_end + 8) / 9);
+    return dim3((unsigned)(N + 1), (unsigned)((o2e - o2b + kCfTPer - 1) / kCfTPer));
+  }
+  // X sparse: V = Li W, vy = Li b_c of the list entries of class cls (esl_cf.hpp -- 0 all, 1 / 2 those of interior / separator slots)
+  void edge_scale(int cls, hipStream_t s) const {
+    hipLaunchKernelGGL(k_cf_edge_scale, dim3((unsigned)edge_blocks()), dim3(256), 0, s, g, pl.n_list, c->cf_oe_u, c->cf_oe_slot, c->Wbb, c->cf_Linv, c->bc,
+                       c->cf_V, c->cf_vy, cls, st);
+  }
+  // nested dissection (esl_cf.hpp), first half: the segments' chains in parallel and the separators' system assembled from them
+  void segment_chains() const {
+    hipLaunchKernelGGL(k_cf_chain, dim3((unsigned)nseg), dim3(64), 0, main, nf, c->Hcc, c->cf_B, lambda, c->cf_Lfac, c->cf_G, c->chol_info, st, st - 1);
+    hipLaunchKernelGGL(k_cf_factor_blocks, dim3((unsigned)((nf + 63) / 64)), dim3(64), 0, main, nf, c->cf_Lfac, c->cf_G, c->cf_Linv, c->cf_M, c->cf_N, st);
+    if (nseg > 1) hipLaunchKernelGGL(k_cf_zt, dim3((unsigned)(nseg - 1)), dim3(64), 0, main, nf, st, c->cf_Linv, c->cf_M, c->cf_B, c->cf_Zt);
+    hipLaunchKernelGGL(k_cf_sep_assemble, dim3((unsigned)((ns * 36 + 255) / 256)), dim3(256), 0, main, nf, st, ns, c->Hcc, lambda, c->cf_G, c->cf_Zt,
+                       c->cf_Hs, c->cf_Bs);
+  }
+  // second half: the separators' own short chain (one wave, n_sep steps) and its blocks
+  void sep_chain(hipStream_t s) const {
+    hipLaunchKernelGGL(k_cf_chain, dim3(1), dim3(64), 0, s, ns, c->cf_Hs, c->cf_Bs, 0.0, c->cf_LfacS, c->cf_GS, c->chol_info, ns, ns);
+    hipLaunchKernelGGL(k_cf_factor_blocks, dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, s, ns, c->cf_LfacS, c->cf_GS, c->cf_LiS, c->cf_MS, c->cf_NS, 0,
+                       c->cf_Linv, st);   // (+ the separators' L_ii^-1 into the per-slot array: was k_cf_sep_scatter)
+  }
+  // X sparse, the head of every schedule: the segments' chains, the separators' chain, V and vy, the interior rows into the segments'
+  // compact slabs (sums for the separators into R).  beside: the separators' chain on the side stream -- enqueued FIRST: a small grid is
+  // resident at once and a full grid on the other stream fills the rest of the GPU (two full grids do not share it: esl_chol.hpp,
+  // cf_overlap_init) -- beside V and vy of the INTERIOR slots, which need L_ii^-1 of the segments' chains alone; the separator slots'
+  // are then left to the caller, behind cf_ev_s (the separators' blocks exist)
+  int slabs(bool beside) {
+    segment_chains();
+    if (beside) {
+      ESL_HIP_TRY(hipEventRecord(rt.cf_ev_a, main));
+      ESL_HIP_TRY(hipStreamWaitEvent(rt.cf_side, rt.cf_ev_a, 0));
+      join.armed = true;
+    }
+    sep_chain(beside ? rt.cf_side : main);
+    if (beside) ESL_HIP_TRY(hipEventRecord(rt.cf_ev_s, rt.cf_side));
+    edge_scale(beside ? 1 : 0, main);
+    hipLaunchKernelGGL(k_cf_forward<2>, dim3((unsigned)pl.n_fwork), dim3(64), 0, main, nf, n_o, pl.n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V,
+                       c->cf_vy, c->cf_M, c->cf_Xc, ldx, st, st - 1, (const double*)c->cf_Zt, c->cf_R, st, segs());
+    return ESL_OK;
+  }
+  // the separators' right-hand sides from the slabs (sp; else from the dense X), the sums and their own V ...
+  void sep_rhs(hipStream_t s, bool sp = true) const {
+    hipLaunchKernelGGL(k_cf_sep_rhs, dim3(cg, (unsigned)ns), dim3(64), 0, s, nf, n_o, st, pl.n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V, c->cf_vy,
+                       c->cf_G, c->cf_LiS, sp ? c->cf_Xc : c->cf_Xt, ldx, c->cf_R, sp ? (const int*)c->cf_cmap : nullptr, sp ? segs() : CfSegs{});
+  }
+  // ... and the separators' dense rows: into Xs (row block k = separator k), else into X at their slots; one wave per 64 columns
+  void sep_forward(hipStream_t s, bool sp = true) const {
+    hipLaunchKernelGGL(k_cf_forward<1>, dim3(cg), dim3(64), 0, s, ns, n_o, pl.n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V, c->cf_vy,
+                       c->cf_MS, sp ? c->cf_Xs : c->cf_Xt, ldx, ns, ns, (const double*)nullptr, c->cf_R, sp ? 0 : st, CfSegs{});
+  }
+  void products(hipStream_t s) const {   // form 1: the segments' products P_p = Xc_p^T Xc_p and their right-hand sides' rows
+    hipLaunchKernelGGL(k_cf_seg_syrk, dim3((unsigned)pl.n_twork), dim3(256), 0, s, c->cf_twork, c->cf_seg_start, c->cf_seg_first, c->cf_xoff,
+                       c->cf_xld, c->cf_Xc, c->cf_boff, c->cf_P);
+    hipLaunchKernelGGL(k_cf_seg_rhs, dim3((unsigned)pl.n_fwork), dim3(64), 0, s, c->cf_fwork, c->cf_seg_start, c->cf_xoff, c->cf_xld, c->cf_Xc,
+                       c->cf_roff, c->cf_Prhs);
+  }
+  void gather_products(long c_begin, long c_end, int accumulate) const {   // form 1: T = D - sum of the stored products, block by block
+    int o2b, o2e;
+    const dim3 grid = block_grid(c_begin, c_end, o2b, o2e);
+    hipLaunchKernelGGL(k_cf_T_gather, grid, dim3(256), 0, main, N, pl.nw, c->cf_mask, c->cf_cmap, c->cf_boff, c->cf_roff, c->cf_P, c->cf_Prhs,
+                       c->Hoo, c->bo, lambda, c->cf_T, ldt, o2b, o2e, (const int*)c->cf_unrank, accumulate);
+  }
+  // T -= X^T X over the rows of X that are dense: all of them, or (X sparse) the separators' under the staircase
+  void update() const {
+    ProfScope pk(c, 7);   // the rank-K update alone (nested in class 2): the MFMA roofline kernel of this form
+    const double* Xf = pl.sparse ? c->cf_Xs : c->cf_Xt;
+    const int K = (int)(pl.sparse ? pl.kpad_s : pl.kpad);
+    if (!dist && K <= 0) return;
+    my_columns([&](long c_begin, long c_end) {
+      chol_launch_update(rt.sw, c->cf_T, ldt, (long)n_o + 1, main, 0, K, c_begin, c_end, Xf, ldx, dist ? nullptr : c->cf_part, pl.sparse ? c->cf_kfirst : nullptr);
+    });
+  }
+
+  // ---- dense X (plain chain or nested dissection), in stream order ----
+  int build_dense() {
+    // V = Li W, vy = Li b_c of every list entry; the same launch writes the whole of T (D's lower blocks, b_o's row, zeros) -- nothing
+    // reads T before the rank-K update
+    auto edge_scale_T = [&] {
+      const int nb_es = edge_blocks();
+      hipLaunchKernelGGL(k_cf_edge_scale_T, dim3((unsigned)(nb_es + (int)((ldt * (long)n_o + 255) / 256))), dim3(256), 0, main, g, nb_es, pl.n_list, c->cf_oe_u,
+                         c->cf_oe_slot, c->Wbb, c->cf_Linv, c->bc, c->cf_V, c->cf_vy, c->Hoo, c->bo, lambda, c->cf_T, ldt, (long)n_o);
     };
     if (!nd) {
-      hipLaunchKernelGGL(k_cf_chain, dim3(1), dim3(64), 0, c->stream, nf, c->Hcc, c->cf_B, lambda, c->cf_Lfac, c->cf_G, c->chol_info, nf, nf);
-      hipLaunchKernelGGL(k_cf_factor_blocks, dim3((unsigned)((nf + 63) / 64)), dim3(64), 0, c->stream, nf, c->cf_Lfac, c->cf_G, c->cf_Linv, c->cf_M, c->cf_N, 0);
-      launch_edge_scale(0, c->stream);
-      hipLaunchKernelGGL(k_cf_forward<0>, dim3(cg), dim3(64), 0, c->stream, nf, n_o, c->cf_n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V, c->cf_vy,
+      hipLaunchKernelGGL(k_cf_chain, dim3(1), dim3(64), 0, main, nf, c->Hcc, c->cf_B, lambda, c->cf_Lfac, c->cf_G, c->chol_info, nf, nf);
+      hipLaunchKernelGGL(k_cf_factor_blocks, dim3((unsigned)((nf + 63) / 64)), dim3(64), 0, main, nf, c->cf_Lfac, c->cf_G, c->cf_Linv, c->cf_M, c->cf_N, 0);
+      edge_scale_T();
+      hipLaunchKernelGGL(k_cf_forward<0>, dim3(cg), dim3(64), 0, main, nf, n_o, pl.n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V, c->cf_vy,
                          c->cf_M, c->cf_Xt, ldx, nf, nf, (const double*)nullptr, (double*)nullptr, 0, CfSegs{});
-    } else {   // nested dissection (esl_cf.hpp): segments in parallel, then the separators' own short chain
-      hipLaunchKernelGGL(k_cf_chain, dim3((unsigned)nseg), dim3(64), 0, c->stream, nf, c->Hcc, c->cf_B, lambda, c->cf_Lfac, c->cf_G, c->chol_info, st, st - 1);
-      hipLaunchKernelGGL(k_cf_factor_blocks, dim3((unsigned)((nf + 63) / 64)), dim3(64), 0, c->stream, nf, c->cf_Lfac, c->cf_G, c->cf_Linv, c->cf_M, c->cf_N, st);
-      if (nseg > 1) hipLaunchKernelGGL(k_cf_zt, dim3((unsigned)(nseg - 1)), dim3(64), 0, c->stream, nf, st, c->cf_Linv, c->cf_M, c->cf_B, c->cf_Zt);
-      hipLaunchKernelGGL(k_cf_sep_assemble, dim3((unsigned)((ns * 36 + 255) / 256)), dim3(256), 0, c->stream, nf, st, ns, c->Hcc, lambda, c->cf_G, c->cf_Zt,
-                         c->cf_Hs, c->cf_Bs);
-      auto launch_sep_chain = [&](hipStream_t st2) {
-        hipLaunchKernelGGL(k_cf_chain, dim3(1), dim3(64), 0, st2, ns, c->cf_Hs, c->cf_Bs, 0.0, c->cf_LfacS, c->cf_GS, c->chol_info, ns, ns);
-        hipLaunchKernelGGL(k_cf_factor_blocks, dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, st2, ns, c->cf_LfacS, c->cf_GS, c->cf_LiS, c->cf_MS, c->cf_NS, 0,
-                           c->cf_Linv, st);   // (+ the separators' L_ii^-1 into the per-slot array: was k_cf_sep_scatter)
-      };
-      if (side_chain) {
-        ESL_HIP_TRY(hipEventRecord(rt.cf_ev_a, c->stream));
-        ESL_HIP_TRY(hipStreamWaitEvent(rt.cf_side, rt.cf_ev_a, 0));
-        join.armed = true;
-        launch_sep_chain(rt.cf_side);
-        ESL_HIP_TRY(hipEventRecord(rt.cf_ev_s, rt.cf_side));
-        launch_edge_scale(1, c->stream);
-      } else {
-        launch_sep_chain(c->stream);
-        launch_edge_scale(0, c->stream);
-      }
-      if (!c->cf_sparse) {
-        hipLaunchKernelGGL(k_cf_forward<0>, dim3(cg, (unsigned)nseg), dim3(64), 0, c->stream, nf, n_o, c->cf_n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V,
-                           c->cf_vy, c->cf_M, c->cf_Xt, ldx, st, st - 1, (const double*)c->cf_Zt, c->cf_R, st, CfSegs{});
-        hipLaunchKernelGGL(k_cf_sep_rhs, dim3(cg, (unsigned)ns), dim3(64), 0, c->stream, nf, n_o, st, c->cf_n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V, c->cf_vy,
-                           c->cf_G, c->cf_LiS, c->cf_Xt, ldx, c->cf_R, (const int*)nullptr, CfSegs{});
-        hipLaunchKernelGGL(k_cf_forward<1>, dim3(cg), dim3(64), 0, c->stream, ns, n_o, c->cf_n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V, c->cf_vy,
-                           c->cf_MS, c->cf_Xt, ldx, ns, ns, (const double*)nullptr, c->cf_R, st, CfSegs{});
-      } else {   // interior rows into the segments' compact slabs, the separators' dense rows into Xs (row block k = separator k)
-        const CfSegs sg{c->cf_fwork, c->cf_seg_start, c->cf_seg_obj, c->cf_xoff, c->cf_xld, c->cf_rank, c->cf_unrank};
-        hipLaunchKernelGGL(k_cf_forward<2>, dim3((unsigned)c->cf_n_fwork), dim3(64), 0, c->stream, nf, n_o, c->cf_n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V,
-                           c->cf_vy, c->cf_M, c->cf_Xc, ldx, st, st - 1, (const double*)c->cf_Zt, c->cf_R, st, sg);
-        // form 3 with the switch on: everything of the separators stays on the side stream, which waits for the slabs and the sums in R
-        const hipStream_t sst = (os && side) ? rt.cf_side : c->stream;
-        if (os && side) {
-          ESL_HIP_TRY(hipEventRecord(rt.cf_ev_x, c->stream));
-          ESL_HIP_TRY(hipStreamWaitEvent(rt.cf_side, rt.cf_ev_x, 0));
-          launch_edge_scale(2, sst);
-        } else if (side_chain) {   // the separators' chain is needed from here on: their V and vy, then the right-hand sides
-          ESL_HIP_TRY(join.wait(rt.cf_ev_s));
-          launch_edge_scale(2, c->stream);
-        }
-        hipLaunchKernelGGL(k_cf_sep_rhs, dim3(cg, (unsigned)ns), dim3(64), 0, sst, nf, n_o, st, c->cf_n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V, c->cf_vy,
-                           c->cf_G, c->cf_LiS, c->cf_Xc, ldx, c->cf_R, (const int*)c->cf_cmap, sg);
-        if (early_products) ESL_HIP_TRY(hipEventRecord(rt.cf_ev_x, c->stream));   // (the slabs were complete after k_cf_forward<2>; k_cf_sep_rhs only reads them)
-        hipLaunchKernelGGL(k_cf_forward<1>, dim3(cg), dim3(64), 0, sst, ns, n_o, c->cf_n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V, c->cf_vy,
-                           c->cf_MS, c->cf_Xs, ldx, ns, ns, (const double*)nullptr, c->cf_R, 0, CfSegs{});
-        if (os && side) {
-          ESL_HIP_TRY(hipEventRecord(rt.cf_ev_p, rt.cf_side));
-        } else if (side) {   // the products behind k_cf_forward<1>'s 282 waves (C4), beside them.  Measured at C4: the products start 1.4 ms
-                      // earlier, k_cf_forward<1> stretches from 0.61 to 1.08 ms beside them, the update starts 0.32 ms earlier
-          if (!early_products) ESL_HIP_TRY(hipEventRecord(rt.cf_ev_x, c->stream));
-          ESL_HIP_TRY(hipStreamWaitEvent(rt.cf_side, rt.cf_ev_x, 0));
-          join.armed = true;
-          launch_products(rt.cf_side);
-          ESL_HIP_TRY(hipEventRecord(rt.cf_ev_p, rt.cf_side));
-        }
-      }
+    } else {   // segments in parallel, then the separators' own short chain
+      segment_chains();
+      sep_chain(main);
+      edge_scale_T();
+      hipLaunchKernelGGL(k_cf_forward<0>, dim3(cg, (unsigned)nseg), dim3(64), 0, main, nf, n_o, pl.n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V,
+                         c->cf_vy, c->cf_M, c->cf_Xt, ldx, st, st - 1, (const double*)c->cf_Zt, c->cf_R, st, CfSegs{});
+      sep_rhs(main, false);
+      sep_forward(main, false);
     }
-    auto launch_gather = [&](int accumulate) {
-      for (int op = dist ? c->comm_rank : 0; op < (dist ? n_outer : 1); op += dist ? c->comm_ranks : 1) {
-        const long c_begin = dist ? (long)op * Wp * kNB : 0, c_end = dist ? std::min<long>((long)(op + 1) * Wp * kNB, (long)n_o) : (long)n_o;
-        const int o2b = (int)(c_begin / 9), o2e = (int)((c_end + 8) / 9);   // (a block that straddles a panel boundary: on both sides)
-        const dim3 grid((unsigned)(N + 1), (unsigned)((o2e - o2b + kCfTPer - 1) / kCfTPer));
-        if (c->cf_sp_form == 3 && c->cf_os_offsets) {
-          hipLaunchKernelGGL(k_cf_T_onesided_lds, grid, dim3(256), 0, c->stream, N, (const int2*)c->cf_os_pairs, (const long long*)c->cf_os_start,
-                             (const int*)c->cf_os_cnt, c->cf_V, c->cf_Y, c->cf_Yr, c->Hoo, c->bo, lambda, c->cf_T, ldt, o2b, o2e, (const int*)c->cf_unrank, accumulate);
-        } else if (c->cf_sp_form == 3)
-          hipLaunchKernelGGL(k_cf_T_onesided, grid, dim3(256), 0, c->stream, N, (const int2*)c->cf_os_pairs, (const long long*)c->cf_os_start,
-                             (const int*)c->cf_os_cnt, c->cf_V, c->cf_Y, c->cf_Yr, c->Hoo, c->bo, lambda, c->cf_T, ldt, o2b, o2e, (const int*)c->cf_unrank, accumulate);
-        else if (c->cf_sp_form == 1)
-          hipLaunchKernelGGL(k_cf_T_gather, grid, dim3(256), 0, c->stream, N, c->cf_sp_nw, c->cf_mask, c->cf_cmap, c->cf_boff, c->cf_roff, c->cf_P, c->cf_Prhs,
-                             c->Hoo, c->bo, lambda, c->cf_T, ldt, o2b, o2e, (const int*)c->cf_unrank, accumulate);
-        else
-          hipLaunchKernelGGL(k_cf_T_sparse, grid, dim3(256), 0, c->stream, N, c->cf_sp_nw, c->cf_mask, c->cf_cmap, c->cf_xoff, c->cf_xld, c->cf_Xc, c->Hoo, c->bo,
-                             lambda, c->cf_T, ldt, o2b, o2e, (const int*)c->cf_unrank);
-      }
-    };
-    auto launch_update = [&]() {   // T -= X^T X over the rows of X that are dense: all of them, or (X sparse) the separators'
-      ProfScope pk(c, 7);   // the rank-K update alone (nested in class 2): the MFMA roofline kernel of this form
-      const double* Xf = c->cf_sparse ? c->cf_Xs : c->cf_Xt;
-      const int K = (int)(c->cf_sparse ? c->cf_kpad_s : c->cf_kpad);
-      if (dist) {
-        for (int op = c->comm_rank; op < n_outer; op += c->comm_ranks) {
-          const long c_begin = (long)op * Wp * kNB, c_end = std::min<long>((long)(op + 1) * Wp * kNB, (long)n_o);
-          chol_launch_update(rt.sw, c->cf_T, ldt, (long)n_o + 1, c->stream, 0, K, c_begin, c_end, Xf, ldx, nullptr, c->cf_sparse ? c->cf_kfirst : nullptr);
-        }
-      } else if (K > 0) {
-        chol_launch_update(rt.sw, c->cf_T, ldt, (long)n_o + 1, c->stream, 0, K, 0, (long)n_o, Xf, ldx, c->cf_part, c->cf_sparse ? c->cf_kfirst : nullptr);
-      }
-    };
-    if (os) {   // Y behind the slabs, T = D - sum from V and Y; the update last, uncapped, with nothing beside it
-      // ESL_CF_OS_ORDER=1 (A/B, profiles/cf_onesided_c4.md): the update first in its assign form, the assembly adding D - sum behind
-      // it -- (D - sum) + (-acc), the same double as (D - sum) - acc
-      static const bool update_first = [] { const char* e = std::getenv("ESL_CF_OS_ORDER"); return e && e[0] == '1'; }();
-      const bool swap = update_first && chol_update_v_applies(rt.sw, ldt, (long)n_o + 1, 0, (long)n_o, true, ldx);
-      if (swap) {
-        if (side) ESL_HIP_TRY(join.wait(rt.cf_ev_p));
-        ProfScope pk(c, 7);
-        chol_launch_update(rt.sw, c->cf_T, ldt, (long)n_o + 1, c->stream, 0, Ks_, 0, (long)n_o, c->cf_Xs, ldx, nullptr, c->cf_kfirst, true, false);
-      }
+    ESL_HIP_TRY(hipGetLastError());
+    update();
+    return ESL_OK;
+  }
+
+  // ---- X sparse, forms 1 (stored products) and 2 (blocks straight from the slabs), every launch in stream order: ESL_CF_OVERLAP=0, and
+  // the only schedule of a run with a communicator (the products on every rank, 3 % of a trial; gather and update over this rank's panels) ----
+  int build_stored_serial() {
+    if (int rc = slabs(false)) return rc;
+    sep_rhs(main);
+    sep_forward(main);
+    {   // T = D - (interior rows)^T (interior rows), block by block (every block on and below the diagonal is written)
+      ProfScope pk(c, 8);
+      if (pl.form == 1) products(main);
+      my_columns([&](long c_begin, long c_end) {
+        if (pl.form == 1) { gather_products(c_begin, c_end, 0); return; }
+        int o2b, o2e;
+        const dim3 grid = block_grid(c_begin, c_end, o2b, o2e);
+        hipLaunchKernelGGL(k_cf_T_sparse, grid, dim3(256), 0, main, N, pl.nw, c->cf_mask, c->cf_cmap, c->cf_xoff, c->cf_xld, c->cf_Xc, c->Hoo, c->bo,
+                           lambda, c->cf_T, ldt, o2b, o2e, (const int*)c->cf_unrank);
+      });
+    }
+    ESL_HIP_TRY(hipGetLastError());
+    update();
+    return ESL_OK;
+  }
+
+  // ---- X sparse, form 1 on a single rank with the side stream (ESL_CF_OVERLAP=ov, 1 to 4).  Two dependent chains meet only at k_cf_sep_rhs:
+  //   interior    k_cf_edge_scale (interior slots) -> k_cf_forward<2> -> the segments' products (k_cf_seg_syrk, k_cf_seg_rhs)
+  //   separators  k_cf_chain (one wave, n_sep steps) -> k_cf_factor_blocks -> V, vy of the separator slots -> [k_cf_forward<2>'s slabs
+  //               and sums] -> k_cf_sep_rhs -> k_cf_forward<1> (one wave per 64 columns) -> the rank-K update
+  // so (1) the separators' chain and its blocks run on the side stream beside the interior pipeline (ov != 3) and (2) the products,
+  // which need the slabs alone, run there beside k_cf_forward<1> (ov != 2; each alone: A/B) and the update.
+  // No arithmetic and no address changes, so every array has the bits of the serial order.
+  // Across trials: the side chain of trial t + 1 writes cf_LfacS, cf_GS, cf_LiS, cf_MS, cf_NS and the separators' slots of cf_Linv,
+  // which trial t's k_cf_edge_scale (separator slots), k_cf_sep_rhs, k_cf_forward<1>, k_cf_tridiag_back and k_cf_back_prep read: all of
+  // them are on the main stream in front of trial t + 1's cf_ev_a, which the side chain waits for.  Trial t + 1's k_cf_forward<2>
+  // writes the slabs trial t's products read: the main stream has waited for trial t's cf_ev_p.  cf_ensure's relayout, esl_ctx_trim
+  // and everything else on the main stream are covered the same way, because every way out of a trial leaves the side stream joined
+  // to the main one (CfSideJoin). ----
+  int build_stored_side(int ov) {
+    const bool side_chain = ov != 3, early_products = ov != 2;
+    if (int rc = slabs(side_chain)) return rc;
+    if (side_chain) {   // the separators' chain is needed from here on: their V and vy, then the right-hand sides
+      ESL_HIP_TRY(join.wait(rt.cf_ev_s));
+      edge_scale(2, main);
+    }
+    sep_rhs(main);
+    // cf_ev_x, the products may start: the slabs were complete after k_cf_forward<2> and k_cf_sep_rhs only reads them, so in front
+    // of k_cf_forward<1>'s 282 waves (C4), beside them -- or (ov == 2) behind them.  Measured at C4: the products start 1.4 ms
+    // earlier, k_cf_forward<1> stretches from 0.61 to 1.08 ms beside them, the update starts 0.32 ms earlier
+    if (early_products) ESL_HIP_TRY(hipEventRecord(rt.cf_ev_x, main));
+    sep_forward(main);
+    if (!early_products) ESL_HIP_TRY(hipEventRecord(rt.cf_ev_x, main));
+    ESL_HIP_TRY(hipStreamWaitEvent(rt.cf_side, rt.cf_ev_x, 0));
+    join.armed = true;
+    products(rt.cf_side);
+    ESL_HIP_TRY(hipEventRecord(rt.cf_ev_p, rt.cf_side));   // cf_ev_p: the products are stored
+    if (chol_update_v_applies(rt.sw, ldt, (long)n_o + 1, 0, (long)n_o, true, ldx)) {
+      // with the update on its k_chol_update_v path (the one with an assign form) the products also run beside the UPDATE (round 6): it
+      // ASSIGNS T = -Xs^T Xs instead of updating what the gather wrote, and the gather, which then comes last, adds its D - sum to that --
+      // (D - sum) + (-acc) is the same double as (D - sum) - acc, so T has the same bits
       {
-        ProfScope pk(c, 8);
-        auto seg_back = [&](auto mch) {   // (the segment's chunks: the kernel's register arrays want a compile-time length)
-          hipLaunchKernelGGL(k_cf_seg_back<decltype(mch)::value>, dim3((unsigned)c->cf_n_fwork), dim3(64), 0, c->stream, nf, c->cf_fwork, c->cf_seg_start, c->cf_xoff,
-                             c->cf_xld, c->cf_Xc, c->cf_Linv, c->cf_G, c->cf_Y, c->cf_Yr);
-        };
-        if (st == 3 * kCfFwdCh) seg_back(std::integral_constant<int, 3>{});
-        else if (st == 2 * kCfFwdCh) seg_back(std::integral_constant<int, 2>{});
-        else seg_back(std::integral_constant<int, 1>{});
-        launch_gather(swap ? 1 : 0);
-      }
-      ESL_HIP_TRY(hipGetLastError());
-      if (!swap) {
-        if (side) ESL_HIP_TRY(join.wait(rt.cf_ev_p));
-        launch_update();
-      }
-    } else if (assign) {
-      {
-        // ESL_CF_OVERLAP=4 (default): the update CAPPED to one workgroup per CU (chol_launch_update's `cap`).  At its two workgroups
+        // ov == 4 (default): the update CAPPED to one workgroup per CU (chol_launch_update's `cap`).  At its two workgroups
         // per CU (252 registers a lane) every slot that frees goes to the next update workgroup and the products' waves (240) are
         // placed only when the update has nothing left to dispatch; capped, one products workgroup is resident on every CU beside it.
         // C4: the update stretches from 16.4 to 20.0 ms and the products end with it instead of 4.5 ms later
         ProfScope pk(c, 7);   // the rank-K update (assign form), with the products running beside it
-        chol_launch_update(rt.sw, c->cf_T, ldt, (long)n_o + 1, c->stream, 0, Ks_, 0, (long)n_o, c->cf_Xs, ldx, nullptr, c->cf_kfirst, true, c->sw_cf_overlap == 4);
+        chol_launch_update(rt.sw, c->cf_T, ldt, (long)n_o + 1, main, 0, (int)pl.kpad_s, 0, (long)n_o, c->cf_Xs, ldx, nullptr, c->cf_kfirst, true, ov == 4);
       }
       ESL_HIP_TRY(join.wait(rt.cf_ev_p));
-      {
-        ProfScope pk(c, 8);   // (what is left of the products' path on this stream: the gather)
-        launch_gather(1);
-      }
-    } else if (side) {   // (the update has no assign form at this size: the products ran beside k_cf_forward<1> alone)
+      ProfScope pk(c, 8);   // (what is left of the products' path on this stream: the gather)
+      gather_products(0, (long)n_o, 1);
+    } else {   // (the update has no assign form at this size: the products ran beside k_cf_forward<1> alone)
       ESL_HIP_TRY(join.wait(rt.cf_ev_p));
       {
         ProfScope pk(c, 8);
-        launch_gather(0);
+        gather_products(0, (long)n_o, 0);
       }
       ESL_HIP_TRY(hipGetLastError());
-      launch_update();
-    } else {
-      if (c->cf_sparse) {   // T = D - (interior rows)^T (interior rows), block by block (every block on and below the diagonal is written)
-        ProfScope pk(c, 8);   // (X dense: T was written whole by the edge-scale launch)
-        if (c->cf_sp_form == 1)   // the segments' products (all of them on every rank: 3 % of a trial)
-          launch_products(c->stream);
-        launch_gather(0);
+      update();
+    }
+    return ESL_OK;
+  }
+
+  // ---- X sparse, form 3 (one-sided assembly, esl_cf.hpp; single rank).  The assembly needs Y alone, which exists straight behind
+  // k_cf_forward<2>, so with the side stream (`beside`: ESL_CF_OVERLAP != 0) the WHOLE separator path -- chain, V and vy of the
+  // separator slots, k_cf_sep_rhs, k_cf_forward<1> -- runs there beside k_cf_seg_back and the assembly, and the update (uncapped, in
+  // its accumulate form, with nothing beside it) waits for the assembly and Xs only.  One arithmetic order for T at either setting:
+  // T = D - sum (assign), then T -= Xs^T Xs.  Hazards across trials: as in build_stored_side, with cf_ev_p = Xs is complete. ----
+  int build_onesided(bool beside) {
+    const hipStream_t sst = beside ? rt.cf_side : main;   // the separators' stream
+    if (int rc = slabs(beside)) return rc;
+    if (beside) {   // the side stream, which holds the separators' chain, waits for the slabs and the sums in R (cf_ev_x)
+      ESL_HIP_TRY(hipEventRecord(rt.cf_ev_x, main));
+      ESL_HIP_TRY(hipStreamWaitEvent(rt.cf_side, rt.cf_ev_x, 0));
+      edge_scale(2, rt.cf_side);
+    }
+    sep_rhs(sst);
+    sep_forward(sst);
+    if (beside) ESL_HIP_TRY(hipEventRecord(rt.cf_ev_p, rt.cf_side));
+    {   // Y behind the slabs, T = D - sum from V and Y
+      ProfScope pk(c, 8);
+      auto seg_back = [&](auto mch) {   // (the segment's chunks: the kernel's register arrays want a compile-time length)
+        hipLaunchKernelGGL(k_cf_seg_back<decltype(mch)::value>, dim3((unsigned)pl.n_fwork), dim3(64), 0, main, nf, c->cf_fwork, c->cf_seg_start, c->cf_xoff,
+                           c->cf_xld, c->cf_Xc, c->cf_Linv, c->cf_G, c->cf_Y, c->cf_Yr);
+      };
+      if (st == 3 * kCfFwdCh) seg_back(std::integral_constant<int, 3>{});
+      else if (st == 2 * kCfFwdCh) seg_back(std::integral_constant<int, 2>{});
+      else seg_back(std::integral_constant<int, 1>{});
+      const dim3 grid((unsigned)(N + 1), (unsigned)((N + kCfTPer - 1) / kCfTPer));
+      // whole records through LDS, or the per-lane gather: same bits
+      hipLaunchKernelGGL(pl.os_offsets ? k_cf_T_onesided_lds : k_cf_T_onesided, grid, dim3(256), 0, main, N, (const int2*)c->cf_os_pairs,
+                         (const long long*)c->cf_os_start, (const int*)c->cf_os_cnt, c->cf_V, c->cf_Y, c->cf_Yr, c->Hoo, c->bo, lambda, c->cf_T, ldt, 0, N,
+                         (const int*)c->cf_unrank, 0);
+    }
+    ESL_HIP_TRY(hipGetLastError());
+    if (beside) ESL_HIP_TRY(join.wait(rt.cf_ev_p));
+    update();
+    return ESL_OK;
+  }
+
+  // ---- every form: dense Cholesky of the reduced ellipsoid system, the camera back-substitution, trial states and their chi2 ----
+  int back_substitute() const {
+    {
+      ProfScope ps(c, 3);
+      double* xsol = (pl.sparse && pl.tperm) ? c->cf_xo_t : c->xo;   // the solver's x_o: in T's column order
+      if (dist) {
+        CholDist d;
+        if (int rc = chol_dist_fill(c, n_o, d)) return rc;
+        ESL_HIP_TRY(chol_factor_solve(c->cf_T, ldt, n_o, c->cf_Linv_ws, c->z_ws, xsol, c->chol_info, main, rt, &d));
+      } else {
+        ESL_HIP_TRY(chol_factor_solve(c->cf_T, ldt, n_o, c->cf_Linv_ws, c->z_ws, xsol, c->chol_info, main, rt));
+      }
+      if (xsol != c->xo) hipLaunchKernelGGL(k_cf_xo_unpermute, dim3((unsigned)((n_o + 255) / 256)), dim3(256), 0, main, N, c->cf_rank, xsol, c->xo);
+      if (pl.sparse)
+        hipLaunchKernelGGL(k_cf_z_sparse, dim3((unsigned)(6 * nf)), dim3(256), 0, main, n_o, c->cf_Xs, ldx, segs(), c->cf_Xc, c->xo, xsol, c->cf_z, st);
+      else
+        hipLaunchKernelGGL(k_cf_z, dim3((unsigned)(6 * nf)), dim3(256), 0, main, c->cf_Xt, ldx, n_o, c->xo, c->cf_z);
+      if (nd) {
+        hipLaunchKernelGGL(k_cf_tridiag_back, dim3(1), dim3(64), 0, main, ns, c->cf_LiS, c->cf_NS, c->cf_z, c->xc, ns, ns, st);            // separators
+        hipLaunchKernelGGL(k_cf_back_prep, dim3((unsigned)((6 * nf + 255) / 256)), dim3(256), 0, main, nf, st, ns, c->cf_Zt, c->cf_G, c->xc, c->cf_z);
+        hipLaunchKernelGGL(k_cf_tridiag_back, dim3((unsigned)nseg), dim3(64), 0, main, nf, c->cf_Linv, c->cf_N, c->cf_z, c->xc, st, st - 1, 0);  // segments
+      } else {
+        hipLaunchKernelGGL(k_cf_tridiag_back, dim3(1), dim3(64), 0, main, nf, c->cf_Linv, c->cf_N, c->cf_z, c->xc, nf, nf, 0);
       }
       ESL_HIP_TRY(hipGetLastError());
-      launch_update();
     }
-    ESL_HIP_TRY(hipGetLastError());
-  }
-  {
-    ProfScope ps(c, 3);   // dense Cholesky of the reduced ellipsoid system + the camera back-substitution
-    double* xsol = (c->cf_sparse && c->cf_tperm) ? c->cf_xo_t : c->xo;   // the solver's x_o: in T's column order
-    if (cf_dist(c)) {
-      CholDist d;
-      if ((rc = chol_dist_fill(c, n_o, d))) return rc;
-      ESL_HIP_TRY(chol_factor_solve(c->cf_T, ldt, n_o, c->cf_Linv_ws, c->z_ws, xsol, c->chol_info, c->stream, rt, &d));
-    } else {
-      ESL_HIP_TRY(chol_factor_solve(c->cf_T, ldt, n_o, c->cf_Linv_ws, c->z_ws, xsol, c->chol_info, c->stream, rt));
-    }
-    if (xsol != c->xo) hipLaunchKernelGGL(k_cf_xo_unpermute, dim3((unsigned)((n_o + 255) / 256)), dim3(256), 0, c->stream, N, c->cf_rank, xsol, c->xo);
-    if (c->cf_sparse)
-      hipLaunchKernelGGL(k_cf_z_sparse, dim3((unsigned)(6 * nf)), dim3(256), 0, c->stream, n_o, c->cf_Xs, ldx,
-                         CfSegs{c->cf_fwork, c->cf_seg_start, c->cf_seg_obj, c->cf_xoff, c->cf_xld, c->cf_rank, c->cf_unrank}, c->cf_Xc, c->xo, xsol, c->cf_z,
-                         c->cf_stride);
-    else
-      hipLaunchKernelGGL(k_cf_z, dim3((unsigned)(6 * nf)), dim3(256), 0, c->stream, c->cf_Xt, ldx, n_o, c->xo, c->cf_z);
-    if (c->cf_stride > 0 && c->cf_n_sep > 0) {
-      const int st = c->cf_stride, ns = c->cf_n_sep;
-      hipLaunchKernelGGL(k_cf_tridiag_back, dim3(1), dim3(64), 0, c->stream, ns, c->cf_LiS, c->cf_NS, c->cf_z, c->xc, ns, ns, st);            // separators
-      hipLaunchKernelGGL(k_cf_back_prep, dim3((unsigned)((6 * nf + 255) / 256)), dim3(256), 0, c->stream, nf, st, ns, c->cf_Zt, c->cf_G, c->xc, c->cf_z);
-      hipLaunchKernelGGL(k_cf_tridiag_back, dim3((unsigned)c->cf_n_seg), dim3(64), 0, c->stream, nf, c->cf_Linv, c->cf_N, c->cf_z, c->xc, st, st - 1, 0);  // segments
-    } else {
-      hipLaunchKernelGGL(k_cf_tridiag_back, dim3(1), dim3(64), 0, c->stream, nf, c->cf_Linv, c->cf_N, c->cf_z, c->xc, nf, nf, 0);
-    }
-    ESL_HIP_TRY(hipGetLastError());
-  }
-  {
     ProfScope ps(c, 1);
-    const int nb_obj = (N + 255) / 256, nb_cam = (F + 255) / 256;
-    hipLaunchKernelGGL(k_cf_updates, dim3((unsigned)(nb_obj + nb_cam)), dim3(256), 0, c->stream, g, nb_obj, lambda, c->objs, c->bo, c->xo, c->objs_trial, c->obj_part,
+    const int F = g.n_cams, nb_obj = (N + 255) / 256, nb_cam = (F + 255) / 256;
+    hipLaunchKernelGGL(k_cf_updates, dim3((unsigned)(nb_obj + nb_cam)), dim3(256), 0, main, g, nb_obj, lambda, c->objs, c->bo, c->xo, c->objs_trial, c->obj_part,
                        c->cams, c->xc, c->bc, c->cams_trial, c->cam_part);
     const int nb_co = (N + kWavesPerBlock - 1) / kWavesPerBlock, nb_od = (g.n_odom + kWave * kWavesPerBlock - 1) / (kWave * kWavesPerBlock);
     robust_dispatch(c->robust_on, [&](auto robust) {
-      hipLaunchKernelGGL(k_slam_chi2_all<decltype(robust)::value>, dim3((unsigned)(nb_co + nb_od)), dim3(kWave * kWavesPerBlock), 0, c->stream, g, nb_co,
+      hipLaunchKernelGGL(k_slam_chi2_all<decltype(robust)::value>, dim3((unsigned)(nb_co + nb_od)), dim3(kWave * kWavesPerBlock), 0, main, g, nb_co,
                          c->cams_trial, c->objs_trial, c->obj_part, c->od_part);
     });
     ESL_HIP_TRY(hipGetLastError());
+    return ESL_OK;
   }
-  return ESL_OK;
+};
+}  // namespace
+static int slam_try_step_cf(esl_ctx* c, double lambda) {
+  int rc = cf_ensure(c);
+  if (rc) return rc;
+  const CfPlan& pl = c->cf_plan;
+  CfTrial t(c, chol_rt(c), lambda);
+  {
+    ProfScope ps(c, 2);   // "reduced-system build"
+    ESL_HIP_TRY(hipMemsetAsync(c->chol_info, 0, sizeof(int), c->stream));
+    hipLaunchKernelGGL(k_cf_gather_B, dim3((unsigned)(((long)t.nf * 36 + 255) / 256)), dim3(256), 0, c->stream, t.nf, c->Aod, c->cf_od_start, c->cf_od_edge, c->cf_B);
+    ESL_HIP_TRY(chol_set_attributes(t.rt));   // (fills rt.sw)
+    if (!pl.sparse) rc = t.build_dense();
+    else if (!t.nd) {   // (ESL_CF_ND_MIN above this graph's free cameras with X forced sparse: there is no such schedule, and never was)
+      set_error("camera-first elimination: sparse X needs the dissected camera chain");
+      rc = ESL_ERR_STATE;
+    }
+    else {
+      // the side stream: a single rank's forms 1 and 3, unless ESL_CF_OVERLAP was 0 when the context was created or the stream cannot be made
+      const bool side = c->sw_cf_overlap != 0 && (pl.form == 1 || pl.form == 3) && !t.dist && pl.kpad_s > 0 && t.rt.cf_overlap_init() == hipSuccess;
+      rc = pl.form == 3 ? t.build_onesided(side) : side ? t.build_stored_side(c->sw_cf_overlap) : t.build_stored_serial();
+    }
+    if (rc) return rc;
+    ESL_HIP_TRY(hipGetLastError());
+  }
+  return t.back_substitute();
 }
 
 // Sharded runs: factor the reduced camera system distributed over the ranks (esl_chol.hpp, CholDist) instead of all-reducing
@@ -1504,17 +1341,18 @@ extern "C" int esl_lm_solver_stats(esl_ctx* c, double* st) {
   if (!c || !st) return ESL_ERR_INVALID;
   for (int k = 0; k < ESL_SOLVER_STATS; ++k) st[k] = 0;
   if (c->lm_solver_used != ESL_SOLVER_REDUCED_ELLIPSOID || !c->cf_ready) return ESL_OK;
-  st[0] = c->cf_sparse ? c->cf_sp_form : 0;
-  st[1] = c->cf_stride; st[2] = c->cf_n_sep; st[3] = c->cf_n_seg;
-  if (c->cf_sparse) {
-    st[4] = 2.0 * c->cf_sp_flops;   // (FMAs of the block lower triangles, rows from each block row's first camera on)
-    st[5] = c->cf_sp_form == 1 ? 8.0 * 81.0 * (double)c->cf_p_blocks : 0.0;
-    if (c->cf_sp_form == 3) { st[4] = c->cf_os_flops; st[5] = 8.0 * (double)c->cf_y_len; }   // (the one-sided assembly's products; bytes of Y)
-    st[6] = 8.0 * (double)c->cf_xc_len;
+  const esl::CfPlan& pl = c->cf_plan;
+  st[0] = pl.sparse ? pl.form : 0;
+  st[1] = pl.stride; st[2] = pl.n_sep; st[3] = pl.n_seg;
+  if (pl.sparse) {
+    st[4] = 2.0 * pl.sp_flops;   // (FMAs of the block lower triangles, rows from each block row's first camera on)
+    st[5] = pl.form == 1 ? 8.0 * 81.0 * (double)pl.p_blocks : 0.0;
+    if (pl.form == 3) { st[4] = pl.os_flops; st[5] = 8.0 * (double)pl.y_len; }   // (the one-sided assembly's products; bytes of Y)
+    st[6] = 8.0 * (double)pl.xc_len;
   }
-  st[7] = (double)(c->cf_sparse ? c->cf_kpad_s : c->cf_kpad);
-  st[8] = c->cf_tperm ? c->cf_upd_flops : 0.0;   // (0: the whole lower triangle times K)
-  st[9] = c->cf_tperm ? 1.0 : 0.0;
+  st[7] = (double)(pl.sparse ? pl.kpad_s : pl.kpad);
+  st[8] = pl.tperm ? pl.upd_flops : 0.0;   // (0: the whole lower triangle times K)
+  st[9] = pl.tperm ? 1.0 : 0.0;
   return ESL_OK;
 }
 extern "C" int esl_lm_pcg_stats(esl_ctx* c, double* st) {
@@ -1565,7 +1403,7 @@ extern "C" int esl_debug_update_v_applies(int64_t lda, int64_t rows, int64_t bas
   return ESL_OK;
 }
 
-// test / debug: the segment length the layout would choose for form 3 from these counts (esl_cf.hpp, cf_stride_choose), and the
+// test / debug: the segment length the layout would choose for form 3 from these counts (esl_cf_plan.hpp, cf_stride_choose), and the
 // model's ms per stride.  A pure host function
 extern "C" int esl_debug_cf_stride_choose(int64_t n_o, const double upd_flops[3], const double pairs[3], const double slab[3], int32_t* stride_out,
                                           double ms_out[3]) {

@@ -5,7 +5,7 @@ camera (slot = camera - 1: camera 0 is the fixed one).
     python scripts/cf_onesided_counts.py [C4] [stride ...]
 
 The full report is for dissection stride 16; behind it one line per stride given (default 16 24 32 48): what the assembly
-multiplies and reads with segments that long (the library runs 16, 32 or 48: esl_cf.hpp, cf_stride_choose, which weighs these
+multiplies and reads with segments that long (the library runs 16, 32 or 48: esl_cf_plan.hpp, cf_stride_choose, which weighs these
 entry-products against the separators' update and the slabs).  block_pairs() is the per-block count of the
 assembly's pair list (tests/test_cf_onesided_pairs.py).
 """

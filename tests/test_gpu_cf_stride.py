@@ -1,4 +1,4 @@
-"""Camera-first elimination, form 3 with camera segments of two and three chunks (esl_cf.hpp, "choosing the segment length"): every
+"""Camera-first elimination, form 3 with camera segments of two and three chunks (esl_cf_plan.hpp, "choosing the segment length"): every
 32nd or 48th free camera is a separator instead of every 16th.  Another, equally exact elimination order of the same linear system:
 a forced stride is held against the dense X (ESL_CF_SPARSE=0) and the reduced camera system with the bounds
 tests/test_gpu_cf_onesided.py holds the stride-16 form to, and against itself bit for bit where only the stream order or the layout's
@@ -8,6 +8,7 @@ host function and is checked on a table of counts without a GPU.
 import numpy as np
 import pytest
 
+from tests import cf_plan_ref
 from tests.test_gpu_cf_onesided import _assert_same_runs, _first_trial_and_run, _graph, _hold_against, _refs
 from tests.test_gpu_cf_sep_overlap import ITERS, _same_bits, _two_runs
 
@@ -181,7 +182,38 @@ def test_stride_32_trim_between_optimize_calls(pkg, monkeypatch):
     assert _same_bits(s0[0], s1[0]) and _same_bits(s0[1], s1[1])
 
 
-# ---- the rule that chooses the stride (esl_cf.hpp, cf_stride_choose): a host function, no GPU ----------------------------------------
+@gpu
+def test_the_plan_the_device_ran_is_the_host_plan(pkg, monkeypatch, tmp_path):
+    """The layout the library ships is cf_plan_build's (csrc/esl_cf_plan.hpp), which tests/test_cf_plan.py pins on the CPU: after one trial
+    all ten numbers of esl_lm_solver_stats equal what tests/cf_plan_main.cpp, compiled here, prints for the same lists and switches -- the
+    flops as exact doubles.  256 free cameras, 40 ellipsoids: X dense with nothing set (9 N < 2,048), forms 1 and 2, form 3 at strides 32
+    and 48 (a short last segment).  (The device's memory size only decides between forms 1 and 2, at gigabytes: this graph's need is a
+    few megabytes, so the program's default stands for it.)"""
+    g, c, o = _graph(257, 40, 6)
+    exe = cf_plan_ref.build(tmp_path)
+    assert exe, "no host compiler"
+    L = cf_plan_ref.lists(g)
+    for sparse, stride, form in ((None, None, 0), ("1", None, 1), ("2", None, 2), ("3", 32, 3), ("3", 48, 3)):
+        if sparse is None:
+            monkeypatch.delenv("ESL_CF_SPARSE", raising=False)
+        else:
+            monkeypatch.setenv("ESL_CF_SPARSE", sparse)
+        cx = _context(pkg, monkeypatch, stride, overlap=None)
+        try:
+            cx.upload_graph(g); cx.upload_states(c, o)
+            cx.lm_begin(pkg.default_lm_params(jacobian_mode=1, linear_solver=2))
+            tr = cx.lm_try_step(1e-5 * cx.lm_linearize().max_diag)
+            assert tr.solve_ok == 1 and cx.lm_solver_used() == 2
+            st = list(cx.lm_solver_stats().values())
+        finally:
+            cx.close()
+            monkeypatch.delenv("ESL_CF_SPARSE", raising=False)
+        want = cf_plan_ref.solver_stats(cf_plan_ref.run(exe, L, tmp_path, sparse=-1 if sparse is None else int(sparse), stride=stride or 0))
+        print("ESL_CF_SPARSE", sparse, "ESL_CF_STRIDE", stride, "stats", st)
+        assert st[0] == form and st == [float(x) for x in want], (st, want)
+
+
+# ---- the rule that chooses the stride (esl_cf_plan.hpp, cf_stride_choose): a host function, no GPU ----------------------------------------
 # ms per trial = update flops / (0.83 x 79 TFLOP/s) + entry-products x 0.078 ms per million + slab elements x 1.30 ms / 1.35e8; a wider
 # stride is taken when it is under 0.95 of the stride-16 figure, the cheapest of them; 16 below 8,192 unknowns.
 _UPD, _PAIR, _SLAB = 0.83 * 79.0e9, (7.82 - 4.21) / (77.35e6 - 31.05e6), 1.30 / 1.35e8
