@@ -371,6 +371,13 @@ int esl_lm_solver_used(esl_ctx* ctx, int32_t* solver_out);
  *     staircase are skipped tile by tile (0: the closed form n (n + 1) K applies), [9] 1 if T is in that order. */
 #define ESL_SOLVER_STATS 10
 int esl_lm_solver_stats(esl_ctx* ctx, double stats[ESL_SOLVER_STATS]);
+/* the pair list of the one-sided assembly (form 3) of the resident graph as the last trial step ran it (zeros otherwise), in record
+ * pairs, the b row included: counts[0] the row side over every list entry (what stats[4] prices), [1] with a camera's bounding-box
+ * and 3-D edge to one ellipsoid merged into one pair, [2] merged and, per block and shared segment, the side with fewer pairs;
+ * [3] the length of the list that was built ([2], or [0] with ESL_CF_OS_LIST=0 when the context was created), [4] the flops of its
+ * 9 x 6 . 6 x 9 products, [5] its bytes. */
+#define ESL_OS_COUNTS 6
+int esl_lm_os_counts(esl_ctx* ctx, double counts[ESL_OS_COUNTS]);
 
 /* inspection (tests, debugging): copy one device array of the current linearisation to the host.
  * which: 0 Hoo (n_objs x 45 packed upper 9x9), 1 bo (n_objs x 9), 2 xo (n_objs x 9, last trial),

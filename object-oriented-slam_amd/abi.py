@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 ESL_MAX_TRACE = 32
+ESL_OS_COUNTS = 6   # esl_lm_os_counts
 
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)

@@ -314,7 +314,7 @@ struct CfSegs {
   const int* fwork; const int* seg_start; const int* seg_obj; const long long* xoff; const int* xld;
   const int* rank; const int* unrank;
 };
-template <int MODE>
+template <int MODE, int PARTS = 2>
 static __global__ __launch_bounds__(64) void k_cf_forward(int nf_all, int n_o, int n_chunks, const int* __restrict__ oe_cst /* [N][n_chunks + 1] */,
                                                           const int* __restrict__ oe_slot, const double* __restrict__ V,
                                                           const double* __restrict__ vy, const double* __restrict__ Mm,
@@ -327,7 +327,10 @@ static __global__ __launch_bounds__(64) void k_cf_forward(int nf_all, int n_o, i
   // one-wave workgroup instead of 59 KB, so four of them fit a CU where two did (the grid is 23,565 waves at C4 and the kernel is
   // bound by the waves in flight).  The entries of a slot are still added in list order, each half walks the chunk's entry
   // range and takes its own slots: every sum has the bits it had.  MODE 0 and MODE 1: one part, the whole chunk.
-  constexpr int CH = MODE == 2 ? kCfFwdCh / 2 : kCfFwdCh;
+  // PARTS (MODE 2; ESL_CF_FWD_PARTS, esl_ctx.hpp): the same in quarters or eighths of a chunk -- 22 KB and 16 KB per workgroup, seven
+  // and ten of them per CU.  Same sums, same bits, whatever the parts.
+  static_assert(PARTS == 2 || (MODE == 2 && (PARTS == 4 || PARTS == 8)), "halves, quarters or eighths of a chunk");
+  constexpr int CH = MODE == 2 ? kCfFwdCh / PARTS : kCfFwdCh;
   __shared__ double sv[CH * 6 * 64];
   __shared__ double svy[kCfFwdCh * 6];
   const int lane = threadIdx.x;
@@ -1052,7 +1055,8 @@ static __global__ __launch_bounds__(256) void k_cf_T_gather(int N, int nw, const
 //                    the separator is not part of L_p).  One 432-byte record per (compact ellipsoid, interior slot), [b][a] like V:
 //                    Y[((seg_start[p] + i) (stride - 1) + pos) 54 + 6 b + a]; the right-hand side's column to Yr[6 slot + a].
 //   k_cf_T_onesided  ownership and order of k_cf_T_gather (one wave per block of T, lower triangle + the b row, the segments two
-//                    ellipsoids share, ascending); per segment o1's entries in list order, each a 9 x 6 . 6 x 9 product on
+//                    ellipsoids share, ascending); per segment the pairs of the layout's list (k_cf_os_list below: o1's entries in
+//                    list order, or with twins merged and the shorter side walked), each a 9 x 6 . 6 x 9 product on
 //                    v_mfma_f64_16x16x4 with the block's pairs concatenated along K (zero padded to a multiple of four at the
 //                    block's end).  The b row walks o2's entries against Yr.  No atomics.
 // A segment is M chunks of kCfFwdCh slots (M = 1, 2, 3: stride 16, 32, 48), its last slot the separator: 16 M - 1 interior slots.  The
@@ -1132,12 +1136,23 @@ static __global__ __launch_bounds__(64) void k_cf_seg_back(int nf_all, const int
 // pair = (record of the A operand, record of the B operand): (list entry of o1, Y record of o2) -- b row: (slot, list entry of o2).
 // `offsets` != 0 (k_cf_T_onesided_lds): the pair holds what that kernel would multiply out, the records' first elements -- entry x 54,
 // Y record x 54, slot x 6; the plan checked that they fit 32 bits (esl_cf_plan.hpp, os_offsets).  0: record numbers (k_cf_T_onesided).
+// Twins and the shorter side (`run` / `heads` != null; null = ESL_CF_OS_LIST=0, the list above).  Two kinds of work the sum does
+// not need are left out of the list:
+//   twins   a camera's bounding-box and 3-D edge to one ellipsoid are two entries at one slot (adjacent: the list is sorted by
+//           (slot, u)) and multiply the same Y record: V_a^T Y + V_b^T Y = (V_a + V_b)^T Y.  k_cf_v_merge adds the run's V records
+//           into Vm at the run's first entry, its head; the list holds the heads only (run[entry] != 0) and the B / A record is Vm's.
+//   sides   X(:, o1)^T X(:, o2) transposed is sum over the entries k of o2 of Y_slot(k)(o1)^T V_k: the same 9 x 6 . 6 x 9 product with
+//           the operands' arrays exchanged.  Per block and shared segment the list walks o2's heads when o2 has FEWER of them in the
+//           segment than o1 (heads[incidence], from the plan; ties and the diagonal keep o1's) and marks each such pair with the sign
+//           bit of its first number: (Y record of o1 at the entry's slot | sign, Vm record of the entry).
+// The order inside a block is fixed by the layout alone: shared segments ascending, the walked ellipsoid's heads in list order.
 template <bool FILL>
 static __global__ __launch_bounds__(256) void k_cf_os_list(int N, int nw, int n_chunks, int seg_chunks, const unsigned long long* __restrict__ mask,
                                                            const int* __restrict__ cmap, const int* __restrict__ seg_start,
                                                            const int* __restrict__ oe_cst, const int* __restrict__ oe_slot,
                                                            const int* __restrict__ unrank, const long long* __restrict__ bstart,
-                                                           int* __restrict__ bcnt, int2* __restrict__ pairs, int offsets) {
+                                                           int* __restrict__ bcnt, int2* __restrict__ pairs, int offsets,
+                                                           const int* __restrict__ run, const int* __restrict__ heads) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int t1 = blockIdx.x;
   const int o1 = (t1 == N || !unrank) ? t1 : unrank[t1];
@@ -1150,31 +1165,38 @@ static __global__ __launch_bounds__(256) void k_cf_os_list(int N, int nw, int n_
     if (t2 > t1 || t2 >= N) continue;
     const int o2 = unrank ? unrank[t2] : t2;
     const long b = rhs ? (long)N * (N + 1) / 2 + t2 : (long)t1 * (t1 + 1) / 2 + t2;
-    const int* cst = oe_cst + (size_t)(rhs ? o2 : o1) * (n_chunks + 1);   // the ellipsoid whose list entries are walked
     const long long w0 = FILL ? bstart[b] : 0;
     int cnt = 0;
     for (int wd = 0; wd < nw; ++wd) {
       unsigned long long mk = mask[(size_t)o1 * nw + wd] & mask[(size_t)o2 * nw + wd];
       if (!mk) continue;
-      // lane = bit: entry range and first Y record of all 64 segments of this word in one round trip
+      // lane = bit: the side, its entry range and the other side's first Y record of all 64 segments of this word in one round trip
       const int pl = wd * 64 + lane;
       const bool mine = (mk >> lane) & 1ull;
       const int che = seg_chunks * (pl + 1) < n_chunks ? seg_chunks * (pl + 1) : n_chunks;   // (a short last segment)
+      const int q2 = mine ? seg_start[pl] + (cmap[(size_t)pl * N1 + o2] & 0xFFFFFF) : 0;     // the incidences (rhs: o1 = N has none)
+      const int q1 = (mine && !rhs) ? seg_start[pl] + (cmap[(size_t)pl * N1 + o1] & 0xFFFFFF) : 0;
+      const bool swl = mine && !rhs && heads && heads[q2] < heads[q1];
+      const int* cst = oe_cst + (size_t)((rhs || swl) ? o2 : o1) * (n_chunks + 1);   // the ellipsoid whose list entries are walked
       const int kal = mine ? cst[seg_chunks * pl] : 0, kbl = mine ? cst[che] : 0;
-      const int yrl = (mine && !rhs) ? (seg_start[pl] + (cmap[(size_t)pl * N1 + o2] & 0xFFFFFF)) * (stride - 1) : 0;
+      const int yrl = (swl ? q1 : q2) * (stride - 1);
       while (mk) {
         const int bit = __builtin_ctzll(mk);
         mk &= mk - 1;
         const int p = wd * 64 + bit;
         const int ka = __builtin_amdgcn_readlane(kal, bit), kb = __builtin_amdgcn_readlane(kbl, bit), yr = __builtin_amdgcn_readlane(yrl, bit);
+        const int sw = __builtin_amdgcn_readlane((int)swl, bit) ? (int)0x80000000u : 0;
         for (int k0 = ka; k0 < kb; k0 += 64) {   // lane = entry: the prefix count keeps the list order
           const int ent = k0 + lane;
           const int pos = ent < kb ? oe_slot[ent] - p * stride : stride - 1;
-          const bool valid = pos != stride - 1;   // (the separator's entries are not the assembly's)
+          // (the separator's entries are not the assembly's; of a run of twins the head alone)
+          const bool valid = pos != stride - 1 && (!run || run[ent] != 0);
           const unsigned long long vb = __ballot(valid);
           if (FILL && valid) {
             const int at = cnt + __builtin_popcountll(vb & ((1ull << lane) - 1ull));
-            pairs[w0 + at] = rhs ? make_int2((p * stride + pos) * m6, ent * m54) : make_int2(ent * m54, (yr + pos) * m54);
+            pairs[w0 + at] = rhs  ? make_int2((p * stride + pos) * m6, ent * m54)
+                             : sw ? make_int2(((yr + pos) * m54) | sw, ent * m54)
+                                  : make_int2(ent * m54, (yr + pos) * m54);
           }
           cnt += __builtin_popcountll(vb);
         }
@@ -1182,6 +1204,25 @@ static __global__ __launch_bounds__(256) void k_cf_os_list(int N, int nw, int n_
     }
     if (!FILL && lane == 0) bcnt[b] = cnt;
   }
+}
+
+// Vm (twins above): thread = (list entry k, ellipsoid column b); at the head of a run of interior entries Vm_k = the sum of the run's V
+// records, added in list order.  Every other record of Vm is never written and never read.
+static __global__ __launch_bounds__(256) void k_cf_v_merge(int n_list, const int* __restrict__ run, const double* __restrict__ V, double* __restrict__ Vm) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long)n_list * 9) return;
+  const long k = t / 9;
+  const int n = run[k];
+  if (n == 0) return;
+  double s[6];
+#pragma unroll
+  for (int a = 0; a < 6; ++a) s[a] = V[t * 6 + a];
+  for (int j = 1; j < n; ++j) {
+#pragma unroll
+    for (int a = 0; a < 6; ++a) s[a] += V[(t + 9L * j) * 6 + a];
+  }
+#pragma unroll
+  for (int a = 0; a < 6; ++a) Vm[t * 6 + a] = s[a];
 }
 
 constexpr int kCfOsBatch = 12;   // K-steps (of four rows) in flight: eight pairs
@@ -1252,8 +1293,10 @@ static __global__ __launch_bounds__(256) void k_cf_T_onesided(int N, const int2*
           const int a = kidx - 6 * (hi ? e1 : e0);
           const bool ok = (hi ? e1 : e0) < m && kidx < 6 * m;
           const bool oka = ok && alane, okb = ok && blane;
-          const size_t ia = oka ? (size_t)(hi ? x1 : x0) * astep + aoff + a : 0, ib = okb ? (size_t)(hi ? y1 : y0) * 54 + r * 6 + a : 0;
-          const double va = Asrc[ia], vb = Bsrc[ib];
+          const int xs = hi ? x1 : x0;
+          const bool swp = xs < 0;   // (the swapped form: A from Y, B from V -- k_cf_os_list; never in the b row)
+          const size_t ia = oka ? (size_t)(xs & 0x7FFFFFFF) * astep + aoff + a : 0, ib = okb ? (size_t)(hi ? y1 : y0) * 54 + r * 6 + a : 0;
+          const double va = (swp ? Y : Asrc)[ia], vb = (swp ? V : Bsrc)[ib];
           av[j] = oka ? va : 0.0; bv[j] = okb ? vb : 0.0;
         }
 #pragma unroll
@@ -1360,8 +1403,10 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4
 #pragma unroll
     for (int e = 0; e < E; ++e)
       if (full || e < m) {
-        const unsigned x = (unsigned)__builtin_amdgcn_readlane(px, e0 + e), y = (unsigned)__builtin_amdgcn_readlane(py, e0 + e);
-        unsigned long long pa = (unsigned long long)(Asrc + x), pb = (unsigned long long)(Bsrc + y);
+        const int xs = __builtin_amdgcn_readlane(px, e0 + e);
+        const bool swp = xs < 0;   // (the swapped form: A from Y, B from V -- k_cf_os_list; never in the b row.  Scalar selects)
+        const unsigned x = (unsigned)xs & 0x7FFFFFFFu, y = (unsigned)__builtin_amdgcn_readlane(py, e0 + e);
+        unsigned long long pa = (unsigned long long)((swp ? Y : Asrc) + x), pb = (unsigned long long)((swp ? V : Bsrc) + y);
         unsigned oa = la8, ob = lb8;
 #if defined(__HIP_DEVICE_COMPILE__)
         // (no instructions: the record's base stays in scalar registers and the lane's offset 32 bits wide next to its load, so

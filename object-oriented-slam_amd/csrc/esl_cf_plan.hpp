@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 namespace esl {
@@ -33,6 +34,9 @@ constexpr int kCfSparseMinCams = 256;   // X is kept sparse from this many free 
 // it grows with the pairs: measured at the three strides (profiles/cf_stride_c4.md: 4.21 / 6.32 / 7.82 ms for 31.05 / 57.57 / 77.35 M)
 // k_cf_T_onesided_lds takes 1.8 ms for its walk over T's 2 M blocks, whatever their lists hold, and 0.078 ms per million
 // entry-products on top.  The marginal rate is the one a comparison of strides needs.
+// (The rule still prices the row side over every entry, cf_os_counts: the list that is built since -- twins merged, the shorter side,
+// cf_os_sides below -- is 0.65 - 0.75 of that at C4 and falls fastest at 48, so it only favours the wider stride;
+// profiles/cf_os_sides_c4.md has the kernel's times on it.)
 // A wider stride must win by kCfStrideMargin of the stride-16 figure: the rates move with the shapes (the update's C tile weighs more
 // against a shorter K loop), and below that the choice is within what the model can tell.  Ties go to the narrower stride.
 constexpr double kCfUpdFlopsPerMs = 0.83 * 79.0e9;
@@ -56,7 +60,7 @@ inline int cf_stride_choose(long n_o, const double* upd_flops, const double* pai
 }
 
 // The environment as the caller read it (cf_ensure_impl: ESL_CF_SPARSE, ESL_CF_TPERM and ESL_CF_NO_ND at every layout, ESL_CF_ND_MIN
-// once per process, ESL_CF_STRIDE and ESL_CF_OS_KERNEL when the context was created)
+// once per process, ESL_CF_STRIDE, ESL_CF_OS_KERNEL and ESL_CF_OS_LIST when the context was created)
 struct CfSwitches {
   int sparse = -1;         // ESL_CF_SPARSE: -1 unset, else the value's first character -- '0' dense X, '1' sparse (form by memory), '2' / '3' that form
   bool tperm_off = false;  // ESL_CF_TPERM=0: T keeps the ellipsoid order (A/B)
@@ -64,6 +68,7 @@ struct CfSwitches {
   int nd_min = 48;         // ESL_CF_ND_MIN: first free-camera count that is dissected (at least two chunks)
   int stride = 0;          // ESL_CF_STRIDE: 16, 32 or 48 forces form 3's segment length, 0 = by cf_stride_choose
   int os_kernel = 1;       // ESL_CF_OS_KERNEL: 0 = the per-lane gather (k_cf_T_onesided) whatever the offsets' size
+  int os_list = 1;         // ESL_CF_OS_LIST: 0 = the assembly's list walks the row side over every entry, twins apart (A/B: the bits of that list)
 };
 
 // The sparse form's tables for segments of S slots (the last slot of a segment is its separator): what cf_walk returns.
@@ -103,6 +108,19 @@ struct CfPlan : CfSegTables {
   size_t os_npairs = 0;
   bool os_offsets = false;
   double os_flops = 0;
+  // The list the assembly walks unless ESL_CF_OS_LIST=0 (esl_cf.hpp, "twins and the shorter side").  A RUN is an ellipsoid's list
+  // entries of one slot (a bounding-box and a 3-D edge of one camera: adjacent in os / ou); its first entry is the run's head and
+  // stands for the run with the sum of its V records.  os_run[k] = length of the run whose head is entry k, at interior slots; 0 for
+  // every other entry (not a head, or at a separator's slot).  os_heads[q] = run heads of incidence q (the order of p / o).
+  // Per block of T and shared segment the list walks the ellipsoid with FEWER heads (ties and the diagonal: the row's):
+  // osm_npairs = sum over the segments of sum_{i >= j} min(heads_i, heads_j) + the b row's heads; osm_flops as os_flops.
+  // osm_row_npairs: twins merged, row side throughout (the middle column of profiles/cf_os_sides_c4.md).
+  // os_list: the switch; os_list_npairs = the length of the list that is built, osm_npairs or os_npairs.
+  // The sign bit of a pair's first number marks the swapped form; os_offsets keeps every offset below 2^31, so the bit is free.
+  bool os_list = false;
+  std::vector<int> os_run, os_heads;
+  size_t osm_npairs = 0, osm_row_npairs = 0, os_list_npairs = 0;
+  double osm_flops = 0;
   // T's ellipsoids in the order of their first free camera (sparse form): column block rank[o] of T / R / Xs belongs to ellipsoid o;
   // kfirst[g] = first row of Xs that can be non-zero in columns [64 g, 64 g + 64) (the rank-K update skips the rest);
   // upd_flops = what the dense update executes with the staircase
@@ -219,6 +237,46 @@ inline CfOsCounts cf_os_counts(int S, int N, const std::vector<int>& start, cons
   return n;
 }
 
+// Twins and the shorter side (CfPlan::os_run ...): the runs of every ellipsoid's interior entries, the run heads of every incidence
+// -- an ellipsoid's incidences come in ascending segment order in p / o, as its entries do in os, so one cursor per ellipsoid finds
+// them -- and the lengths of the merged lists.  Per segment with head counts v sorted ascending, sum_{i >= j} min(v_i, v_j) =
+// sum_i v_(i) (n - i): the i-th smallest is the minimum against itself and the n - 1 - i larger ones.
+// Every incidence has at least one head: cf_walk makes an incidence where it meets an interior entry, so "o2 is live in the segment"
+// and "o2 has heads there" are the same set in osm_row_npairs.
+inline void cf_os_sides(CfPlan& pl, const std::vector<int>& start) {
+  const int S = pl.S;
+  const size_t n_inc = pl.p.size();
+  pl.os_run.assign(pl.os.size(), 0); pl.os_heads.assign(n_inc, 0);
+  std::vector<int> cur(start.begin(), start.end() - 1);
+  for (size_t q = 0; q < n_inc; ++q) {
+    const int o = pl.o[q], p = pl.p[q], end = start[(size_t)o + 1];
+    int k = cur[(size_t)o];
+    while (k < end && pl.os[(size_t)k] / S < p) ++k;   // (separator entries of segments without an interior one)
+    for (int head = -1; k < end && pl.os[(size_t)k] / S == p; ++k) {
+      const int sl = pl.os[(size_t)k];
+      if (sl % S == S - 1) continue;
+      if (head < 0 || pl.os[(size_t)head] != sl) { head = k; ++pl.os_heads[q]; }
+      ++pl.os_run[(size_t)head];
+    }
+    cur[(size_t)o] = k;
+  }
+  double both = 0, row = 0, brow = 0;
+  std::vector<int> v;
+  std::vector<std::pair<int, int>> byrank;
+  for (int p = 0; p < pl.nseg; ++p) {
+    const int q0 = pl.seg_start[(size_t)p], n = pl.seg_start[(size_t)p + 1] - q0;
+    v.assign(pl.os_heads.begin() + q0, pl.os_heads.begin() + q0 + n);
+    std::sort(v.begin(), v.end());
+    for (int i = 0; i < n; ++i) { both += (double)v[(size_t)i] * (double)(n - i); brow += v[(size_t)i]; }
+    byrank.clear();
+    for (int i = 0; i < n; ++i) { const int o = pl.o[(size_t)(q0 + i)]; byrank.push_back({pl.rank.empty() ? o : pl.rank[(size_t)o], pl.os_heads[(size_t)(q0 + i)]}); }
+    std::sort(byrank.begin(), byrank.end());
+    for (int i = 0; i < n; ++i) row += (double)byrank[(size_t)i].second * (double)(i + 1);
+  }
+  pl.osm_npairs = (size_t)(both + brow); pl.osm_row_npairs = (size_t)(row + brow);
+  pl.osm_flops = 2.0 * 6.0 * (81.0 * both + 9.0 * brow);
+}
+
 // The plan of one layout.  start = per-ellipsoid list starts (N + 1), cu_* = the per-camera lists of slam_alloc, EU = edge slots
 // (bounding-box + 3-D), comm = a communicator is present, total_mem = the device's TOTAL memory in bytes.
 // false: the (ellipsoid, camera chunk) range table of this graph exceeds 1 GB (nothing else can fail).
@@ -313,6 +371,9 @@ inline bool cf_plan_build(int N, int nf, size_t EU, const std::vector<int>& star
     // element offsets for k_cf_T_onesided_lds where every record's first element fits the list's 32 bits (C4: 1.4e8), else record
     // numbers and the per-lane gather
     pl.os_offsets = sw.os_kernel != 0 && 54 * std::max(EU, y_recs) <= (size_t)INT32_MAX;
+    cf_os_sides(pl, start);
+    pl.os_list = sw.os_list != 0;
+    pl.os_list_npairs = pl.os_list ? pl.osm_npairs : pl.os_npairs;
   }
   return true;
 }

@@ -299,6 +299,10 @@ struct esl_ctx {
   // pairs start and how many there are
   long long* cf_os_start = nullptr;
   int *cf_os_cnt = nullptr, *cf_os_pairs = nullptr;
+  // twins merged, shorter side (esl_cf.hpp k_cf_os_list; null with ESL_CF_OS_LIST=0): the plan's os_run and os_heads, and Vm -- at
+  // every run's head the sum of the run's V records (k_cf_v_merge, every trial; the arena's and the hazards' rules of cf_V)
+  int *cf_os_run = nullptr, *cf_os_heads = nullptr;
+  double* cf_Vm = nullptr;
   int *cf_rank = nullptr, *cf_unrank = nullptr, *cf_kfirst = nullptr;
   double* cf_xo_t = nullptr;   // x_o as the solver returns it (T's order)
   int lm_solver_used = 0;   // esl_linear_solver the last trial step ran with (1 reduced camera system, 2 reduced ellipsoid system, 3 camera chain)
@@ -347,6 +351,12 @@ struct esl_ctx {
   // ESL_CF_OS_KERNEL as read when the context was created (A/B and tests): 1 (default) the one-sided assembly feeds whole records
   // through LDS (k_cf_T_onesided_lds), 0 the per-lane gather (k_cf_T_onesided).  Same bits either way.
   int sw_cf_os_kernel = 1;
+  // ESL_CF_OS_LIST as read when the context was created (A/B and tests): 1 (default) the assembly's list holds one pair per run of
+  // twins and walks the shorter side per block and segment; 0 the row side over every entry, from cf_V (the bits of that list)
+  int sw_cf_os_list = 1;
+  // ESL_CF_FWD_PARTS as read when the context was created (A/B and tests): 8 (default), 4 or 2 parts per chunk of the slab sweep
+  // k_cf_forward<2> (esl_cf.hpp): less LDS per one-wave workgroup, more waves per CU.  Same bits at every value.
+  int sw_cf_fwd_parts = 8;
   // ESL_CF_STRIDE as read when the context was created: 16, 32 or 48 forces the segment length of the sparse form where T is
   // assembled one-sided (form 3); 0 (unset) = chosen at layout time from the graph's counts (esl_cf_plan.hpp, cf_stride_cost)
   int sw_cf_stride = 0;

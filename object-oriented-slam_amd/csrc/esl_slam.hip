@@ -304,7 +304,7 @@ static void cf_forget(esl_ctx* c) {
   c->cf_T = c->cf_Linv_ws = c->cf_part = nullptr;
   c->cf_Zt = c->cf_Hs = c->cf_Bs = c->cf_LfacS = c->cf_GS = c->cf_LiS = c->cf_MS = c->cf_NS = c->cf_R = nullptr;
   c->cf_Xc = c->cf_Xs = c->cf_P = c->cf_Prhs = c->cf_Xt = c->cf_Y = c->cf_Yr = nullptr;
-  c->cf_os_start = nullptr; c->cf_os_cnt = c->cf_os_pairs = nullptr;
+  c->cf_os_start = nullptr; c->cf_os_cnt = c->cf_os_pairs = c->cf_os_run = c->cf_os_heads = nullptr; c->cf_Vm = nullptr;
   c->cf_rank = c->cf_unrank = c->cf_kfirst = nullptr; c->cf_xo_t = nullptr;
   c->cf_plan = CfPlan{};
   c->cf_ready = false;
@@ -338,7 +338,7 @@ static int cf_ensure_impl(esl_ctx* c) {
   { const char* e = std::getenv("ESL_CF_TPERM"); sw.tperm_off = e && e[0] == '0'; }
   sw.no_nd = std::getenv("ESL_CF_NO_ND") != nullptr;
   static const int nd_min = [] { const char* e = std::getenv("ESL_CF_ND_MIN"); return e ? std::atoi(e) : 48; }();
-  sw.nd_min = nd_min; sw.stride = c->sw_cf_stride; sw.os_kernel = c->sw_cf_os_kernel;
+  sw.nd_min = nd_min; sw.stride = c->sw_cf_stride; sw.os_kernel = c->sw_cf_os_kernel; sw.os_list = c->sw_cf_os_list;
   size_t free_b = 0, total_b = 0;   // (the TOTAL decides between forms 1 and 2, never what happens to be free)
   if (nfi >= kCfSparseMinCams) ESL_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
   CfPlan& pl = c->cf_plan;
@@ -346,7 +346,7 @@ static int cf_ensure_impl(esl_ctx* c) {
     set_error("camera-first elimination: the (ellipsoid, camera chunk) range table of this graph exceeds 1 GB");
     return ESL_ERR_ALLOC;
   }
-  const bool sp = pl.sparse, os3 = sp && pl.form == 3;
+  const bool sp = pl.sparse, os3 = sp && pl.form == 3, osm = os3 && pl.os_list;   // (osm: twins merged, shorter side)
   const int nch = pl.n_chunks, nseg = pl.nseg, nw = pl.nw, N1 = N + 1;
   const size_t n_inc = pl.p.size();
   const size_t y_recs = std::max<size_t>(n_inc, 1) * (size_t)(pl.S - 1), nb = (size_t)N * (N + 1) / 2 + N;   // (Y's records; blocks of T's lower triangle + the b row)
@@ -364,6 +364,7 @@ static int cf_ensure_impl(esl_ctx* c) {
     i_inc = st.up(&d_inc, 4 * n_inc); ship(&c->cf_seg_start, pl.seg_start); ship(&c->cf_xld, pl.xld);
     ship(&c->cf_xoff, pl.xoff); ship(&c->cf_boff, pl.boff); ship(&c->cf_roff, pl.roff); ship(&d_fw_off, pl.fw_off); ship(&d_tw_off, pl.tw_off);
   }
+  if (osm) { ship(&c->cf_os_run, pl.os_run); ship(&c->cf_os_heads, pl.os_heads); }
   st.work(&c->cf_oe_cst, (size_t)std::max(N, 1) * (nch + 1));
   if (sp) {
     st.work(&c->cf_cmap, (size_t)nseg * N1); st.work(&c->cf_mask, (size_t)N1 * nw); st.work(&c->cf_seg_obj, n_inc); st.work(&c->cf_seg_first, n_inc);
@@ -385,7 +386,8 @@ static int cf_ensure_impl(esl_ctx* c) {
     if (pl.form == 1) { st.work(&c->cf_P, pl.p_blocks * 81); st.work(&c->cf_Prhs, pl.prhs_len); }
     if (pl.form == 3) {
       st.work(&c->cf_Y, y_recs * 54); st.work(&c->cf_Yr, std::max<size_t>(nf, 1) * 6);
-      st.work(&c->cf_os_start, nb + 1); st.work(&c->cf_os_cnt, nb); st.work(&c->cf_os_pairs, 2 * std::max<size_t>(pl.os_npairs, 1));
+      st.work(&c->cf_os_start, nb + 1); st.work(&c->cf_os_cnt, nb); st.work(&c->cf_os_pairs, 2 * std::max<size_t>(pl.os_list_npairs, 1));
+      if (osm) st.work(&c->cf_Vm, EU * 54);
     }
   } else {
     st.work(&c->cf_Xt, (size_t)pl.ldx * (size_t)pl.kpad);
@@ -418,20 +420,21 @@ static int cf_ensure_impl(esl_ctx* c) {
     const dim3 grid((unsigned)(N + 1), (unsigned)((N + kCfTPer - 1) / kCfTPer));
     ESL_HIP_TRY(hipMemsetAsync(c->cf_os_cnt, 0, nb * sizeof(int), c->stream));
     hipLaunchKernelGGL(k_cf_os_list<false>, grid, dim3(256), 0, c->stream, N, nw, nch, pl.S / kCfFwdCh, c->cf_mask, c->cf_cmap, c->cf_seg_start, c->cf_oe_cst, c->cf_oe_slot,
-                       (const int*)c->cf_unrank, (const long long*)nullptr, c->cf_os_cnt, (int2*)nullptr, 0);
+                       (const int*)c->cf_unrank, (const long long*)nullptr, c->cf_os_cnt, (int2*)nullptr, 0, (const int*)c->cf_os_run, (const int*)c->cf_os_heads);
     std::vector<int> h_cnt(nb);
     std::vector<long long> h_start(nb + 1);
     ESL_HIP_TRY(hipMemcpyAsync(h_cnt.data(), c->cf_os_cnt, nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     ESL_HIP_TRY(hipStreamSynchronize(c->stream));
     h_start[0] = 0;
     for (size_t b = 0; b < nb; ++b) h_start[b + 1] = h_start[b] + h_cnt[b];
-    if ((size_t)h_start[nb] != pl.os_npairs) {
+    if ((size_t)h_start[nb] != pl.os_list_npairs) {
       set_error("camera-first elimination: the one-sided assembly's pair list does not have the length the host counted");
       return ESL_ERR_STATE;
     }
     ESL_HIP_TRY(hipMemcpyAsync(c->cf_os_start, h_start.data(), (nb + 1) * sizeof(long long), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_cf_os_list<true>, grid, dim3(256), 0, c->stream, N, nw, nch, pl.S / kCfFwdCh, c->cf_mask, c->cf_cmap, c->cf_seg_start, c->cf_oe_cst, c->cf_oe_slot,
-                       (const int*)c->cf_unrank, (const long long*)c->cf_os_start, c->cf_os_cnt, (int2*)c->cf_os_pairs, pl.os_offsets ? 1 : 0);
+                       (const int*)c->cf_unrank, (const long long*)c->cf_os_start, c->cf_os_cnt, (int2*)c->cf_os_pairs, pl.os_offsets ? 1 : 0,
+                       (const int*)c->cf_os_run, (const int*)c->cf_os_heads);
     ESL_HIP_TRY(hipStreamSynchronize(c->stream));   // (h_start is read by the copy until here)
   }
   // ---- what must be zero ----
@@ -532,8 +535,13 @@ struct CfTrial {
     sep_chain(beside ? rt.cf_side : main);
     if (beside) ESL_HIP_TRY(hipEventRecord(rt.cf_ev_s, rt.cf_side));
     edge_scale(beside ? 1 : 0, main);
-    hipLaunchKernelGGL(k_cf_forward<2>, dim3((unsigned)pl.n_fwork), dim3(64), 0, main, nf, n_o, pl.n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V,
-                       c->cf_vy, c->cf_M, c->cf_Xc, ldx, st, st - 1, (const double*)c->cf_Zt, c->cf_R, st, segs());
+    auto forward = [&](auto parts) {   // (the parts of a chunk, ESL_CF_FWD_PARTS: LDS per workgroup, so the waves in flight; same bits)
+      hipLaunchKernelGGL((k_cf_forward<2, decltype(parts)::value>), dim3((unsigned)pl.n_fwork), dim3(64), 0, main, nf, n_o, pl.n_chunks, c->cf_oe_cst, c->cf_oe_slot,
+                         c->cf_V, c->cf_vy, c->cf_M, c->cf_Xc, ldx, st, st - 1, (const double*)c->cf_Zt, c->cf_R, st, segs());
+    };
+    if (c->sw_cf_fwd_parts == 8) forward(std::integral_constant<int, 8>{});
+    else if (c->sw_cf_fwd_parts == 4) forward(std::integral_constant<int, 4>{});
+    else forward(std::integral_constant<int, 2>{});
     return ESL_OK;
   }
   // the separators' right-hand sides from the slabs (sp; else from the dense X), the sums and their own V ...
@@ -682,7 +690,10 @@ struct CfTrial {
   // k_cf_forward<2>, so with the side stream (`beside`: ESL_CF_OVERLAP != 0) the WHOLE separator path -- chain, V and vy of the
   // separator slots, k_cf_sep_rhs, k_cf_forward<1> -- runs there beside k_cf_seg_back and the assembly, and the update (uncapped, in
   // its accumulate form, with nothing beside it) waits for the assembly and Xs only.  One arithmetic order for T at either setting:
-  // T = D - sum (assign), then T -= Xs^T Xs.  Hazards across trials: as in build_stored_side, with cf_ev_p = Xs is complete. ----
+  // T = D - sum (assign), then T -= Xs^T Xs.  Hazards across trials: as in build_stored_side, with cf_ev_p = Xs is complete.
+  // k_cf_v_merge reads cf_V on the main stream while edge_scale(2) may still write cf_V on the side stream: disjoint records -- a run
+  // is an ellipsoid's entries of one INTERIOR slot (os_run is 0 elsewhere), class 2 writes the entries of separator slots only; the
+  // interior ones were written by edge_scale(1) in front of it on the main stream.  cf_Vm is written and read on the main stream. ----
   int build_onesided(bool beside) {
     const hipStream_t sst = beside ? rt.cf_side : main;   // the separators' stream
     if (int rc = slabs(beside)) return rc;
@@ -703,10 +714,13 @@ struct CfTrial {
       if (st == 3 * kCfFwdCh) seg_back(std::integral_constant<int, 3>{});
       else if (st == 2 * kCfFwdCh) seg_back(std::integral_constant<int, 2>{});
       else seg_back(std::integral_constant<int, 1>{});
+      // twins merged (esl_cf.hpp k_cf_os_list): the runs' sums of V, which the list's pairs name; ESL_CF_OS_LIST=0: V itself
+      if (pl.os_list && pl.n_list > 0)
+        hipLaunchKernelGGL(k_cf_v_merge, dim3((unsigned)(((long)pl.n_list * 9 + 255) / 256)), dim3(256), 0, main, pl.n_list, (const int*)c->cf_os_run, c->cf_V, c->cf_Vm);
       const dim3 grid((unsigned)(N + 1), (unsigned)((N + kCfTPer - 1) / kCfTPer));
       // whole records through LDS, or the per-lane gather: same bits
       hipLaunchKernelGGL(pl.os_offsets ? k_cf_T_onesided_lds : k_cf_T_onesided, grid, dim3(256), 0, main, N, (const int2*)c->cf_os_pairs,
-                         (const long long*)c->cf_os_start, (const int*)c->cf_os_cnt, c->cf_V, c->cf_Y, c->cf_Yr, c->Hoo, c->bo, lambda, c->cf_T, ldt, 0, N,
+                         (const long long*)c->cf_os_start, (const int*)c->cf_os_cnt, pl.os_list ? c->cf_Vm : c->cf_V, c->cf_Y, c->cf_Yr, c->Hoo, c->bo, lambda, c->cf_T, ldt, 0, N,
                          (const int*)c->cf_unrank, 0);
     }
     ESL_HIP_TRY(hipGetLastError());
@@ -1353,6 +1367,16 @@ extern "C" int esl_lm_solver_stats(esl_ctx* c, double* st) {
   st[7] = (double)(pl.sparse ? pl.kpad_s : pl.kpad);
   st[8] = pl.tperm ? pl.upd_flops : 0.0;   // (0: the whole lower triangle times K)
   st[9] = pl.tperm ? 1.0 : 0.0;
+  return ESL_OK;
+}
+extern "C" int esl_lm_os_counts(esl_ctx* c, double* n) {
+  if (!c || !n) return ESL_ERR_INVALID;
+  for (int k = 0; k < ESL_OS_COUNTS; ++k) n[k] = 0;
+  if (c->lm_solver_used != ESL_SOLVER_REDUCED_ELLIPSOID || !c->cf_ready) return ESL_OK;
+  const esl::CfPlan& pl = c->cf_plan;
+  if (!pl.sparse || pl.form != 3) return ESL_OK;
+  n[0] = (double)pl.os_npairs; n[1] = (double)pl.osm_row_npairs; n[2] = (double)pl.osm_npairs;
+  n[3] = (double)pl.os_list_npairs; n[4] = pl.os_list ? pl.osm_flops : pl.os_flops; n[5] = 8.0 * (double)pl.os_list_npairs;
   return ESL_OK;
 }
 extern "C" int esl_lm_pcg_stats(esl_ctx* c, double* st) {

@@ -22,7 +22,7 @@ EXPORTS = [
     "esl_abi_version", "esl_last_error", "esl_device_count", "esl_ctx_create", "esl_ctx_destroy",
     "esl_ctx_synchronize", "esl_ctx_trim", "esl_lm_params_default", "esl_optimize", "esl_optimize_fixed", "esl_graph_upload", "esl_graph_upload_fixed", "esl_graph_obj_fixed", "esl_graph_append", "esl_graph_sizes", "esl_states_upload",
     "esl_states_download", "esl_optimize_resident", "esl_states_snapshot", "esl_states_restore", "esl_profile_enable", "esl_profile_get", "esl_lm_begin", "esl_lm_linearize", "esl_lm_reduced_system", "esl_lm_reduced_residual",
-    "esl_lm_try_step", "esl_lm_commit", "esl_lm_solver_used", "esl_lm_solver_stats", "esl_lm_download", "esl_lm_set_robust", "esl_edge_chi2", "esl_pcg_params_default", "esl_lm_set_pcg", "esl_lm_pcg_stats", "esl_comm_unique_id", "esl_comm_init", "esl_comm_init_host", "esl_comm_set_replicated", "esl_comm_destroy", "esl_partition_objects", "esl_fit_params_default", "esl_fit_frame", "esl_fit_frame_debug", "esl_fit_frame_ex", "esl_selftest_cholesky", "esl_debug_chol_plan", "esl_debug_update_v_applies", "esl_debug_cf_stride_choose",
+    "esl_lm_try_step", "esl_lm_commit", "esl_lm_solver_used", "esl_lm_solver_stats", "esl_lm_os_counts", "esl_lm_download", "esl_lm_set_robust", "esl_edge_chi2", "esl_pcg_params_default", "esl_lm_set_pcg", "esl_lm_pcg_stats", "esl_comm_unique_id", "esl_comm_init", "esl_comm_init_host", "esl_comm_set_replicated", "esl_comm_destroy", "esl_partition_objects", "esl_fit_params_default", "esl_fit_frame", "esl_fit_frame_debug", "esl_fit_frame_ex", "esl_selftest_cholesky", "esl_debug_chol_plan", "esl_debug_update_v_applies", "esl_debug_cf_stride_choose",
     "esl_init_quadric", "esl_init_from_qstar", "esl_init_plane_error", "esl_init_quadrics", "esl_plane_params_default", "esl_extract_ground_plane", "esl_extract_planes",
     "esl_reloc_params_default", "esl_reloc_set_map", "esl_relocalize",
     "esl_assoc_params_default", "esl_predict_boxes", "esl_associate_boxes",
@@ -246,6 +246,13 @@ class Context:
         names = ["x_form", "stride", "separators", "segments", "product_flops", "product_bytes", "slab_bytes", "dense_update_rows",
                  "dense_update_flops_executed", "t_ordered_by_first_camera"]
         return {n: float(st[i]) for i, n in enumerate(names)}
+
+    def lm_os_counts(self):
+        """The one-sided assembly's pair list as the last trial ran it (esl_lm_os_counts)."""
+        n = (C.c_double * abi.ESL_OS_COUNTS)()
+        _check(load().esl_lm_os_counts(self._h, n), "esl_lm_os_counts")
+        names = ["row_side_pairs", "merged_pairs", "merged_shorter_side_pairs", "list_pairs", "list_flops", "list_bytes"]
+        return {k: float(n[i]) for i, k in enumerate(names)}
 
     def lm_reduced_system(self, lam):
         ptr, n, lda = C.c_void_p(), C.c_int64(0), C.c_int64(0)

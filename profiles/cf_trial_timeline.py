@@ -41,10 +41,10 @@ def overlap(a, c):
 
 
 if onesided:
-    pairs = ((("k_cf_chain", 64), ("k_cf_forward<2>", None)), (("k_cf_forward<1>", None), ("k_cf_T_onesided", None)),
+    pairs = ((("k_cf_chain", 64), ("k_cf_forward<2", None)), (("k_cf_forward<1", None), ("k_cf_T_onesided", None)),
              (("k_cf_sep_rhs", None), ("k_cf_seg_back", None)), (("k_chol_update_v", None), ("k_cf_T_onesided", None)))
 else:
-    pairs = ((("k_cf_chain", 64), ("k_cf_forward<2>", None)), (("k_cf_forward<1>", None), ("k_cf_seg_syrk", None)),
+    pairs = ((("k_cf_chain", 64), ("k_cf_forward<2", None)), (("k_cf_forward<1", None), ("k_cf_seg_syrk", None)),
              (("k_chol_update_v", None), ("k_cf_seg_syrk", None)), (("k_chol_update_v", None), ("k_cf_T_gather", None)))
 for (pa, ga), (pc, gc) in pairs:
     for a in find(pa, ga):

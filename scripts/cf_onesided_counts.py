@@ -7,7 +7,9 @@ camera (slot = camera - 1: camera 0 is the fixed one).
 The full report is for dissection stride 16; behind it one line per stride given (default 16 24 32 48): what the assembly
 multiplies and reads with segments that long (the library runs 16, 32 or 48: esl_cf_plan.hpp, cf_stride_choose, which weighs these
 entry-products against the separators' update and the slabs).  block_pairs() is the per-block count of the
-assembly's pair list (tests/test_cf_onesided_pairs.py).
+assembly's pair list with the row side walked over every entry (tests/test_cf_onesided_pairs.py; ESL_CF_OS_LIST=0), block_sides() that
+of the list the library builds: a camera's bounding-box and 3-D edge to one ellipsoid merged into one pair, and per block and shared
+segment the side with fewer pairs (tests/test_cf_os_sides.py).  Behind the strides' lines, the three totals at 16, 32 and 48.
 """
 import importlib
 import os
@@ -55,6 +57,53 @@ def block_pairs(g, stride=16):
     return pairs[np.tril_indices(g.n_objs)], ent.sum(0)
 
 
+def run_heads(g, stride=16):
+    """[segment, position in T's order]: the ellipsoid's RUN HEADS in the segment = its distinct interior slots (the entries of one
+    slot, a bounding-box and a 3-D edge of one camera, are one run); and the same count over every entry."""
+    slot, obj = entries(g)
+    first = np.full(g.n_objs, g.n_cams, np.int64)
+    np.minimum.at(first, obj, slot)
+    unrank = np.argsort(first, kind="stable")
+    interior = slot % stride != stride - 1
+    nseg = int((g.n_cams - 1 + stride - 1) // stride)
+    ent = np.zeros((nseg, g.n_objs), np.int64)
+    np.add.at(ent, ((slot // stride)[interior], obj[interior]), 1)
+    heads = np.zeros((nseg, g.n_objs), np.int64)
+    so = np.unique(slot[interior] * g.n_objs + obj[interior])
+    np.add.at(heads, (so // g.n_objs // stride, so % g.n_objs), 1)
+    return heads[:, unrank], ent[:, unrank]
+
+
+def block_sides(g, stride=16):
+    """The list with twins merged and the shorter side walked.  Per block of T's lower triangle (the order of block_pairs): its pairs
+    = sum over the shared segments of min(heads of o1, heads of o2); its pairs with the row side kept (heads of o1); the shared segments
+    where the column side is walked (o2 has fewer heads), and those where the two have equally many (ties keep the row side; the
+    diagonal is all ties).  Last, the b row: o2's heads."""
+    heads, _ = run_heads(g, stride)
+    N = g.n_objs
+    both, row, swapped, ties = (np.zeros((N, N), np.int64) for _ in range(4))
+    for h in heads:
+        live = np.flatnonzero(h)
+        h1, h2 = h[live][:, None], h[live][None, :]
+        at = np.ix_(live, live)
+        both[at] += np.minimum(h1, h2); row[at] += np.broadcast_to(h1, (live.size, live.size))
+        swapped[at] += h2 < h1; ties[at] += h2 == h1
+    tril = np.tril_indices(N)
+    return both[tril], row[tril], swapped[tril], ties[tril], heads.sum(0)
+
+
+def side_totals(g, stride):
+    """pairs of the whole list, the b row included: the row side over every entry, twins merged, merged and the shorter side"""
+    heads, ent = run_heads(g, stride)
+    today = merged = both = 0
+    for h, e in zip(heads, ent):
+        live = np.flatnonzero(h)
+        place = np.arange(1, live.size + 1)                      # the ellipsoid at place q of T's order meets q + 1 partners
+        today += int((e[live] * place).sum()); merged += int((h[live] * place).sum())
+        both += int((np.sort(h[live]) * place[::-1]).sum())      # the i-th smallest is the minimum against itself and the larger ones
+    return today + int(ent.sum()), merged + int(heads.sum()), both + int(heads.sum())
+
+
 def main():
     pkg_synth = importlib.import_module("object-oriented-slam_amd.synth")
     args = sys.argv[1:]
@@ -86,6 +135,10 @@ def main():
     for st in strides:
         ps, ep, yr, yb = stride_counts(g, st)
         print(f"  | {st} | {ps:.4g} | {ep:.4g} | {yr / 1e9:.1f} | {yb / 1e9:.2f} |")
+    print("  pairs of the assembly's list, b row included:\n  | stride | today (row side) | twins merged | merged + shorter side |\n  |---|---|---|---|")
+    for st in (16, 32, 48):
+        today, merged, both = side_totals(g, st)
+        print(f"  | {st} | {today / 1e6:.1f} M | {merged / 1e6:.1f} M | {both / 1e6:.1f} M |")
 
 
 if __name__ == "__main__":
