@@ -53,7 +53,8 @@ extern "C" {
                              *    (esl_predict_boxes, esl_associate_boxes), and the SVD initialisation of many ellipsoids in one call
                              *    (esl_init_quadrics) and its outlier-rejecting form (esl_init_quadrics_robust), and map maintenance
                              *    (esl_map_overlaps, esl_map_merge), and the per-pixel rendering of a map (esl_render_map), and the voxel-fused
-                             *    dense map of many RGB-D frames (esl_dense_begin / _add_frames / _info_get / _extract / _end) */
+                             *    dense map of many RGB-D frames (esl_dense_begin / _add_frames / _info_get / _extract / _end) with its
+                             *    per-instance ellipsoids (esl_dense_objects) */
 #define ESL_MAX_TRACE 32
 
 typedef enum {
@@ -934,6 +935,70 @@ int esl_dense_end(esl_ctx* ctx);   /* forget the map; the buffers stay (grow-onl
  * bracketed as kernel class 4.  esl_debug_dense_allocs: the device allocations these calls have made on this context and the bytes
  * their buffers hold (the owner has no value in esl_scratch_owner). */
 int esl_debug_dense_allocs(esl_ctx* ctx, int64_t* allocs_out, int64_t* bytes_out);
+
+/* ---- per-instance ellipsoids from the dense map (additive part of ABI 5: detect by the symbol) ------------------------------------------
+ * The reference estimates an object's ellipsoid from the depth points of ONE view (EllipsoidExtractor.cpp; esl_fit_frame).  The dense
+ * map holds the same object seen from every frame, deduplicated, exactly summed and labelled by vote.  esl_dense_objects answers, per
+ * instance label of that map: which voxels hang together, and which gravity-aligned ellipsoid bounds the largest connected set.  It
+ * is the map-side twin of esl_fit_frame: voxel centres instead of points, connected components instead of Euclidean clustering, the
+ * same gravity-aligned PCA and extent rule.  Integers and total orders decide everything discrete; runs are bit-reproducible and do
+ * not depend on the order the frames were added in.
+ *  1. Kept voxel.  A voxel of the map (dense-map steps 3 to 5) has its integer key k, count, label and votes.  Three tests run in
+ *     this order and a voxel is counted at the first one it fails: label in [0, N) (passing: n_in_range); votes >= min_votes and
+ *     count >= min_count (passing: n_gated); height h >= plane_dist (passing: n_kept).  Centre x_a = ((double)k_a + 0.5) leaf.  The
+ *     plane is normalised once on the host: n^ = n / |n|, d^ = d / |n|, |n| = sqrt(n0^2 + n1^2 + n2^2) summed left to right;
+ *     h = (n^0 x0 + n^1 x1) + n^2 x2 + d^.  No product is contracted with a sum.
+ *  2. Components.  Two kept voxels of equal label are linked iff max_a |k_a - k'_a| <= reach; components are the connected components
+ *     of the links.  A component's key is the smallest packed key of its members, its size the number of members, its samples the
+ *     integer sum of the members' counts.  n_components_all counts every component.
+ *  3. Table: the components of size >= min_component, sorted by label ascending, then size descending, then key ascending;
+ *     n_components rows.  More rows than max_components give out->status = 3 -- a result, the return is ESL_OK --: objs_out and
+ *     stats_out are zero, the first min(comp_cap, n_components) rows of comp_out are zero, voxel_comp_out is -1, n_ok is 0; the
+ *     counts of the result stand.  comp_out row: label, size, samples, kx, ky, kz of the key; the first comp_cap rows are written.
+ *  4. Object o: its chosen component is the first table row of label o.  Status 1: no kept voxel of label o; 2: kept voxels but no
+ *     table row; 6: the guard of step 5; 0 otherwise.  A non-zero status zeroes the object's ten numbers.
+ *  5. Moments of the chosen component, all int64: kmin_a, kmax_a over the members; d = k - kmin, n = size, s_a = sum d_a,
+ *     M_ab = sum d_a d_b.  Guard: with span = max_a (kmax_a - kmin_a + 1) the object takes status 6 when n span^2 >= 2^62 (tested in
+ *     integers without overflowing): below it no sum can leave int64.  A connected component needs some 8e5 voxels in a line to reach it.
+ *  6. Frame.  The gravity basis (u, v, n^) by the rule of esl_relocalize step 1: e_k = the axis with the smallest |n^_k| (lowest k on
+ *     ties), u = normalise(e_k x n^), v = n^ x u.  m_a = s_a / n, C_ab = M_ab / n - m_a m_b (voxel units), C_uu = u^T C u, C_uv =
+ *     u^T C v, C_vv = v^T C v, each a^T C b = (a0 r0 + a1 r1) + a2 r2 with r_i = (C_i0 b0 + C_i1 b1) + C_i2 b2.  theta = 0.5 atan2(2 C_uv,
+ *     C_uu - C_vv), x = cos theta u + sin theta v, y = n^ x x, R = [x y n^] (columns).
+ *  7. Extents over the members: the projections (x0 p0 + x1 p1) + x2 p2 of every member's centre p, the same with y and with n^;
+ *     minimum and maximum of each.  Centre coordinate = (min + max) / 2, half-axis = (max - min) / 2 + leaf / 2: the box of the
+ *     members' voxel centres grown by half a voxel, the reference's extent rule (esl_fit_frame's last step).
+ *  8. Output row: t_a = (x_a c_x + y_a c_y) + n^_a c_z; q = the library's rotation-to-quaternion of R, negated when qw < 0; a, b, c =
+ *     the half-axes along x, y, n^.  stats_out[6 o ..] = status, kept voxels of the label, table rows of the label, the chosen row
+ *     or -1, size and samples of the chosen component.  out->n_ok counts the objects of status 0.
+ *  9. voxel_comp_out[i] for the i-th voxel in ascending packed-key order (esl_dense_extract's order), the first voxel_cap written:
+ *     the table row of the voxel's component; -2 kept, but in a component below min_component; -1 not kept.
+ * Voxel CENTRES are used, not the voxels' centroids, and the reach is a Chebyshev distance on keys, not a Euclidean radius. */
+typedef struct {
+  int32_t reach;           /* 2: voxels link when max_a |k_a - k'_a| <= reach (integer keys); 1..3.  2 = the reference's 2 cm cluster tolerance at the 1 cm leaf */
+  int32_t min_votes;       /* 1: a voxel takes part only with votes >= this */
+  int32_t min_count;       /* 1: ... and count (samples) >= this */
+  int32_t min_component;   /* 100: components with fewer voxels are not objects (MinClusterSize, TUM3.yaml:9) */
+  int32_t max_components;  /* 65536: more table rows than this give status 3; 1 .. 2^20 */
+  int32_t pad;
+  double  plane_dist;      /* 0.05 m: voxels whose centre is lower than this above the ground are dropped (EllipsoidExtractor.cpp:570); finite */
+} esl_dense_obj_params;    /* 32 bytes; design choices except where a reference line is named */
+void esl_dense_obj_params_default(esl_dense_obj_params* p);
+
+typedef struct { int32_t status, n_voxels, n_in_range, n_gated, n_kept, n_components_all, n_components, n_ok; } esl_dense_obj_result; /* 32 bytes */
+
+/* ESL_ERR_INVALID: null ctx, ground_world or out; N < 0 or a negative cap; objs_out NULL with N > 0; a cap > 0 with its array NULL; a
+ * non-finite plane number or |n| < 1e-12; reach outside 1..3; min_votes, min_count or min_component < 1; max_components outside
+ * 1..2^20; plane_dist not finite.  ESL_ERR_STATE: no esl_dense_begin before; a map begun without labels.  A map over its capacity
+ * (sticky status 3) is not an error: ESL_OK, out->status = 3, n_voxels = -1, nothing else is written.  N = 0 and an empty map are valid.
+ * The call changes nothing in the map except the best words, which it rebuilds as esl_dense_extract does: adds, extracts and object
+ * calls may alternate.  Its buffers are the dense map's own (grow-only; a warm call of a shape no larger than an earlier one allocates
+ * nothing: esl_debug_dense_allocs); one GPU, no collective, launches bracketed as kernel class 4. */
+int esl_dense_objects(esl_ctx* ctx, int32_t N /* labels 0 .. N-1 are objects */, const double ground_world[4],
+                      const esl_dense_obj_params* p /* NULL = defaults */,
+                      double* objs_out /* N x 10 world ellipsoids */, int32_t* stats_out /* N x 6 or NULL */,
+                      int64_t comp_cap, int32_t* comp_out /* comp_cap x 6 or NULL */,
+                      int64_t voxel_cap, int32_t* voxel_comp_out /* voxel_cap or NULL, in esl_dense_extract's order */,
+                      esl_dense_obj_result* out);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------*/
 /* Dense FP64-MFMA Cholesky factor + solve (the reduced-camera solver of SLAM mode) on a procedurally generated,

@@ -272,6 +272,32 @@ def default_dense_params(**kw):
     return p
 
 
+class EslDenseObjParams(C.Structure):
+    """esl_dense_obj_params: the gates, the reach and the table limits of esl_dense_objects."""
+    _fields_ = [("reach", C.c_int32), ("min_votes", C.c_int32), ("min_count", C.c_int32), ("min_component", C.c_int32),
+                ("max_components", C.c_int32), ("pad", C.c_int32), ("plane_dist", C.c_double)]
+
+
+class EslDenseObjResult(C.Structure):
+    """esl_dense_obj_result: the totals of one esl_dense_objects call; status 3 = more table rows than max_components, or a map over
+    its capacity (n_voxels = -1)."""
+    _fields_ = [("status", C.c_int32), ("n_voxels", C.c_int32), ("n_in_range", C.c_int32), ("n_gated", C.c_int32), ("n_kept", C.c_int32),
+                ("n_components_all", C.c_int32), ("n_components", C.c_int32), ("n_ok", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def default_dense_obj_params(**kw):
+    """esl_dense_obj_params_default (include/esl.h)"""
+    p = EslDenseObjParams(reach=2, min_votes=1, min_count=1, min_component=100, max_components=65536, pad=0, plane_dist=0.05)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
 def dense_argtypes(L):
     """the esl_dense_* calls take nullable pointers: declared, so that None passes as NULL and a wrong type raises"""
     dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
@@ -284,8 +310,12 @@ def dense_argtypes(L):
     L.esl_dense_extract.argtypes = [C.c_void_p, C.c_int64, ip, dp, ip, C.POINTER(C.c_uint8), ip, ip, lp]
     L.esl_dense_end.argtypes = [C.c_void_p]
     L.esl_debug_dense_allocs.argtypes = [C.c_void_p, lp, lp]
+    L.esl_dense_obj_params_default.argtypes = [C.POINTER(EslDenseObjParams)]
+    L.esl_dense_obj_params_default.restype = None
+    L.esl_dense_objects.argtypes = [C.c_void_p, C.c_int32, dp, C.POINTER(EslDenseObjParams), dp, ip, C.c_int64, ip, C.c_int64, ip,
+                                    C.POINTER(EslDenseObjResult)]
     for f in (L.esl_dense_begin, L.esl_dense_add_frames, L.esl_dense_info_get, L.esl_dense_extract, L.esl_dense_end,
-              L.esl_debug_dense_allocs):
+              L.esl_debug_dense_allocs, L.esl_dense_objects):
         f.restype = C.c_int
 
 

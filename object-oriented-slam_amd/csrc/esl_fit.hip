@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "esl_ctx.hpp"
+#include "esl_uf.hpp"
 
 namespace esl {
 
@@ -166,39 +167,8 @@ __device__ __forceinline__ unsigned long long cell_key(float x, float y, float z
                   cz = (long long)floor((double)z / tol) + dz;
   return ((unsigned long long)(cz + kKeyOff) << 42) | ((unsigned long long)(cy + kKeyOff) << 21) | (unsigned long long)(cx + kKeyOff);
 }
-// find with path halving: a node is re-pointed at its grandparent.  Linking by index (larger root under smaller) alone
-// grows chains hundreds of hops long inside a 4.5k-point cluster, and every hop is an L2 round trip.  The re-pointing is
-// a plain (relaxed atomic) STORE: only roots are ever targets of the linking CAS and a non-root never becomes a root
-// again, so the only concurrent writers of parent[i] are other halvings, all of them writing ancestors of i -- and a
-// same-address read-modify-write costs ~10 ns of serialisation on this part where a store does not.
-__device__ __forceinline__ int uf_find(int* parent, int i) {
-  for (;;) {
-    const int p = __hip_atomic_load(&parent[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (p == i) return i;
-    const int gp = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (gp == p) return p;
-    __hip_atomic_store(&parent[i], gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    i = gp;
-  }
-}
-
-// The same walk on CACHED loads (workgroup-scope relaxed atomics = plain loads the compiler may not fold): an agent-scope load
-// goes past this XCD's L2 to the fabric for every hop (~1 - 2 us, and a find is a chain of them); a cached copy of the forest may be
-// stale, but a stale parent is an OLDER ancestor of the same node (roots only ever gain parents, halving only re-points at
-// ancestors), so the walk still ends at an ancestor: "same ancestor" proves the two points are joined, and a stale "root" is
-// caught by the linking CAS, whose return value is the truth (cl_union continues from it).  Only the union stage may use this --
-// the statistics stage of the next kernel needs the real roots.
-__device__ __forceinline__ int uf_find_cached(int* parent, int i) {
-  for (;;) {
-    const int p = __hip_atomic_load(&parent[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (p == i) return i;
-    const int gp = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (gp == p) return p;
-    __hip_atomic_store(&parent[i], gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    i = gp;
-  }
-}
-
+// uf_find (agent-scope loads, path halving by plain stores) and uf_find_cached (the same walk on cached loads, for the union stage
+// only): esl_uf.hpp, shared with the dense map's component labelling.
 __device__ __forceinline__ int uf_find_lds(int* parent, int i) {   // same, forest in LDS
   for (;;) {
     const int p = __hip_atomic_load(&parent[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);

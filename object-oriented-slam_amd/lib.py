@@ -30,7 +30,7 @@ EXPORTS = [
     "esl_merge_params_default", "esl_map_overlaps", "esl_map_merge",
     "esl_render_params_default", "esl_render_map", "esl_debug_render_allocs", "esl_debug_scratch_allocs",
     "esl_dense_params_default", "esl_dense_begin", "esl_dense_add_frames", "esl_dense_info_get", "esl_dense_extract", "esl_dense_end",
-    "esl_debug_dense_allocs",
+    "esl_debug_dense_allocs", "esl_dense_obj_params_default", "esl_dense_objects",
 ]
 
 
@@ -815,6 +815,32 @@ class Context:
         res = {k: v[:m] for k, v in out.items()}
         res["n_voxels"] = int(n.value)
         return res
+
+    def dense_objects(self, N, ground_world, params=None, comp_cap=None, voxel_cap=None):
+        """esl_dense_objects: per label 0 .. N-1 of the dense map, the gravity-aligned ellipsoid that bounds the label's largest connected
+        set of kept voxels.  comp_cap / voxel_cap None = room for the whole table / every voxel.  Returns a dict: result (the totals),
+        objs (N, 10), stats (N, 6) int32, comp (min(comp_cap, n_components), 6) int32, voxel_comp (min(voxel_cap, n_voxels),) int32; on
+        a map over its capacity (result n_voxels = -1) the arrays are empty."""
+        N = int(N)
+        g = np.ascontiguousarray(ground_world, dtype=np.float64).reshape(4)
+        p = params if params is not None else abi.default_dense_obj_params()
+        nv = max(self.dense_info()["n_voxels"], 0)
+        comp_cap = nv if comp_cap is None else int(comp_cap)          # a table never has more rows than the map has voxels
+        voxel_cap = nv if voxel_cap is None else int(voxel_cap)
+        objs = np.zeros((max(N, 0), 10)); stats = np.zeros((max(N, 0), 6), np.int32)
+        comp = np.zeros((max(comp_cap, 0), 6), np.int32); vox = np.zeros(max(voxel_cap, 0), np.int32)
+        ip = C.POINTER(C.c_int32)
+        res = abi.EslDenseObjResult()
+        t0 = time.perf_counter()
+        rc = load().esl_dense_objects(self._h, N, g.ctypes.data_as(_dp), C.byref(p), objs.ctypes.data_as(_dp) if objs.size else None,
+                                      stats.ctypes.data_as(ip) if stats.size else None, comp_cap, comp.ctypes.data_as(ip) if comp.size else None,
+                                      voxel_cap, vox.ctypes.data_as(ip) if vox.size else None, C.byref(res))
+        self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
+        _check(rc, "esl_dense_objects")
+        r = res.as_dict()
+        if r["n_voxels"] < 0:
+            return dict(result=r, objs=objs[:0], stats=stats[:0], comp=comp[:0], voxel_comp=vox[:0])
+        return dict(result=r, objs=objs, stats=stats, comp=comp[:min(comp_cap, r["n_components"])], voxel_comp=vox[:min(voxel_cap, r["n_voxels"])])
 
     def dense_end(self):
         """esl_dense_end: forget the map (the buffers stay with the context)"""

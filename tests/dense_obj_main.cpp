@@ -1,0 +1,120 @@
+// A stand-alone program over csrc/esl_dense_obj.hpp (the host side of the header esl_dense.hip compiles for esl_dense_objects).
+//   no argument: self-checks on hand-computed cases -- the plane and its gravity basis, a voxel's centre and height, the guard of the
+//                moments at its boundary (no GPU test can reach status 6), the order-preserving encoding, the quaternion branches, the
+//                frame and the output row of a solid 12 x 8 x 6 block; exit status 0 when all hold.
+//   "guard":     reads lines  n span  from stdin and prints the predicate (0 / 1) per line.
+//   "frames":    reads  ground(4) leaf count  then per line  n mom(9) min(3) max(3) ; prints the nine axis numbers and the ten numbers
+//                of the output row with 17 significant digits: the CPU test compares them with the numpy statement.
+// Built and run by tests/test_dense_objects_ref.py, also under -fsanitize=address,undefined.  Compile with -ffp-contract=off.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "../object-oriented-slam_amd/csrc/esl_dense_obj.hpp"
+
+using namespace esl;
+
+static int fails = 0;
+#define CHECK(c) do { if (!(c)) { std::printf("FAILED line %d: %s\n", __LINE__, #c); ++fails; } } while (0)
+
+static bool near(double a, double b, double tol = 1e-15) { return std::fabs(a - b) <= tol; }
+
+static void self_checks() {
+  DobjPlane P;
+  {   // the floor z = 0.5 given with a normal of length 2: u = e_0 x n^ = (0, -1, 0), v = n^ x u = (1, 0, 0)
+    const double g[4] = {0, 0, 2, -1};
+    CHECK(dobj_plane(g, P));
+    CHECK(P.n[0] == 0 && P.n[1] == 0 && P.n[2] == 1 && P.d == -0.5);
+    CHECK(P.u[0] == 0 && P.u[1] == -1 && P.u[2] == 0 && P.v[0] == 1 && P.v[1] == 0 && P.v[2] == 0);
+    const double x[3] = {dobj_center(3, 0.25), dobj_center(-1, 0.25), dobj_center(2, 0.25)};
+    CHECK(x[0] == 0.875 && x[1] == -0.125 && x[2] == 0.625 && dobj_height(P.n, P.d, x) == 0.125);
+    CHECK(dobj_center(-4, 0.5) == -1.75 && dobj_center(0, 0.01) == 0.005);
+  }
+  {   // ties go to the lowest axis; the smallest component decides otherwise
+    const double g1[4] = {0, 3, 4, 0}, g2[4] = {1, 0.5, 2, 7};
+    DobjPlane Q;
+    CHECK(dobj_plane(g1, Q) && near(Q.n[1], 0.6) && near(Q.n[2], 0.8) && near(Q.u[0], 0) && near(Q.u[1], -0.8) && near(Q.u[2], 0.6));
+    CHECK(dobj_plane(g2, Q));   // e_1: u = e_1 x n^ = (n2, 0, -n0) / |.|
+    CHECK(near(Q.u[1], 0) && Q.u[0] > 0 && Q.u[2] < 0 && near(Q.u[0] * Q.n[0] + Q.u[2] * Q.n[2], 0));
+    CHECK(near(dobj_proj(Q.u, Q.v), 0) && near(dobj_proj(Q.v, Q.n), 0) && near(dobj_proj(Q.v, Q.v), 1));
+    const double z[4] = {0, 0, 1e-13, 0}, nn[4] = {0, std::nan(""), 1, 0}, inf[4] = {0, 0, 1, HUGE_VAL}, ok[4] = {0, 0, 1e-12, 0};
+    CHECK(!dobj_plane(z, Q)); CHECK(!dobj_plane(nn, Q)); CHECK(!dobj_plane(inf, Q)); CHECK(dobj_plane(ok, Q));
+  }
+  // the guard n span^2 >= 2^62 at its boundary
+  CHECK(dobj_guard(1, 1ll << 31) && !dobj_guard(1, (1ll << 31) - 1) && dobj_guard(2, (1ll << 31) - 1));
+  CHECK(dobj_guard(1ll << 22, 1ll << 20) && !dobj_guard((1ll << 22) - 1, 1ll << 20) && dobj_guard((1ll << 22) + 1, 1ll << 20));
+  CHECK(dobj_guard(1ll << 62, 1) && !dobj_guard((1ll << 62) - 1, 1) && !dobj_guard(1, 1));
+  CHECK(dobj_guard(1ll << 26, (1ll << 21) + 1) && !dobj_guard(1ll << 26, 1ll << 17) && dobj_guard(1ll << 26, 1ll << 18));
+  CHECK(dobj_guard(3, 1240000000) == (3.0L * 1240000000.0L * 1240000000.0L >= 4611686018427387904.0L));
+  {   // the encoding keeps the order of the doubles, both zeros included, and round-trips
+    const double v[] = {-HUGE_VAL, -1e300, -2.5, -1.0, -1e-300, -0.0, 0.0, 5e-324, 1e-300, 1.0, 2.5, 1e300, HUGE_VAL};
+    const int n = (int)(sizeof(v) / sizeof(v[0]));
+    for (int i = 0; i < n; ++i) {
+      CHECK(dobj_dec(dobj_enc(v[i])) == v[i] && std::signbit(dobj_dec(dobj_enc(v[i]))) == std::signbit(v[i]));
+      if (i) CHECK(dobj_enc(v[i - 1]) < dobj_enc(v[i]));
+      CHECK(dobj_enc(v[i]) != 0 && dobj_enc(v[i]) != ~0ull);   // the reductions' neutral elements stay free
+    }
+  }
+  {   // the four branches of the quaternion
+    double q[4];
+    const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, Zh[9] = {-1, 0, 0, 0, -1, 0, 0, 0, 1}, Xh[9] = {1, 0, 0, 0, -1, 0, 0, 0, -1},
+                 Yh[9] = {-1, 0, 0, 0, 1, 0, 0, 0, -1}, Zq[9] = {0, -1, 0, 1, 0, 0, 0, 0, 1}, Zm[9] = {0, 1, 0, -1, 0, 0, 0, 0, 1};
+    dobj_quat(I, q); CHECK(q[0] == 0 && q[1] == 0 && q[2] == 0 && q[3] == 1);
+    dobj_quat(Zh, q); CHECK(q[0] == 0 && q[1] == 0 && q[2] == 1 && q[3] == 0);
+    dobj_quat(Xh, q); CHECK(q[0] == 1 && q[1] == 0 && q[2] == 0 && q[3] == 0);
+    dobj_quat(Yh, q); CHECK(q[0] == 0 && q[1] == 1 && q[2] == 0 && q[3] == 0);
+    dobj_quat(Zq, q); CHECK(q[0] == 0 && q[1] == 0 && near(q[2], std::sqrt(0.5)) && near(q[3], std::sqrt(0.5)));
+    dobj_quat(Zm, q); CHECK(near(q[2], -std::sqrt(0.5)) && near(q[3], std::sqrt(0.5)));   // w >= 0 keeps the sign of the axis
+  }
+  {   // a solid block of 12 x 8 x 6 voxels, d = k - kmin: n = 576, s = (3168, 2016, 1440), M = (24288, 11088, 7920, 10080, 5040, 5280)
+    const long long mom[kDobjMoments] = {3168, 2016, 1440, 24288, 11088, 7920, 10080, 5040, 5280};
+    double A[9], row[10];
+    dobj_frame(P, 576, mom, A);   // C = diag(143, 63, 35) / 12: C_uu = 63 / 12 < C_vv = 143 / 12, theta = pi / 2, x = v = (1, 0, 0)
+    CHECK(near(A[0], 1) && near(A[1], 0) && near(A[2], 0) && near(A[3], 0) && near(A[4], 1) && near(A[5], 0));
+    CHECK(A[6] == 0 && A[7] == 0 && A[8] == 1);
+    const double mn[3] = {0.025, 0.025, 0.025}, mx[3] = {0.575, 0.375, 0.275};
+    dobj_row(A, mn, mx, 0.05, row);
+    CHECK(near(row[0], 0.3) && near(row[1], 0.2) && near(row[2], 0.15) && near(row[7], 0.3) && near(row[8], 0.2) && near(row[9], 0.15));
+    CHECK(near(row[3], 0) && near(row[4], 0) && near(row[5], 0) && near(row[6], 1));
+    // the same block turned by 90 degrees about z (12 along y): x = (0, 1, 0) or its opposite, y = n^ x x
+    const long long turned[kDobjMoments] = {2016, 3168, 1440, 10080, 11088, 5040, 24288, 7920, 5280};
+    dobj_frame(P, 576, turned, A);
+    CHECK(near(std::fabs(A[1]), 1) && near(A[0], 0) && near(A[3], -A[1]) && near(A[4], 0));
+  }
+}
+
+static int guards() {
+  long long n, span;
+  while (std::scanf("%lld %lld", &n, &span) == 2) std::printf("%d\n", dobj_guard(n, span) ? 1 : 0);
+  return 0;
+}
+
+static int frames() {
+  double g[4], leaf;
+  int count;
+  if (std::scanf("%lf %lf %lf %lf %lf %d", &g[0], &g[1], &g[2], &g[3], &leaf, &count) != 6) return 2;
+  DobjPlane P;
+  if (!dobj_plane(g, P)) return 3;
+  for (int i = 0; i < count; ++i) {
+    long long n, mom[kDobjMoments];
+    double mn[3], mx[3], A[9], row[10];
+    if (std::scanf("%lld", &n) != 1) return 2;
+    for (int a = 0; a < kDobjMoments; ++a) if (std::scanf("%lld", &mom[a]) != 1) return 2;
+    for (int a = 0; a < 3; ++a) if (std::scanf("%lf", &mn[a]) != 1) return 2;
+    for (int a = 0; a < 3; ++a) if (std::scanf("%lf", &mx[a]) != 1) return 2;
+    dobj_frame(P, n, mom, A);
+    dobj_row(A, mn, mx, leaf, row);
+    for (int a = 0; a < 9; ++a) std::printf("%.17g ", A[a]);
+    for (int a = 0; a < 10; ++a) std::printf("%.17g%c", row[a], a == 9 ? '\n' : ' ');
+  }
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && !std::strcmp(argv[1], "guard")) return guards();
+  if (argc > 1 && !std::strcmp(argv[1], "frames")) return frames();
+  self_checks();
+  if (fails) return 1;
+  std::printf("dense_obj ok\n");
+  return 0;
+}
