@@ -54,7 +54,7 @@ extern "C" {
                              *    (esl_init_quadrics) and its outlier-rejecting form (esl_init_quadrics_robust), and map maintenance
                              *    (esl_map_overlaps, esl_map_merge), and the per-pixel rendering of a map (esl_render_map), and the voxel-fused
                              *    dense map of many RGB-D frames (esl_dense_begin / _add_frames / _info_get / _extract / _end) with its
-                             *    per-instance ellipsoids (esl_dense_objects) */
+                             *    per-instance ellipsoids (esl_dense_objects) and its dominant planes and ground (esl_dense_planes) */
 #define ESL_MAX_TRACE 32
 
 typedef enum {
@@ -999,6 +999,89 @@ int esl_dense_objects(esl_ctx* ctx, int32_t N /* labels 0 .. N-1 are objects */,
                       int64_t comp_cap, int32_t* comp_out /* comp_cap x 6 or NULL */,
                       int64_t voxel_cap, int32_t* voxel_comp_out /* voxel_cap or NULL, in esl_dense_extract's order */,
                       esl_dense_obj_result* out);
+
+/* ---- dominant planes and the ground from the dense map (additive part of ABI 5: detect by the symbol) -----------------------------------
+ * esl_dense_objects and esl_relocalize take a world ground plane as an input; esl_extract_ground_plane finds one in ONE depth image.
+ * The dense map holds the floor, the walls and the table tops as seen from every frame, deduplicated into voxels with exact integer
+ * keys and counts.  esl_dense_planes reads them as planes: an exhaustive, totally ordered hypothesise-and-score search on the device
+ * that peels one plane per round, in the manner of esl_relocalize and esl_init_quadrics_robust.  Integers and total orders decide
+ * everything discrete, the few floating-point steps run in one stated order (planes are built on the host: one compiler decides every
+ * bit), and the result is a function of the set of samples: any frame order, any split into esl_dense_add_frames calls and any run
+ * give the same bytes.
+ *  1. Eligible voxel.  A voxel of the map (dense-map steps 3 to 5) has its key k, count, label and votes.  It is eligible iff
+ *     count >= min_count and, with skip_labelled != 0, it carries no label (votes == 0; on a map begun without labels no voxel carries
+ *     one).  Centre x_a = ((double)k_a + 0.5) leaf.  n_eligible counts them; kmin_a, kmax_a over them give span = max_a (kmax_a -
+ *     kmin_a + 1).
+ *  2. Round r = 0, 1, ...: U_r = the eligible voxels not yet assigned, in ascending packed-key order, n_r its length.  n_r < 3 ends the
+ *     search with stop_reason 1; such a round does not count as started.
+ *  3. Hypothesis h = 0 .. n_hypotheses - 1 of round r: for k = 0, 1, 2, i_k = (mix >> 11) % n_r with mix = the splitmix64 finaliser
+ *     (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB, z ^= z >> 31) of seed ^ (0x9E3779B97F4A7C15 *
+ *     (uint64)(4 (r n_hypotheses + h) + k + 1)), everything mod 2^64.  With a, b, c the keys of the entries i_0, i_1, i_2 of U_r the
+ *     hypothesis is INVALID iff two indices are equal; or one of the three pairwise Chebyshev key distances is < min_baseline; or,
+ *     with N = (b - a) x (c - a) in int64 (exact) and N_a converted to double, norm = sqrt((N0 N0 + N1 N1) + N2 N2) is
+ *     < 0.5 (min_baseline min_baseline) -- near-collinear triples.  Otherwise n^ = N / norm and d^ = -((n^0 x0 + n^1 x1) + n^2 x2), x
+ *     the centre of a.
+ *  4. Score over all of U_r: h(x) = (n^0 x0 + n^1 x1) + n^2 x2 + d^, no product contracted with a sum; inlier iff |h(x)| <= dist_tol;
+ *     n_in = the inlier voxels, samples = the int64 sum of their counts.
+ *  5. Winner: the valid hypothesis with the largest n_in, then the largest samples, then the smallest h.  None valid: stop_reason 2.
+ *  6. Refinement (refine != 0).  Over the winner's inliers the int64 moments relative to kmin: n, s_a = sum d_a, M_ab = sum d_a d_b,
+ *     d = k - kmin.  n span^2 >= 2^62 (tested in integers) skips the refit: refined = 3.  Otherwise m_a = s_a / n, C_ab = M_ab / n -
+ *     m_a m_b; the eigenvector of C's smallest eigenvalue (ties to the lowest index) by a cyclic Jacobi -- 8 sweeps over the pivots
+ *     (0,1), (0,2), (1,2); a zero pivot is skipped; theta = (C_qq - C_pp) / (2 C_pq), t = sign(theta) / (|theta| + sqrt(theta^2 +
+ *     1)), c = 1 / sqrt(t^2 + 1), s = t c; columns, then rows of C, then the columns of V (p: c x_p - s x_q, q: s x_p + c x_q) --
+ *     re-normalised by sqrt((v0 v0 + v1 v1) + v2 v2); xbar_a = ((double)kmin_a + m_a + 0.5) leaf, d^ = -((n^0 xbar0 + n^1 xbar1) +
+ *     n^2 xbar2).  The refit is scored over U_r by step 4 and replaces the winner iff its (n_in, samples) is lexicographically not
+ *     smaller: refined = 1; otherwise 2; 0 with refine == 0.
+ *  7. The final plane's n_in < min_inliers ends the search with stop_reason 3: the plane is not reported, nothing is assigned.
+ *     Otherwise its inliers are assigned plane index p = r and the next round starts; max_planes planes reported end the search with
+ *     stop_reason 0.  rounds = the rounds started.
+ *  8. planes_out row p: (n^, d^) negated when d^ < 0; with d^ == 0, when the first non-zero component of n^ is negative.  centroid_out:
+ *     ((double)kmin_a + s_a / n + 0.5) leaf of the final inliers.  stats_out[8 p ..] = final inlier voxels, n_r of its round, valid
+ *     hypotheses of its round, the winner h, the winner's inlier voxels before the refit, refined, 0, 0.  samples_out[p] = the inliers'
+ *     sample sum.  voxel_plane_out[i] for the i-th voxel in esl_dense_extract's order, the first voxel_cap written: p assigned; -2
+ *     eligible and unassigned; -1 not eligible.  hyp_out[(r n_hypotheses + h) 3 ..] = valid, n_in, samples of every hypothesis of
+ *     every round started, the stopping round included (zero for an invalid hypothesis); the other rows are zero.
+ *  9. Ground (up non-zero): up^ = up / sqrt((up0 up0 + up1 up1) + up2 up2).  Candidates: the reported planes (rows of planes_out) with
+ *     |(n^0 up^0 + n^1 up^1) + n^2 up^2| >= up_min_cos.  ground_index = the candidate with the most inlier voxels, ties to the lowest
+ *     p, or -1; ground_out = that plane negated when n^ . up^ < 0 -- the orientation the height gate of esl_dense_objects needs,
+ *     whatever side of the floor the origin lies on -- or zero.  With up zero ground_index is -1. */
+typedef struct {
+  double   dist_tol;       /* 0.02 m: a voxel is an inlier of a plane when |height of its centre| <= dist_tol (PlaneRefinementComparator's 0.02) */
+  double   up[3];          /* 0 0 0: no ground choice; otherwise the world's up direction, any length > 1e-12 */
+  double   up_min_cos;     /* 0.7071067811865476: a ground candidate needs |n^ . up^| >= this (the reference's 45 degrees, PlaneExtractor.cpp:126-183) */
+  int32_t  n_hypotheses;   /* 1024 per round; 1 .. 65536 */
+  int32_t  max_planes;     /* 8; 1 .. 64 */
+  int32_t  min_inliers;    /* 1000 voxels; >= 3 */
+  int32_t  min_baseline;   /* 8: the three voxels of a hypothesis are pairwise at Chebyshev key distance >= this; >= 1 */
+  int32_t  min_count;      /* 1: a voxel takes part only with count (samples) >= this */
+  int32_t  skip_labelled;  /* 0; 1: voxels that carry an instance label (votes > 0) do not take part */
+  int32_t  refine;         /* 1: least-squares re-fit over the winner's inliers, kept only when not worse */
+  int32_t  pad;
+  uint64_t seed;           /* 0 */
+} esl_dense_plane_params;  /* 80 bytes; design choices, not values tuned on real data */
+void esl_dense_plane_params_default(esl_dense_plane_params* p);
+
+typedef struct { int32_t status, n_voxels, n_eligible, n_planes, n_assigned, ground_index, rounds, stop_reason; } esl_dense_plane_result; /* 32 bytes */
+
+/* ESL_ERR_INVALID: null ctx, out or planes_out; a negative voxel_cap, or voxel_cap > 0 with voxel_plane_out NULL; a parameter outside
+ * the ranges above; dist_tol not finite or <= 0; a non-finite up component, or an up that is neither zero nor longer than 1e-12;
+ * up_min_cos outside [0, 1]; max_planes n_hypotheses >= 2^31.  ESL_ERR_STATE: no esl_dense_begin before.  A map over its capacity is
+ * a result: ESL_OK, out->status = 3, n_voxels = -1, nothing else is written.  An empty map and a map without labels are valid.  The
+ * call changes nothing in the map except the best words and the shared sorted list, which esl_dense_extract and esl_dense_objects
+ * rebuild too: adds, extracts, object calls and plane calls may alternate.  Its buffers are slots of the dense map's own set
+ * (grow-only, sized by the map and the parameters; a warm call of a shape no larger than an earlier one allocates nothing:
+ * esl_debug_dense_allocs); one GPU, no collective, launches bracketed as kernel class 4. */
+int esl_dense_planes(esl_ctx* ctx, const esl_dense_plane_params* p /* NULL = defaults */,
+                     double* planes_out     /* max_planes x 4 world, unit normal, n_planes rows written, the others zero */,
+                     double* centroid_out   /* max_planes x 3 or NULL */,
+                     int32_t* stats_out     /* max_planes x 8 or NULL */,
+                     int64_t* samples_out   /* max_planes or NULL */,
+                     double ground_out[4]   /* or NULL */,
+                     int64_t voxel_cap, int32_t* voxel_plane_out /* voxel_cap or NULL, in esl_dense_extract's order */,
+                     int64_t* hyp_out       /* max_planes x n_hypotheses x 3 or NULL: valid, inlier voxels, inlier samples -- tests and tuning */,
+                     esl_dense_plane_result* out);
+/* the score kernel's layout: entries of U_r per LDS tile and hypotheses per workgroup (tests place list lengths around them) */
+int esl_debug_dense_planes_layout(int32_t* tile_out, int32_t* group_out);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------*/
 /* Dense FP64-MFMA Cholesky factor + solve (the reduced-camera solver of SLAM mode) on a procedurally generated,

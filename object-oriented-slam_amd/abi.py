@@ -298,6 +298,37 @@ def default_dense_obj_params(**kw):
     return p
 
 
+class EslDensePlaneParams(C.Structure):
+    """esl_dense_plane_params: the inlier tolerance, the up direction, the search's sizes and the gates of esl_dense_planes."""
+    _fields_ = [("dist_tol", C.c_double), ("up", C.c_double * 3), ("up_min_cos", C.c_double), ("n_hypotheses", C.c_int32),
+                ("max_planes", C.c_int32), ("min_inliers", C.c_int32), ("min_baseline", C.c_int32), ("min_count", C.c_int32),
+                ("skip_labelled", C.c_int32), ("refine", C.c_int32), ("pad", C.c_int32), ("seed", C.c_uint64)]
+
+
+class EslDensePlaneResult(C.Structure):
+    """esl_dense_plane_result: the totals of one esl_dense_planes call; status 3 = a map over its capacity (n_voxels = -1);
+    stop_reason 0 max_planes reported, 1 fewer than three voxels left, 2 no valid hypothesis, 3 the best plane below min_inliers."""
+    _fields_ = [("status", C.c_int32), ("n_voxels", C.c_int32), ("n_eligible", C.c_int32), ("n_planes", C.c_int32), ("n_assigned", C.c_int32),
+                ("ground_index", C.c_int32), ("rounds", C.c_int32), ("stop_reason", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert C.sizeof(EslDensePlaneParams) == 80 and C.sizeof(EslDensePlaneResult) == 32
+
+
+def default_dense_plane_params(**kw):
+    """esl_dense_plane_params_default (include/esl.h); up = a sequence of three numbers"""
+    p = EslDensePlaneParams(dist_tol=0.02, up=(C.c_double * 3)(0.0, 0.0, 0.0), up_min_cos=0.7071067811865476, n_hypotheses=1024, max_planes=8,
+                            min_inliers=1000, min_baseline=8, min_count=1, skip_labelled=0, refine=1, pad=0, seed=0)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, (C.c_double * 3)(*[float(x) for x in v]) if k == "up" else v)
+    return p
+
+
 def dense_argtypes(L):
     """the esl_dense_* calls take nullable pointers: declared, so that None passes as NULL and a wrong type raises"""
     dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
@@ -314,8 +345,13 @@ def dense_argtypes(L):
     L.esl_dense_obj_params_default.restype = None
     L.esl_dense_objects.argtypes = [C.c_void_p, C.c_int32, dp, C.POINTER(EslDenseObjParams), dp, ip, C.c_int64, ip, C.c_int64, ip,
                                     C.POINTER(EslDenseObjResult)]
+    L.esl_dense_plane_params_default.argtypes = [C.POINTER(EslDensePlaneParams)]
+    L.esl_dense_plane_params_default.restype = None
+    L.esl_dense_planes.argtypes = [C.c_void_p, C.POINTER(EslDensePlaneParams), dp, dp, ip, lp, dp, C.c_int64, ip, lp,
+                                   C.POINTER(EslDensePlaneResult)]
+    L.esl_debug_dense_planes_layout.argtypes = [ip, ip]
     for f in (L.esl_dense_begin, L.esl_dense_add_frames, L.esl_dense_info_get, L.esl_dense_extract, L.esl_dense_end,
-              L.esl_debug_dense_allocs, L.esl_dense_objects):
+              L.esl_debug_dense_allocs, L.esl_dense_objects, L.esl_dense_planes, L.esl_debug_dense_planes_layout):
         f.restype = C.c_int
 
 

@@ -14,12 +14,16 @@ namespace esl {
 
 constexpr int kInitSampleMax = 16;   // the largest sample_size
 
-// splitmix64's finaliser on seed ^ (golden ratio * (32 h + k + 1)), everything mod 2^64
-ESL_SAMPLE_HD inline uint64_t init_sample_mix(uint64_t seed, uint32_t h, uint32_t k) {
-  uint64_t z = seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)(32ull * h + k + 1ull));
+// splitmix64's finaliser of seed ^ (golden ratio * counter), everything mod 2^64 (esl_dense_planes.hpp counts differently)
+ESL_SAMPLE_HD inline uint64_t init_sample_finalise(uint64_t seed, uint64_t counter) {
+  uint64_t z = seed ^ (0x9E3779B97F4A7C15ull * counter);
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
+}
+// ... on the counter 32 h + k + 1
+ESL_SAMPLE_HD inline uint64_t init_sample_mix(uint64_t seed, uint32_t h, uint32_t k) {
+  return init_sample_finalise(seed, (uint64_t)(32ull * h + k + 1ull));
 }
 
 // how many hypotheses an object of n entries has, and how many entries each uses

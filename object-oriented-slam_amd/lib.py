@@ -31,6 +31,7 @@ EXPORTS = [
     "esl_render_params_default", "esl_render_map", "esl_debug_render_allocs", "esl_debug_scratch_allocs",
     "esl_dense_params_default", "esl_dense_begin", "esl_dense_add_frames", "esl_dense_info_get", "esl_dense_extract", "esl_dense_end",
     "esl_debug_dense_allocs", "esl_dense_obj_params_default", "esl_dense_objects",
+    "esl_dense_plane_params_default", "esl_dense_planes", "esl_debug_dense_planes_layout",
 ]
 
 
@@ -841,6 +842,42 @@ class Context:
         if r["n_voxels"] < 0:
             return dict(result=r, objs=objs[:0], stats=stats[:0], comp=comp[:0], voxel_comp=vox[:0])
         return dict(result=r, objs=objs, stats=stats, comp=comp[:min(comp_cap, r["n_components"])], voxel_comp=vox[:min(voxel_cap, r["n_voxels"])])
+
+    def dense_planes(self, params=None, voxel_cap=None, hyp=False):
+        """esl_dense_planes: the dominant planes of the dense map, one per round of a hypothesise-and-score search, and the ground among
+        them when params.up is not zero.  voxel_cap None = room for every voxel; hyp: also return every hypothesis's row.  Returns a
+        dict: result (the totals), planes (n_planes, 4), centroid (n_planes, 3), stats (n_planes, 8) int32, samples (n_planes,) int64,
+        ground (4,), voxel_plane (min(voxel_cap, n_voxels),) int32, hyp (rounds, n_hypotheses, 3) int64 or None; on a map over its
+        capacity (result n_voxels = -1) the arrays are empty."""
+        p = params if params is not None else abi.default_dense_plane_params()
+        P, Hn = max(int(p.max_planes), 0), max(int(p.n_hypotheses), 0)
+        nv = max(self.dense_info()["n_voxels"], 0)
+        voxel_cap = nv if voxel_cap is None else int(voxel_cap)
+        planes = np.zeros((max(P, 1), 4)); cen = np.zeros((max(P, 1), 3)); stats = np.zeros((max(P, 1), 8), np.int32)
+        smp = np.zeros(max(P, 1), np.int64); ground = np.zeros(4); vox = np.zeros(max(voxel_cap, 0), np.int32)
+        hy = np.zeros((max(P, 1), max(Hn, 1), 3), np.int64) if hyp and 0 < P <= 64 and 0 < Hn <= 65536 else None
+        ip, lp = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        res = abi.EslDensePlaneResult()
+        t0 = time.perf_counter()
+        rc = load().esl_dense_planes(self._h, C.byref(p), planes.ctypes.data_as(_dp), cen.ctypes.data_as(_dp), stats.ctypes.data_as(ip),
+                                     smp.ctypes.data_as(lp), ground.ctypes.data_as(_dp), voxel_cap, vox.ctypes.data_as(ip) if vox.size else None,
+                                     hy.ctypes.data_as(lp) if hy is not None else None, C.byref(res))
+        self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
+        _check(rc, "esl_dense_planes")
+        r = res.as_dict()
+        if r["n_voxels"] < 0:
+            return dict(result=r, planes=planes[:0], centroid=cen[:0], stats=stats[:0], samples=smp[:0], ground=ground, voxel_plane=vox[:0],
+                        hyp=None if hy is None else hy[:0])
+        m = r["n_planes"]
+        return dict(result=r, planes=planes[:m], centroid=cen[:m], stats=stats[:m], samples=smp[:m], ground=ground,
+                    voxel_plane=vox[:min(voxel_cap, r["n_voxels"])], hyp=None if hy is None else hy[:r["rounds"]])
+
+    @staticmethod
+    def dense_planes_layout():
+        """esl_debug_dense_planes_layout: (entries of U_r per LDS tile, hypotheses per workgroup) of the score kernel"""
+        t, g = C.c_int32(0), C.c_int32(0)
+        _check(load().esl_debug_dense_planes_layout(C.byref(t), C.byref(g)), "esl_debug_dense_planes_layout")
+        return t.value, g.value
 
     def dense_end(self):
         """esl_dense_end: forget the map (the buffers stay with the context)"""

@@ -1,0 +1,183 @@
+// A stand-alone program over csrc/esl_dense_planes.hpp (the host side of the header esl_dense.hip compiles for esl_dense_planes).
+//   no argument: self-checks on hand-computed cases -- the sampler's first values, a lattice triple's plane, the validity tests at
+//                their boundaries, the inlier test, the winner's order, the Jacobi of a diagonal and of a known matrix, the refit of a
+//                lattice slab, both orientation rules and the ground choice; exit status 0 when all hold.
+//   "sample":    lines  seed r n_hypotheses h k n_r  ->  mix (hex) and the index.
+//   "hyp":       min_baseline leaf, then lines  i(3) a(3) b(3) c(3)  ->  valid and the plane's four doubles as bit patterns.
+//   "jacobi":    lines of six doubles  ->  the vector's three bit patterns.
+//   "refit":     leaf, then lines  kmin(3) mom(11)  ->  the plane's four and the centroid's three bit patterns.
+//   "orient":    lines of four doubles  ->  the oriented plane's bit patterns.
+//   "ground":    up(3) up_min_cos n, then n lines  plane(4) n_in  ->  the index and the ground's four bit patterns.
+// Doubles are read with 17 significant digits (a round trip) and printed as bit patterns: the CPU test compares them with the numpy
+// statement bit for bit.  Built and run by tests/test_dense_planes_ref.py, also under -fsanitize=address,undefined.  Compile with
+// -ffp-contract=off.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../object-oriented-slam_amd/csrc/esl_dense_planes.hpp"
+
+using namespace esl;
+
+static int fails = 0;
+#define CHECK(c) do { if (!(c)) { std::printf("FAILED line %d: %s\n", __LINE__, #c); ++fails; } } while (0)
+
+static bool near(double a, double b, double tol = 1e-15) { return std::fabs(a - b) <= tol; }
+static unsigned long long bits(double v) { unsigned long long u; std::memcpy(&u, &v, 8); return u; }
+static void put(const double* v, int n) { for (int a = 0; a < n; ++a) std::printf("%016llx%c", bits(v[a]), a == n - 1 ? '\n' : ' '); }
+
+static void self_checks() {
+  // the counter of (r, h, k) = (0, 0, 0) is 1: splitmix64's first output of the state 0
+  CHECK(dpl_mix(0, 0, 64, 0, 0) == 0xE220A8397B1DCDAFull);
+  CHECK(dpl_mix(0, 0, 64, 0, 1) == init_sample_finalise(0, 2) && dpl_mix(5, 2, 100, 7, 2) == init_sample_finalise(5, 4ull * 207 + 3));
+  CHECK(init_sample_mix(9, 3, 4) == init_sample_finalise(9, 32ull * 3 + 5));
+  CHECK(dpl_index(0, 0, 64, 0, 0, 1000) == (int)((0xE220A8397B1DCDAFull >> 11) % 1000ull) && dpl_index(1, 3, 9, 2, 1, 1) == 0);
+  {   // the slab kz = 0 at leaf 0.01: N = (8,0,0) x (0,8,0) = (0,0,64), the plane z = 0.005
+    const int i[3] = {0, 1, 2}, a[3] = {0, 0, 0}, b[3] = {8, 0, 0}, c[3] = {0, 8, 0};
+    double pl[4];
+    CHECK(dpl_hypothesis(i, a, b, c, 8, 0.01, pl) && pl[0] == 0 && pl[1] == 0 && pl[2] == 1 && pl[3] == -0.005);
+    CHECK(!dpl_hypothesis(i, a, b, c, 9, 0.01, pl) && pl[0] == 0 && pl[3] == 0);          // a baseline of 8 < 9
+    const int same[3] = {4, 1, 4};
+    CHECK(!dpl_hypothesis(same, a, b, c, 1, 0.01, pl));
+    const int in[3] = {3, 2, 0}, off[3] = {3, 2, 1};
+    const double xi[3] = {dobj_center(in[0], 0.01), dobj_center(in[1], 0.01), dobj_center(in[2], 0.01)};
+    const double xo[3] = {dobj_center(off[0], 0.01), dobj_center(off[1], 0.01), dobj_center(off[2], 0.01)};
+    CHECK(dpl_hypothesis(i, a, b, c, 8, 0.01, pl));
+    CHECK(dpl_inlier(pl, xi, 0.004) && !dpl_inlier(pl, xo, 0.004) && dpl_inlier(pl, xo, 0.0101));
+    // near-collinear: b - a = (8, 0, 0), c - a = (16, 1, 0): N = (0, 0, 8); norm 8 < 12.5 at min_baseline 5, not < 8 at 4
+    const int c2[3] = {16, 1, 0};
+    CHECK(!dpl_hypothesis(i, a, b, c2, 5, 0.01, pl) && dpl_hypothesis(i, a, b, c2, 4, 0.01, pl) && pl[2] == 1);
+    const int c3[3] = {16, 0, 0};
+    CHECK(!dpl_hypothesis(i, a, b, c3, 1, 0.01, pl));          // collinear: norm 0 < 0.5
+    // the slab kx + kz = 60: (1, 0, 1) / sqrt 2
+    const int p0[3] = {20, 0, 40}, p1[3] = {30, 0, 30}, p2[3] = {20, 10, 40};
+    CHECK(dpl_hypothesis(i, p0, p1, p2, 8, 0.01, pl));          // N = (10, 0, -10) x (0, 10, 0) = (100, 0, 100)
+    CHECK(near(pl[0], std::sqrt(0.5)) && pl[1] == 0 && near(pl[2], std::sqrt(0.5)) && near(pl[3], -61 * 0.01 * std::sqrt(0.5)));
+  }
+  CHECK(dpl_better(5, 1, 9, 4, 100, 0) && !dpl_better(4, 100, 0, 5, 1, 9) && dpl_better(5, 2, 9, 5, 1, 0) && dpl_better(5, 2, 3, 5, 2, 4));
+  CHECK(!dpl_better(5, 2, 4, 5, 2, 3));
+  {   // a diagonal matrix is left alone: the smallest entry's axis, ties to the lowest index
+    const double D1[6] = {3, 0, 0, 1, 0, 2}, D2[6] = {2, 0, 0, 2, 0, 5}, S[6] = {2, 1, 0, 2, 0, 3};
+    double n[3];
+    dpl_jacobi_min(D1, n); CHECK(n[0] == 0 && n[1] == 1 && n[2] == 0);
+    dpl_jacobi_min(D2, n); CHECK(n[0] == 1 && n[1] == 0 && n[2] == 0);
+    dpl_jacobi_min(S, n);   // [[2, 1], [1, 2]]: eigenvalue 1 with (1, -1) / sqrt 2 up to sign
+    CHECK(near(std::fabs(n[0]), std::sqrt(0.5)) && near(n[0], -n[1]) && n[2] == 0);
+  }
+  {   // the 40 x 40 slab kz = 0 relative to kmin = (0, 0, 0): s = (31200, 31200, 0), M_xx = M_yy = 40 * 20540, M_xy = 780^2, M_*z = 0
+    const long long mom[kDplMoments] = {1600, 1600, 31200, 31200, 0, 821600, 608400, 0, 821600, 0, 0};
+    const int kmin[3] = {0, 0, 0};
+    double pl[4], x[3];
+    dpl_refit(mom, kmin, 0.01, pl);
+    dpl_centroid(mom, kmin, 0.01, x);
+    CHECK(pl[0] == 0 && pl[1] == 0 && std::fabs(pl[2]) == 1 && std::fabs(pl[3]) == 0.005 && near(x[0], 0.2) && near(x[1], 0.2) && x[2] == 0.005);
+  }
+  {   // the orientation rules
+    double a[4] = {0, 0, 1, -0.5}, b[4] = {0, 0, -1, 0.5}, z1[4] = {0, -1, 0, 0}, z2[4] = {0, 1, 0, 0}, z3[4] = {-0.6, 0.8, 0, 0};
+    dpl_orient_out(a); CHECK(a[2] == -1 && a[3] == 0.5);
+    dpl_orient_out(b); CHECK(b[2] == -1 && b[3] == 0.5);
+    dpl_orient_out(z1); CHECK(z1[1] == 1 && z1[3] == 0);
+    dpl_orient_out(z2); CHECK(z2[1] == 1);
+    dpl_orient_out(z3); CHECK(z3[0] == 0.6 && z3[1] == -0.8);
+  }
+  {   // the ground with up = -z: plane 1 = (0, 0, 1, 1) is reported with d^ > 0 and handed out negated, n^ . up^ > 0
+    const double planes[12] = {1, 0, 0, 2, 0, 0, 1, 1, 0, 0.6, 0.8, 3};
+    const int32_t n_in[3] = {900, 500, 500};
+    const double up[3] = {0, 0, -2}, zero[3] = {0, 0, 0}, tiny[3] = {0, 1e-13, 0}, ok[3] = {0, 1e-11, 0};
+    double uh[3], g[4];
+    CHECK(dpl_up(up, uh) && uh[0] == 0 && uh[2] == -1 && !dpl_up(zero, uh));
+    CHECK(dpl_up_valid(up) && dpl_up_valid(zero) && !dpl_up_valid(tiny) && dpl_up_valid(ok));
+    dpl_up(up, uh);
+    CHECK(dpl_ground(planes, n_in, 3, uh, 0.7071067811865476, g) == 1 && g[2] == -1 && g[3] == -1);   // ties to the lowest index; flipped
+    CHECK(dpl_ground(planes, n_in, 3, uh, 0.9, g) == 1 && dpl_ground(planes, n_in, 1, uh, 0.5, g) == -1 && g[0] == 0 && g[3] == 0);
+    const int32_t more[3] = {900, 500, 501};
+    CHECK(dpl_ground(planes, more, 3, uh, 0.7071067811865476, g) == 2 && g[1] == -0.6 && g[2] == -0.8 && g[3] == -3);
+  }
+  CHECK(dobj_guard(1ll << 22, 1ll << 20) && !dobj_guard((1ll << 22) - 1, 1ll << 20));
+}
+
+static int samples() {
+  unsigned long long seed;
+  int r, H, h, k, n_r;
+  while (std::scanf("%llu %d %d %d %d %d", &seed, &r, &H, &h, &k, &n_r) == 6)
+    std::printf("%016llx %d\n", (unsigned long long)dpl_mix(seed, r, H, h, k), dpl_index(seed, r, H, h, k, n_r));
+  return 0;
+}
+
+static int hyps() {
+  int mb;
+  double leaf;
+  if (std::scanf("%d %lf", &mb, &leaf) != 2) return 2;
+  int v[12];
+  for (;;) {
+    int got = 0;
+    for (int a = 0; a < 12; ++a) got += std::scanf("%d", &v[a]) == 1;
+    if (got != 12) break;
+    double pl[4];
+    const bool ok = dpl_hypothesis(v, v + 3, v + 6, v + 9, mb, leaf, pl);
+    std::printf("%d ", ok ? 1 : 0);
+    put(pl, 4);
+  }
+  return 0;
+}
+
+static int jacobis() {
+  double C[6], n[3];
+  while (std::scanf("%lf %lf %lf %lf %lf %lf", &C[0], &C[1], &C[2], &C[3], &C[4], &C[5]) == 6) { dpl_jacobi_min(C, n); put(n, 3); }
+  return 0;
+}
+
+static int refits() {
+  double leaf;
+  if (std::scanf("%lf", &leaf) != 1) return 2;
+  for (;;) {
+    int kmin[3];
+    long long mom[kDplMoments];
+    if (std::scanf("%d %d %d", &kmin[0], &kmin[1], &kmin[2]) != 3) break;
+    for (int a = 0; a < kDplMoments; ++a) if (std::scanf("%lld", &mom[a]) != 1) return 2;
+    double out[7];
+    dpl_refit(mom, kmin, leaf, out);
+    dpl_centroid(mom, kmin, leaf, out + 4);
+    put(out, 7);
+  }
+  return 0;
+}
+
+static int orients() {
+  double pl[4];
+  while (std::scanf("%lf %lf %lf %lf", &pl[0], &pl[1], &pl[2], &pl[3]) == 4) { dpl_orient_out(pl); put(pl, 4); }
+  return 0;
+}
+
+static int grounds() {
+  double up[3], cosv;
+  int n;
+  if (std::scanf("%lf %lf %lf %lf %d", &up[0], &up[1], &up[2], &cosv, &n) != 5 || n < 0 || n > 64) return 2;
+  std::vector<double> planes((size_t)n * 4 + 4);
+  std::vector<int32_t> n_in((size_t)n + 1);
+  for (int p = 0; p < n; ++p) {
+    int v;
+    if (std::scanf("%lf %lf %lf %lf %d", &planes[4 * p], &planes[4 * p + 1], &planes[4 * p + 2], &planes[4 * p + 3], &v) != 5) return 2;
+    n_in[(size_t)p] = v;
+  }
+  double uh[3], g[4] = {0, 0, 0, 0};
+  int idx = -1;
+  if (dpl_up_valid(up) && dpl_up(up, uh)) idx = dpl_ground(planes.data(), n_in.data(), n, uh, cosv, g);
+  std::printf("%d ", idx);
+  put(g, 4);
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && !std::strcmp(argv[1], "sample")) return samples();
+  if (argc > 1 && !std::strcmp(argv[1], "hyp")) return hyps();
+  if (argc > 1 && !std::strcmp(argv[1], "jacobi")) return jacobis();
+  if (argc > 1 && !std::strcmp(argv[1], "refit")) return refits();
+  if (argc > 1 && !std::strcmp(argv[1], "orient")) return orients();
+  if (argc > 1 && !std::strcmp(argv[1], "ground")) return grounds();
+  self_checks();
+  if (fails) return 1;
+  std::printf("dense_planes ok\n");
+  return 0;
+}
