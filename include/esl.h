@@ -54,7 +54,8 @@ extern "C" {
                              *    (esl_init_quadrics) and its outlier-rejecting form (esl_init_quadrics_robust), and map maintenance
                              *    (esl_map_overlaps, esl_map_merge), and the per-pixel rendering of a map (esl_render_map), and the voxel-fused
                              *    dense map of many RGB-D frames (esl_dense_begin / _add_frames / _info_get / _extract / _end) with its
-                             *    per-instance ellipsoids (esl_dense_objects) and its dominant planes and ground (esl_dense_planes) */
+                             *    per-instance ellipsoids (esl_dense_objects) and its dominant planes and ground (esl_dense_planes), and
+                             *    its exact de-integration (esl_dense_remove_frames / _move_frames / _purge / _slots_get) */
 #define ESL_MAX_TRACE 32
 
 typedef enum {
@@ -897,7 +898,39 @@ int esl_render_map(esl_ctx* ctx,
  *     writes nothing and reports n_voxels = -1, esl_dense_info_get reports n_voxels = n_pairs = -1.  No probe loop is unbounded.
  *  7. Extract: the voxels in ascending packed-key order, the first cap of them written, n_voxels reporting all.  key_out = (kx, ky, kz);
  *     xyz_out[a] = (double)S_a / 2^30 / (double)count; bgr_out = (2 sum + count) / (2 count) in integers (0 on a map without colour);
- *     inst_out / votes_out as step 5 (-1 / 0 on a map without labels).  Extract does not change the map; adds and extracts may alternate. */
+ *     inst_out / votes_out as step 5 (-1 / 0 on a map without labels).  Extract does not change the map; adds and extracts may alternate.
+ * The map follows the poses (esl_dense_remove_frames / _move_frames / _purge / _slots_get, below the calls above).  Every per-voxel
+ * quantity is an integer sum, so subtracting a frame's samples is the exact inverse of adding them.  The contract: while the status
+ * stays 0, any interleaving of add, remove, move and purge calls leaves the map that esl_dense_begin and ONE esl_dense_add_frames of
+ * the multiset difference (the samples added and not removed) would leave -- the same bytes in every output of esl_dense_extract,
+ * esl_dense_objects and esl_dense_planes and in esl_dense_info.  Only esl_dense_slots_get and the capacity status (step 11) may tell
+ * the two apart.
+ *  8. Remove.  The samples of the given frames are formed by steps 1 to 3 exactly as esl_dense_add_frames forms them (the same
+ *     arithmetic, pose handling and validation; n_sampled, n_zero, n_depth_out, n_key_out and n_used mean the same).  Every used
+ *     sample subtracts from its voxel what adding it would have added: 1 from count, llrint(p_w[a] 2^30) from S_a, its B, G and R
+ *     from the colour sums and, with labels and id >= 0, one vote from its (voxel, id) pair.  Removal only looks up: it claims no
+ *     voxel slot and no pair slot.  A used sample whose voxel is not in the table counts in n_missing and subtracts nothing; one whose
+ *     voxel is there but whose (voxel, id) pair is not counts in n_missing too: its voxel is still decremented, no vote is subtracted.
+ *     n_emptied = the number of voxels whose count this call took to 0.  n_samples drops by n_used.
+ *  9. Live and dead; consistency.  A claimed voxel slot with count > 0 is live, with count == 0 dead; the same holds for a pair slot
+ *     and its 32-bit count.  After every removing call an audit pass over both tables recounts the live and the dead slots and sets
+ *     the sticky status 4 (inconsistent) when n_missing > 0, a voxel count is negative as int64, a dead voxel has a non-zero S_a or
+ *     colour sum, a pair count has bit 31 set, or a live pair belongs to a dead voxel: something was removed that had not been added
+ *     as given.  Status 4 is a result like status 3, with the same consequences: the return is ESL_OK; nothing more is added or removed
+ *     until the next esl_dense_begin (the calls' counts are 0); esl_dense_extract, esl_dense_objects and esl_dense_planes report
+ *     n_voxels = -1 and write nothing; esl_dense_info_get reports n_voxels = n_pairs = -1.  A map at status 3 stays at 3.
+ * 10. What the rest sees: live slots only.  esl_dense_info's n_voxels and n_pairs count live slots; extract, objects and planes list
+ *     live voxels, and a dead voxel is no neighbour of a component; a dead pair casts no vote.  A dead slot keeps its key until a
+ *     purge, so no probe chain loses a link, and a later add of the same key revives it.
+ * 11. Capacity counts CLAIMED slots, live plus dead: status 3 is raised when the claimed voxel slots exceed max_voxels or the claimed
+ *     pair slots 2 max_voxels (on a map without removals: step 6).  esl_dense_purge rebuilds both tables from the live records and
+ *     the live pairs alone: afterwards claimed = live and dead = 0, and nothing any other call reports has changed.
+ *     esl_dense_slots_get reports the claimed and the dead slots of both tables (-1 four times on a map whose status is not 0).
+ * Move (esl_dense_move_frames) = remove with cams_old (step 8), then add with cams_new (steps 1 to 5), in one call and with one upload
+ * of the images, for the frames whose seven cams_old doubles differ from their cams_new doubles in any bit (n_frames_moved); the
+ * others are skipped (n_frames_same).  Every check runs before anything changes: all poses of both sets, and n_samples + (sampled
+ * pixels of a frame) n_frames_moved < 2^31 (conservative: the removal is not credited).  If the removal ends in status 4, nothing is
+ * added. */
 typedef struct {
   double  leaf;         /* 0.01 m  (Tracking.cpp:241 voxelFilter(0.01)); finite, > 0 */
   double  depth_scale;  /* 5000   raw units per metre; finite, > 0 */
@@ -930,6 +963,29 @@ int esl_dense_info_get(esl_ctx* ctx, esl_dense_info* out);
 int esl_dense_extract(esl_ctx* ctx, int64_t cap, int32_t* key_out /* cap x 3 */, double* xyz_out /* cap x 3 */, int32_t* count_out /* cap */,
                       uint8_t* bgr_out /* cap x 3 */, int32_t* inst_out /* cap */, int32_t* votes_out /* cap */, int64_t* n_voxels);
 int esl_dense_end(esl_ctx* ctx);   /* forget the map; the buffers stay (grow-only), esl_ctx_destroy frees them */
+
+/* Steps 8 to 11 (additive part of ABI 5: detect by the symbol). */
+typedef struct { int64_t n_sampled, n_zero, n_depth_out, n_key_out, n_used, n_missing, n_emptied; int32_t status, pad; } esl_dense_remove_result; /* 64 bytes */
+/* Errors as esl_dense_add_frames, case by case (the frames' sampled pixels reaching 2^31 in place of n_samples).  F = 0 is valid.  An
+ * error leaves the map as it was. */
+int esl_dense_remove_frames(esl_ctx* ctx, const double* cams /* F x 7 Tcw, the poses the frames were added with; NULL = resident */,
+                            int32_t F, const double K[4], int32_t rows, int32_t cols,
+                            const uint16_t* depth /* F x rows x cols */, const uint8_t* bgr /* F x rows x cols x 3 or NULL */,
+                            const int32_t* inst /* F x rows x cols or NULL */, esl_dense_remove_result* out /* may be NULL */);
+
+typedef struct { esl_dense_remove_result removed; esl_dense_add_result added; int32_t n_frames_moved, n_frames_same; } esl_dense_move_result; /* 120 bytes */
+/* Errors as esl_dense_add_frames, case by case (cams_new in the place of cams); ESL_ERR_INVALID also for a null cams_old with F > 0
+ * and an invalid pose in either set. */
+int esl_dense_move_frames(esl_ctx* ctx, const double* cams_old /* F x 7, not NULL */,
+                          const double* cams_new /* F x 7, NULL = resident camera states */, int32_t F, const double K[4], int32_t rows,
+                          int32_t cols, const uint16_t* depth, const uint8_t* bgr, const int32_t* inst,
+                          esl_dense_move_result* out /* may be NULL */);
+
+typedef struct { int64_t voxel_slots, dead_voxels, pair_slots, dead_pairs; } esl_dense_slots; /* 32 bytes: claimed slots and the dead among them */
+/* ESL_ERR_INVALID: null ctx (esl_dense_slots_get: or out).  ESL_ERR_STATE: no esl_dense_begin before.  On a map whose status is not 0
+ * both return ESL_OK and esl_dense_purge does nothing.  before / after: the slots ahead of and behind the purge. */
+int esl_dense_slots_get(esl_ctx* ctx, esl_dense_slots* out);
+int esl_dense_purge(esl_ctx* ctx, esl_dense_slots* before /* or NULL */, esl_dense_slots* after /* or NULL */);
 /* The calls leave the resident graph, its states and the solver blobs alone, keep grow-only device buffers of their own (a warm call
  * allocates nothing), run on this context's GPU only and issue no collective.  With esl_profile_enable(ctx, 2) their launches are
  * bracketed as kernel class 4.  esl_debug_dense_allocs: the device allocations these calls have made on this context and the bytes

@@ -262,6 +262,35 @@ class EslDenseInfo(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
 
 
+class EslDenseRemoveResult(C.Structure):
+    """esl_dense_remove_result: one esl_dense_remove_frames call's counts; status 4 = the map is inconsistent."""
+    _fields_ = [("n_sampled", C.c_int64), ("n_zero", C.c_int64), ("n_depth_out", C.c_int64), ("n_key_out", C.c_int64),
+                ("n_used", C.c_int64), ("n_missing", C.c_int64), ("n_emptied", C.c_int64), ("status", C.c_int32), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
+
+
+class EslDenseMoveResult(C.Structure):
+    """esl_dense_move_result: the removal's and the add's counts of one esl_dense_move_frames call, and the frames moved / skipped."""
+    _fields_ = [("removed", EslDenseRemoveResult), ("added", EslDenseAddResult), ("n_frames_moved", C.c_int32), ("n_frames_same", C.c_int32)]
+
+    def as_dict(self):
+        return dict(removed=self.removed.as_dict(), added=self.added.as_dict(), n_frames_moved=int(self.n_frames_moved),
+                    n_frames_same=int(self.n_frames_same))
+
+
+class EslDenseSlots(C.Structure):
+    """esl_dense_slots: the claimed slots of the voxel and the pair table and the dead among them."""
+    _fields_ = [("voxel_slots", C.c_int64), ("dead_voxels", C.c_int64), ("pair_slots", C.c_int64), ("dead_pairs", C.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert C.sizeof(EslDenseRemoveResult) == 64 and C.sizeof(EslDenseMoveResult) == 120 and C.sizeof(EslDenseSlots) == 32
+
+
 def default_dense_params(**kw):
     """esl_dense_params_default: the reference's 1 cm leaf and depth gate; stride and max_voxels are design choices (include/esl.h)."""
     p = EslDenseParams(leaf=0.01, depth_scale=5000.0, depth_min=0.5, depth_max=6.0, stride=1, max_voxels=1048576)
@@ -350,8 +379,14 @@ def dense_argtypes(L):
     L.esl_dense_planes.argtypes = [C.c_void_p, C.POINTER(EslDensePlaneParams), dp, dp, ip, lp, dp, C.c_int64, ip, lp,
                                    C.POINTER(EslDensePlaneResult)]
     L.esl_debug_dense_planes_layout.argtypes = [ip, ip]
+    img = [C.c_int32, dp, C.c_int32, C.c_int32, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8), ip]
+    L.esl_dense_remove_frames.argtypes = [C.c_void_p, dp] + img + [C.POINTER(EslDenseRemoveResult)]
+    L.esl_dense_move_frames.argtypes = [C.c_void_p, dp, dp] + img + [C.POINTER(EslDenseMoveResult)]
+    L.esl_dense_slots_get.argtypes = [C.c_void_p, C.POINTER(EslDenseSlots)]
+    L.esl_dense_purge.argtypes = [C.c_void_p, C.POINTER(EslDenseSlots), C.POINTER(EslDenseSlots)]
     for f in (L.esl_dense_begin, L.esl_dense_add_frames, L.esl_dense_info_get, L.esl_dense_extract, L.esl_dense_end,
-              L.esl_debug_dense_allocs, L.esl_dense_objects, L.esl_dense_planes, L.esl_debug_dense_planes_layout):
+              L.esl_debug_dense_allocs, L.esl_dense_objects, L.esl_dense_planes, L.esl_debug_dense_planes_layout,
+              L.esl_dense_remove_frames, L.esl_dense_move_frames, L.esl_dense_slots_get, L.esl_dense_purge):
         f.restype = C.c_int
 
 

@@ -12,8 +12,13 @@
 //                     into its first lane by a segmented shuffle scan and only run heads touch the voxel table; the run's lanes then
 //                     learn the head's slot and fold their votes per (run, id) the same way.  Integer sums: both forms give the same
 //                     bits.  ESL_DENSE_COMBINE=0 / 1 picks the form (read by esl_dense_begin; measurement: scripts/dense_map_bench.py).
-//   k_dense_compact   extract: the occupied slots as (packed key, slot), appended with one atomic per wave; clears the best words
-//   k_dense_vote      extract: per occupied pair one atomicMax of (votes << 32 | ~id) into its voxel's best word: most votes, ties to
+//                     REMOVE (esl_dense_remove_frames / _move_frames, steps 8-11): the same kernel subtracting, by lookups that claim
+//                     nothing.  A slot whose count reaches 0 is DEAD: it keeps its key (no probe chain loses a link) until a purge.
+//   k_dense_audit     after every removing call, and after an add onto a map with dead slots: live and dead slots of both tables,
+//                     and the inconsistencies that raise the sticky status 4
+//   k_dense_export / _reinsert / _reinsert_pairs   esl_dense_purge: the tables rebuilt from the live records and pairs alone
+//   k_dense_compact   extract: the live slots as (packed key, slot), appended with one atomic per wave; clears the best words
+//   k_dense_vote      extract: per live pair one atomicMax of (votes << 32 | ~id) into its voxel's best word: most votes, ties to
 //                     the lowest id.  Done at extract time over the whole pair table, so incremental adds stay exact.
 //   rocprim radix sort of (packed key, slot), then k_dense_gather writes the first `cap` voxels in key order.
 //   esl_dense_objects (include/esl.h, "per-instance ellipsoids from the dense map"; arithmetic: esl_dense_obj.hpp) works on that sorted
@@ -50,6 +55,9 @@ namespace esl {
 static_assert(sizeof(esl_dense_params) == 40, "include/esl.h states this size");
 static_assert(sizeof(esl_dense_add_result) == 48, "include/esl.h states this size");
 static_assert(sizeof(esl_dense_info) == 32, "include/esl.h states this size");
+static_assert(sizeof(esl_dense_remove_result) == 64, "include/esl.h states this size");
+static_assert(sizeof(esl_dense_move_result) == 120, "include/esl.h states this size");
+static_assert(sizeof(esl_dense_slots) == 32, "include/esl.h states this size");
 static_assert(sizeof(esl_dense_obj_params) == 32, "include/esl.h states this size");
 static_assert(sizeof(esl_dense_obj_result) == 32, "include/esl.h states this size");
 static_assert(sizeof(esl_dense_plane_params) == 80, "include/esl.h states this size");
@@ -63,7 +71,10 @@ struct DenseRec { long long S[3]; u64 col[3]; u64 count; u64 best; };
 static_assert(sizeof(DenseRec) == 64, "one record per 64-byte segment");
 
 // the device counters: this call's five counts, then what lives as long as the map
-enum { DC_SAMPLED, DC_ZERO, DC_DEPTH_OUT, DC_KEY_OUT, DC_USED, DC_VOXELS, DC_PAIRS, DC_STATUS, DC_LIST, DC_COUNT };
+// (DC_VOXELS / DC_PAIRS count the slots CLAIMED since esl_dense_begin or the last purge), then a removing call's n_missing, the audit's
+// five words and the purge's two list lengths
+enum { DC_SAMPLED, DC_ZERO, DC_DEPTH_OUT, DC_KEY_OUT, DC_USED, DC_VOXELS, DC_PAIRS, DC_STATUS, DC_LIST,
+       DC_MISSING, DC_LIVE_V, DC_DEAD_V, DC_LIVE_P, DC_DEAD_P, DC_BAD, DC_XV, DC_XP, DC_COUNT };
 
 struct DenseArgs {
   const double* pose; int F;
@@ -82,16 +93,20 @@ enum { DB_KEYS, DB_REC, DB_PKEYS, DB_PCNT, DB_CTR, DB_POSE, DB_DEPTH, DB_BGR, DB
        DB_SIDX, DB_VLAB, DB_PARENT, DB_VROOT, DB_ROWOF, DB_CSIZE, DB_CSAMP, DB_OCTR, DB_LABKEPT, DB_TABLE, DB_ROWROOT, DB_ROWOBJ,
        DB_KBOX, DB_MOM, DB_AXES, DB_EXT, DB_VOUT,
        // esl_dense_planes
-       DB_PSTATE, DB_PCTR, DB_PBOX, DB_PLIST, DB_PSELTMP, DB_PVOX, DB_PGKEY, DB_PPLANES, DB_PVALID, DB_PHACC, DB_PMOM, DB_PVOUT, DB_COUNT };
+       DB_PSTATE, DB_PCTR, DB_PBOX, DB_PLIST, DB_PSELTMP, DB_PVOX, DB_PGKEY, DB_PPLANES, DB_PVALID, DB_PHACC, DB_PMOM, DB_PVOUT,
+       // esl_dense_move_frames (the second pose set), esl_dense_purge (the live records and pairs)
+       DB_POSE2, DB_XKEY, DB_XREC, DB_XPKEY, DB_XPID, DB_XPCNT, DB_COUNT };
 struct DenseState {
   ScratchSet<DB_COUNT> set;
   bool begun = false, combine = true;
   esl_dense_params p;
   int with_color = 0, with_inst = 0;
   u64 H = 0;
-  long long n_samples = 0, n_voxels = 0, n_pairs = 0;
+  long long n_samples = 0, n_voxels = 0, n_pairs = 0;   // n_voxels, n_pairs: LIVE slots (what k_dense_compact lists, what votes)
+  long long dead_voxels = 0, dead_pairs = 0;             // claimed slots whose count is 0 (steps 9 to 11); claimed = live + dead
   int status = 0;
-  std::vector<double> cams, pose;   // host staging of a call's poses
+  std::vector<double> cams, pose, cams2, pose2;   // host staging of a call's poses (esl_dense_move_frames: both sets)
+  std::vector<int> moved;                         // esl_dense_move_frames: the frames whose pose changed
 };
 
 __device__ __forceinline__ u64 dense_hash(u64 k) {   // hash64 of esl_fit.hip
@@ -125,6 +140,19 @@ __device__ __forceinline__ long long dense_find(u64* keys, u64 n, u64 key, u64* 
   return -1;
 }
 
+// The slot of `key`, or -1 when it is not in the table: dense_find's hash and probe without the CAS.  Nothing is claimed; at most n
+// probes, ending at the first empty slot (slots keep their key until a purge, so a chain never loses a link).
+__device__ __forceinline__ long long dense_lookup(const u64* keys, u64 n, u64 key) {
+  u64 slot = dense_hash(key) & (n - 1);
+  for (u64 it = 0; it < n; ++it) {
+    const u64 cur = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == key) return (long long)slot;
+    if (cur == kDenseEmpty) return -1;
+    slot = (slot + 1) & (n - 1);
+  }
+  return -1;
+}
+
 // segmented sum towards the first lane of every run: rid = the run's number (non-decreasing along the wave)
 template <class T>
 __device__ __forceinline__ T dense_run_sum(T v, int rid, int lane) {
@@ -138,7 +166,11 @@ __device__ __forceinline__ T dense_run_sum(T v, int rid, int lane) {
 }
 
 // grid = (blocks over the sampled pixels of a frame, frames: at most 65535, a workgroup takes blockIdx.y, + gridDim.y, ...)
-template <bool COMBINE>
+// REMOVE (step 8): the same samples, formed the same way, subtract what they added.  The slots are looked up, never claimed
+// (dense_lookup); every 64-bit sum takes the two's-complement negation of what the add takes, the pair count an atomicSub; a used
+// sample that finds no voxel, or no pair, counts in ctr[DC_MISSING].  Every `REMOVE ? :` below is a compile-time choice: the add
+// instantiations are the kernels they were, their atomics fire and forget.
+template <bool COMBINE, bool REMOVE>
 static __global__ __launch_bounds__(kDenseThreads) void k_dense_insert(DenseArgs a) {
   const int lane = threadIdx.x & 63;
   const u64 le = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);   // the lanes up to and including this one
@@ -186,20 +218,26 @@ static __global__ __launch_bounds__(kDenseThreads) void k_dense_insert(DenseArgs
     }
     const bool used = cat == DENSE_USED;
     long long slot = -1;
+    bool miss = false;   // REMOVE: this lane's sample found no voxel, or no pair
     if (!COMBINE) {
       if (used) {
-        slot = dense_find(a.keys, a.H, key, a.ctr, DC_VOXELS, a.max_voxels);
+        slot = REMOVE ? dense_lookup(a.keys, a.H, key) : dense_find(a.keys, a.H, key, a.ctr, DC_VOXELS, a.max_voxels);
+        if (REMOVE) miss = slot < 0;
         if (slot >= 0) {
           DenseRec* r = a.rec + slot;
-          atomicAdd((u64*)&r->S[0], (u64)s0); atomicAdd((u64*)&r->S[1], (u64)s1); atomicAdd((u64*)&r->S[2], (u64)s2);
-          atomicAdd(&r->count, 1ull);
+          atomicAdd((u64*)&r->S[0], REMOVE ? 0ull - (u64)s0 : (u64)s0); atomicAdd((u64*)&r->S[1], REMOVE ? 0ull - (u64)s1 : (u64)s1);
+          atomicAdd((u64*)&r->S[2], REMOVE ? 0ull - (u64)s2 : (u64)s2);
+          atomicAdd(&r->count, REMOVE ? ~0ull : 1ull);
           if (a.bgr) {
-            atomicAdd(&r->col[0], rgbc & 0xFFFFull); atomicAdd(&r->col[1], (rgbc >> 16) & 0xFFFFull);
-            atomicAdd(&r->col[2], (rgbc >> 32) & 0xFFFFull);
+            atomicAdd(&r->col[0], REMOVE ? 0ull - (rgbc & 0xFFFFull) : rgbc & 0xFFFFull);
+            atomicAdd(&r->col[1], REMOVE ? 0ull - ((rgbc >> 16) & 0xFFFFull) : (rgbc >> 16) & 0xFFFFull);
+            atomicAdd(&r->col[2], REMOVE ? 0ull - ((rgbc >> 32) & 0xFFFFull) : (rgbc >> 32) & 0xFFFFull);
           }
           if (a.pkeys && id >= 0) {
-            const long long ps = dense_find(a.pkeys, a.P, (u64)slot << 32 | (u64)(unsigned)id, a.ctr, DC_PAIRS, a.max_pairs);
-            if (ps >= 0) atomicAdd(&a.pcnt[ps], 1u);
+            const u64 pk = (u64)slot << 32 | (u64)(unsigned)id;
+            const long long ps = REMOVE ? dense_lookup(a.pkeys, a.P, pk) : dense_find(a.pkeys, a.P, pk, a.ctr, DC_PAIRS, a.max_pairs);
+            if (ps >= 0) { if (REMOVE) atomicSub(&a.pcnt[ps], 1u); else atomicAdd(&a.pcnt[ps], 1u); }
+            else if (REMOVE) miss = true;
           }
         }
       }
@@ -212,31 +250,46 @@ static __global__ __launch_bounds__(kDenseThreads) void k_dense_insert(DenseArgs
       s0 = dense_run_sum(s0, rid, lane); s1 = dense_run_sum(s1, rid, lane); s2 = dense_run_sum(s2, rid, lane);
       rgbc = dense_run_sum(rgbc, rid, lane);
       if (used && head) {
-        slot = dense_find(a.keys, a.H, key, a.ctr, DC_VOXELS, a.max_voxels);
+        slot = REMOVE ? dense_lookup(a.keys, a.H, key) : dense_find(a.keys, a.H, key, a.ctr, DC_VOXELS, a.max_voxels);
         if (slot >= 0) {
           DenseRec* r = a.rec + slot;
-          atomicAdd((u64*)&r->S[0], (u64)s0); atomicAdd((u64*)&r->S[1], (u64)s1); atomicAdd((u64*)&r->S[2], (u64)s2);
-          atomicAdd(&r->count, rgbc >> 48);
+          atomicAdd((u64*)&r->S[0], REMOVE ? 0ull - (u64)s0 : (u64)s0); atomicAdd((u64*)&r->S[1], REMOVE ? 0ull - (u64)s1 : (u64)s1);
+          atomicAdd((u64*)&r->S[2], REMOVE ? 0ull - (u64)s2 : (u64)s2);
+          atomicAdd(&r->count, REMOVE ? 0ull - (rgbc >> 48) : rgbc >> 48);
           if (a.bgr) {
-            atomicAdd(&r->col[0], rgbc & 0xFFFFull); atomicAdd(&r->col[1], (rgbc >> 16) & 0xFFFFull);
-            atomicAdd(&r->col[2], (rgbc >> 32) & 0xFFFFull);
+            atomicAdd(&r->col[0], REMOVE ? 0ull - (rgbc & 0xFFFFull) : rgbc & 0xFFFFull);
+            atomicAdd(&r->col[1], REMOVE ? 0ull - ((rgbc >> 16) & 0xFFFFull) : (rgbc >> 16) & 0xFFFFull);
+            atomicAdd(&r->col[2], REMOVE ? 0ull - ((rgbc >> 32) & 0xFFFFull) : (rgbc >> 32) & 0xFFFFull);
           }
         }
       }
-      if (a.pkeys) {   // workgroup-uniform
+      if (REMOVE || a.pkeys) {   // workgroup-uniform
         const int hl = 63 - __clzll((long long)(hm & le));   // the head of this lane's run; lane 0 is always a head
         const long long rslot = __shfl(slot, hl, 64);
-        const bool vused = used && id >= 0 && rslot >= 0;
-        const u64 vkey = vused ? ((u64)rslot << 32 | (u64)(unsigned)id) : kDenseEmpty;
-        const u64 vprev = __shfl_up(vkey, 1, 64);
-        const bool vhead = !vused || lane == 0 || vprev != vkey;
-        const int vrid = __popcll(__ballot(vhead) & le);
-        const int votes = dense_run_sum(vused ? 1 : 0, vrid, lane);
-        if (vused && vhead) {
-          const long long ps = dense_find(a.pkeys, a.P, vkey, a.ctr, DC_PAIRS, a.max_pairs);
-          if (ps >= 0) atomicAdd(&a.pcnt[ps], (unsigned)votes);
+        if (REMOVE) miss = used && rslot < 0;
+        if (a.pkeys) {
+          const bool vused = used && id >= 0 && rslot >= 0;
+          const u64 vkey = vused ? ((u64)rslot << 32 | (u64)(unsigned)id) : kDenseEmpty;
+          const u64 vprev = __shfl_up(vkey, 1, 64);
+          const bool vhead = !vused || lane == 0 || vprev != vkey;
+          const u64 vhm = __ballot(vhead);
+          const int vrid = __popcll(vhm & le);
+          const int votes = dense_run_sum(vused ? 1 : 0, vrid, lane);
+          long long ps = 0;
+          if (vused && vhead) {
+            ps = REMOVE ? dense_lookup(a.pkeys, a.P, vkey) : dense_find(a.pkeys, a.P, vkey, a.ctr, DC_PAIRS, a.max_pairs);
+            if (ps >= 0) { if (REMOVE) atomicSub(&a.pcnt[ps], (unsigned)votes); else atomicAdd(&a.pcnt[ps], (unsigned)votes); }
+          }
+          if (REMOVE) {   // every lane of a vote run whose head found no pair
+            const long long hps = __shfl(ps, 63 - __clzll((long long)(vhm & le)), 64);
+            miss = miss || (vused && hps < 0);
+          }
         }
       }
+    }
+    if (REMOVE) {
+      const u64 m_m = __ballot(miss);
+      if (lane == 0 && m_m) atomicAdd(&a.ctr[DC_MISSING], (u64)__popcll(m_m));
     }
   }
 }
@@ -256,8 +309,9 @@ static __global__ __launch_bounds__(kDenseThreads) void k_dense_compact(DenseOut
   const u64 i = (u64)blockIdx.x * kDenseThreads + threadIdx.x;
   u64 key = kDenseEmpty;
   if (i < a.H) key = a.keys[i];
-  const bool occ = key != kDenseEmpty;
+  bool occ = key != kDenseEmpty;
   if (occ) a.rec[i].best = 0;
+  occ = occ && a.rec[i].count != 0;   // a dead slot (step 9) keeps its key and is not listed
   const u64 m = __ballot(occ);
   u64 base = 0;
   if (lane == 0 && m) base = atomicAdd(&a.ctr[DC_LIST], (u64)__popcll(m));
@@ -274,7 +328,132 @@ static __global__ __launch_bounds__(kDenseThreads) void k_dense_vote(DenseOutArg
   const u64 key = a.pkeys[i];
   if (key == kDenseEmpty) return;
   const u64 slot = key >> 32;
-  if (slot < a.H) atomicMax(&a.rec[slot].best, (u64)a.pcnt[i] << 32 | (u64)(unsigned)~(unsigned)key);
+  const unsigned int votes = a.pcnt[i];
+  if (votes == 0) return;   // a dead pair casts no vote (0 << 32 | ~id would still be a non-zero best word)
+  if (slot < a.H) atomicMax(&a.rec[slot].best, (u64)votes << 32 | (u64)(unsigned)~(unsigned)key);
+}
+
+// Step 9's audit: one pass over the H voxel slots and the P pair slots, as at most kDenseAuditBlocks workgroups that stride over them.
+// A lane keeps its five counts in registers, a wave folds them by a butterfly, the waves meet in LDS and one lane per count emits the
+// workgroup's atomic.  live / dead: claimed slots with count > 0 / == 0.  bad: a voxel count negative as int64, a dead voxel with a
+// non-zero S_a or colour sum, a pair count with bit 31 set, a live pair whose voxel is dead (or past the table).
+constexpr int kDenseAuditBlocks = 1024;
+static __global__ __launch_bounds__(kDenseThreads) void k_dense_audit(DenseOutArgs a) {
+  __shared__ u64 part[kDenseThreads / 64][5];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const u64 n = a.pkeys ? (a.P > a.H ? a.P : a.H) : a.H, stride = (u64)gridDim.x * kDenseThreads;
+  u64 v[5] = {0, 0, 0, 0, 0};   // live voxels, dead voxels, live pairs, dead pairs, bad
+  for (u64 i = (u64)blockIdx.x * kDenseThreads + threadIdx.x; i < n; i += stride) {
+    if (i < a.H && a.keys[i] != kDenseEmpty) {
+      const DenseRec r = a.rec[i];
+      const long long cnt = (long long)r.count;
+      if (cnt > 0) ++v[0];
+      else if (cnt < 0) ++v[4];
+      else {
+        ++v[1];
+        if ((r.S[0] | r.S[1] | r.S[2]) != 0 || (r.col[0] | r.col[1] | r.col[2]) != 0) ++v[4];
+      }
+    }
+    if (a.pkeys && i < a.P) {
+      const u64 pk = a.pkeys[i];
+      if (pk != kDenseEmpty) {
+        const unsigned int pc = a.pcnt[i];
+        if (pc >> 31) ++v[4];
+        else if (pc == 0) ++v[3];
+        else {
+          ++v[2];
+          const u64 slot = pk >> 32;
+          if (slot >= a.H || a.rec[slot].count == 0) ++v[4];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+    for (int c = 0; c < 5; ++c) v[c] += __shfl_xor(v[c], off, 64);
+  }
+  if (lane == 0) {
+    for (int c = 0; c < 5; ++c) part[wave][c] = v[c];
+  }
+  __syncthreads();
+  if (threadIdx.x < 5) {
+    u64 t = 0;
+    for (int w = 0; w < kDenseThreads / 64; ++w) t += part[w][threadIdx.x];
+    if (t) atomicAdd(&a.ctr[DC_LIVE_V + threadIdx.x], t);
+  }
+}
+
+// esl_dense_purge (step 11).  k_dense_export appends the live records as (packed key, record) and the live pairs as (their voxel's
+// packed key, id, count), one atomic per wave and list; the host clears the tables; k_dense_reinsert claims a slot per record (the
+// keys are distinct: one CAS per probe, bounded by H) and stores it with vector stores; k_dense_reinsert_pairs, a launch later, looks
+// the voxel's new slot up and claims the pair's.  No thread waits for another.
+struct DensePurgeArgs {
+  u64* keys; DenseRec* rec; u64* pkeys; unsigned int* pcnt;
+  u64 H, P;
+  u64* ctr;
+  u64* xkey; DenseRec* xrec; u64 xv_cap;                          // the live records
+  u64* xpkey; unsigned int* xpid; unsigned int* xpcnt; u64 xp_cap;   // the live pairs
+};
+
+static __global__ __launch_bounds__(kDenseThreads) void k_dense_export(DensePurgeArgs a) {
+  const int lane = threadIdx.x & 63;
+  const u64 below = (1ull << lane) - 1ull;
+  const u64 i = (u64)blockIdx.x * kDenseThreads + threadIdx.x;
+  {
+    u64 key = kDenseEmpty;
+    if (i < a.H) key = a.keys[i];
+    const bool live = key != kDenseEmpty && a.rec[i].count != 0;
+    const u64 m = __ballot(live);
+    u64 base = 0;
+    if (lane == 0 && m) base = atomicAdd(&a.ctr[DC_XV], (u64)__popcll(m));
+    base = __shfl(base, 0, 64);
+    if (live) {
+      const u64 pos = base + (u64)__popcll(m & below);
+      if (pos < a.xv_cap) { a.xkey[pos] = key; a.xrec[pos] = a.rec[i]; }
+    }
+  }
+  if (a.pkeys) {   // workgroup-uniform
+    u64 pk = kDenseEmpty;
+    if (i < a.P) pk = a.pkeys[i];
+    const bool live = pk != kDenseEmpty && a.pcnt[i] != 0 && (pk >> 32) < a.H;
+    const u64 m = __ballot(live);
+    u64 base = 0;
+    if (lane == 0 && m) base = atomicAdd(&a.ctr[DC_XP], (u64)__popcll(m));
+    base = __shfl(base, 0, 64);
+    if (live) {
+      const u64 pos = base + (u64)__popcll(m & below);
+      if (pos < a.xp_cap) { a.xpkey[pos] = a.keys[pk >> 32]; a.xpid[pos] = (unsigned int)pk; a.xpcnt[pos] = a.pcnt[i]; }
+    }
+  }
+}
+
+// the slot claimed for `key`, which no other thread inserts, in an otherwise append-only table of n slots; -1 when none is free
+__device__ __forceinline__ long long dense_claim(u64* keys, u64 n, u64 key) {
+  u64 slot = dense_hash(key) & (n - 1);
+  for (u64 it = 0; it < n; ++it) {
+    if (atomicCAS(&keys[slot], kDenseEmpty, key) == kDenseEmpty) return (long long)slot;
+    slot = (slot + 1) & (n - 1);
+  }
+  return -1;
+}
+
+static __global__ __launch_bounds__(kDenseThreads) void k_dense_reinsert(DensePurgeArgs a) {
+  const u64 i = (u64)blockIdx.x * kDenseThreads + threadIdx.x;
+  const u64 nv = a.ctr[DC_XV] < a.xv_cap ? a.ctr[DC_XV] : a.xv_cap;
+  if (i >= nv) return;
+  const long long slot = dense_claim(a.keys, a.H, a.xkey[i]);
+  if (slot >= 0) a.rec[slot] = a.xrec[i];
+}
+
+static __global__ __launch_bounds__(kDenseThreads) void k_dense_reinsert_pairs(DensePurgeArgs a) {
+  const u64 i = (u64)blockIdx.x * kDenseThreads + threadIdx.x;
+  const u64 np = a.ctr[DC_XP] < a.xp_cap ? a.ctr[DC_XP] : a.xp_cap;
+  if (i >= np) return;
+  const long long slot = dense_lookup(a.keys, a.H, a.xpkey[i]);
+  if (slot < 0) return;
+  const long long ps = dense_claim(a.pkeys, a.P, (u64)slot << 32 | (u64)a.xpid[i]);
+  if (ps >= 0) a.pcnt[ps] = a.xpcnt[i];
 }
 
 static __global__ __launch_bounds__(kDenseThreads) void k_dense_gather(DenseOutArgs a) {
@@ -405,7 +584,10 @@ static __global__ __launch_bounds__(kDenseThreads) void k_dobj_union(DobjArgs a)
     int j = -1;
     for (u64 it = 0; it < a.H; ++it) {   // the table is read-only in this launch: cached loads
       const u64 cur = a.keys[slot];
-      if (cur == key) { j = a.sidx[slot]; break; }
+      if (cur == key) {   // a dead slot (dense-map step 9) is no neighbour: it is not in the list and its sidx is stale
+        if (a.rec[slot].count != 0) j = a.sidx[slot];
+        break;
+      }
       if (cur == kDenseEmpty) break;
       slot = (slot + 1) & (a.H - 1);
     }
@@ -864,7 +1046,7 @@ extern "C" int esl_dense_begin(esl_ctx* c, const esl_dense_params* pp, int32_t w
   const char* ev = std::getenv("ESL_DENSE_COMBINE");
   d.combine = !(ev && ev[0] == '0');
   d.p = p; d.with_color = with_color != 0; d.with_inst = with_inst != 0; d.H = H;
-  d.n_samples = 0; d.n_voxels = 0; d.n_pairs = 0; d.status = 0;
+  d.n_samples = 0; d.n_voxels = 0; d.n_pairs = 0; d.dead_voxels = 0; d.dead_pairs = 0; d.status = 0;
   d.begun = true;
   return ESL_OK;
 }
@@ -887,9 +1069,12 @@ extern "C" int esl_dense_info_get(esl_ctx* c, esl_dense_info* out) {
   return ESL_OK;
 }
 
-extern "C" int esl_dense_add_frames(esl_ctx* c, const double* cams, int32_t F, const double K[4], int32_t rows, int32_t cols,
-                                    const uint16_t* depth, const uint8_t* bgr, const int32_t* inst, esl_dense_add_result* out) {
-  const char* who = "esl_dense_add_frames";
+namespace {
+
+// what esl_dense_add_frames, _remove_frames and _move_frames check alike, case by case and in this order; res_cams: the poses (of
+// _move_frames: the new ones) are the resident camera states
+int dense_frames_check(esl_ctx* c, const char* who, int32_t F, const double K[4], int32_t rows, int32_t cols, const uint16_t* depth,
+                       const uint8_t* bgr, const int32_t* inst, bool res_cams) {
   if (!c) return dense_fail(ESL_ERR_INVALID, who, "null ctx");
   if (F < 0) return dense_fail(ESL_ERR_INVALID, who, "negative F");
   if (!K) return dense_fail(ESL_ERR_INVALID, who, "null K");
@@ -902,58 +1087,266 @@ extern "C" int esl_dense_add_frames(esl_ctx* c, const double* cams, int32_t F, c
   DenseState& d = *c->dense;
   if (F > 0 && d.with_color && !bgr) return dense_fail(ESL_ERR_STATE, who, "null bgr on a map begun with colour");
   if (F > 0 && d.with_inst && !inst) return dense_fail(ESL_ERR_STATE, who, "null inst on a map begun with labels");
-  if (const int rc = resident_source_check(c, who, !cams && F > 0, F, false, 0)) return rc;
-  if (out) { std::memset(out, 0, sizeof(*out)); out->status = d.status; }
-  if (F == 0 || d.status) return ESL_OK;   // nothing to add; or over capacity: nothing more is added until the next esl_dense_begin
-  ESL_HIP_TRY(hipSetDevice(c->device));
-  // the poses: R and t of every frame on the host, before anything is added
-  d.cams.resize((size_t)F * 7);
-  if (cams) std::memcpy(d.cams.data(), cams, (size_t)F * 7 * sizeof(double));
+  return resident_source_check(c, who, res_cams && F > 0, F, false, 0);
+}
+
+// step 2 on the host: R and t of every frame, from the given poses or the resident camera states
+int dense_frames_poses(esl_ctx* c, const char* who, const double* cams, int F, std::vector<double>& host, std::vector<double>& pose) {
+  host.resize((size_t)F * 7);
+  if (cams) std::memcpy(host.data(), cams, (size_t)F * 7 * sizeof(double));
   else {
-    ESL_HIP_TRY(hipMemcpyAsync(d.cams.data(), c->cams, (size_t)F * 7 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    ESL_HIP_TRY(hipMemcpyAsync(host.data(), c->cams, (size_t)F * 7 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     ESL_HIP_TRY(hipStreamSynchronize(c->stream));
   }
-  d.pose.resize((size_t)F * kDensePose);
+  pose.resize((size_t)F * kDensePose);
   for (int f = 0; f < F; ++f) {
-    if (!dense_pose(d.cams.data() + (size_t)f * 7, d.pose.data() + (size_t)f * kDensePose))
+    if (!dense_pose(host.data() + (size_t)f * 7, pose.data() + (size_t)f * kDensePose))
       return dense_fail(ESL_ERR_INVALID, who, "a pose with a non-finite number or a quaternion of norm 0");
   }
-  const int srows = (rows + d.p.stride - 1) / d.p.stride, scols = (cols + d.p.stride - 1) / d.p.stride;
-  const long long per = (long long)srows * scols;
-  if (d.n_samples + per * F >= (1ll << 31)) return dense_fail(ESL_ERR_INVALID, who, "n_samples would reach 2^31");
+  return ESL_OK;
+}
+
+long long dense_per_frame(const DenseState& d, int rows, int cols) {
+  return (long long)((rows + d.p.stride - 1) / d.p.stride) * ((cols + d.p.stride - 1) / d.p.stride);
+}
+
+// the kernel's arguments but the poses and the images
+void dense_frames_args(DenseState& d, DenseArgs& k, int F, const double K[4], int rows, int cols) {
   ScratchSet<DB_COUNT>& s = d.set;
-  const size_t n_img = (size_t)F * rows * cols;
-  DenseArgs k;
   std::memset(&k, 0, sizeof(k));
-  if (const int rc = upload(c, s, DB_POSE, (const double*)d.pose.data(), (size_t)F * kDensePose * sizeof(double), &k.pose)) return rc;
-  if (const int rc = upload(c, s, DB_DEPTH, depth, n_img * sizeof(uint16_t), &k.depth)) return rc;
-  if (d.with_color) { if (const int rc = upload(c, s, DB_BGR, bgr, n_img * 3, &k.bgr)) return rc; }
-  if (d.with_inst) { if (const int rc = upload(c, s, DB_INST, inst, n_img * sizeof(int32_t), &k.inst)) return rc; }
-  k.F = F; k.rows = rows; k.cols = cols; k.stride = d.p.stride; k.srows = srows; k.scols = scols;
+  k.F = F; k.rows = rows; k.cols = cols; k.stride = d.p.stride;
+  k.srows = (rows + d.p.stride - 1) / d.p.stride; k.scols = (cols + d.p.stride - 1) / d.p.stride;
   for (int i = 0; i < 4; ++i) k.K[i] = K[i];
   k.leaf = d.p.leaf; k.depth_scale = d.p.depth_scale; k.depth_min = d.p.depth_min; k.depth_max = d.p.depth_max;
   k.keys = s.at<u64>(DB_KEYS); k.rec = s.at<DenseRec>(DB_REC);
   if (d.with_inst) { k.pkeys = s.at<u64>(DB_PKEYS); k.pcnt = s.at<unsigned int>(DB_PCNT); }
   k.H = d.H; k.P = 2 * d.H; k.max_voxels = (u64)d.p.max_voxels; k.max_pairs = 2 * (u64)d.p.max_voxels;
   k.ctr = s.at<u64>(DB_CTR);
+}
+
+// One pass of k_dense_insert over the frames of `k`, adding or removing, and what it means for the map.  k_dense_audit follows every
+// removal, and an add while the map holds dead slots (a revived slot is no new claim: the claim counters no longer count the live
+// ones); otherwise n_voxels and n_pairs come from the claim counters.  ctr: the device counters after the pass.
+int dense_pass(esl_ctx* c, DenseState& d, const DenseArgs& k, bool remove, u64 ctr[DC_COUNT]) {
+  const bool audit = remove || d.dead_voxels > 0 || d.dead_pairs > 0;
   ESL_HIP_TRY(hipMemsetAsync(k.ctr, 0, 5 * sizeof(u64), c->stream));   // this call's counts
+  if (remove) ESL_HIP_TRY(hipMemsetAsync(k.ctr + DC_MISSING, 0, sizeof(u64), c->stream));
+  if (audit) ESL_HIP_TRY(hipMemsetAsync(k.ctr + DC_LIVE_V, 0, 5 * sizeof(u64), c->stream));
   {
     ProfScope ps(c, 4);
-    const dim3 grid(dense_blocks((u64)per), (unsigned)std::min(F, 65535));
-    if (d.combine) hipLaunchKernelGGL(k_dense_insert<true>, grid, dim3(kDenseThreads), 0, c->stream, k);
-    else hipLaunchKernelGGL(k_dense_insert<false>, grid, dim3(kDenseThreads), 0, c->stream, k);
+    const dim3 grid(dense_blocks((u64)k.srows * (u64)k.scols), (unsigned)std::min(k.F, 65535));
+    if (remove) {
+      if (d.combine) hipLaunchKernelGGL((k_dense_insert<true, true>), grid, dim3(kDenseThreads), 0, c->stream, k);
+      else hipLaunchKernelGGL((k_dense_insert<false, true>), grid, dim3(kDenseThreads), 0, c->stream, k);
+    } else {
+      if (d.combine) hipLaunchKernelGGL((k_dense_insert<true, false>), grid, dim3(kDenseThreads), 0, c->stream, k);
+      else hipLaunchKernelGGL((k_dense_insert<false, false>), grid, dim3(kDenseThreads), 0, c->stream, k);
+    }
+    if (audit) {
+      DenseOutArgs o;
+      std::memset(&o, 0, sizeof(o));
+      o.keys = k.keys; o.rec = k.rec; o.pkeys = k.pkeys; o.pcnt = k.pcnt; o.H = k.H; o.P = k.P; o.ctr = k.ctr;
+      const u64 n = k.pkeys ? k.P : k.H;
+      hipLaunchKernelGGL(k_dense_audit, dim3(std::min<unsigned>(dense_blocks(n), kDenseAuditBlocks)), dim3(kDenseThreads), 0, c->stream, o);
+    }
   }
   ESL_HIP_TRY(hipGetLastError());
-  u64 ctr[DC_COUNT];
-  ESL_HIP_TRY(hipMemcpyAsync(ctr, k.ctr, sizeof(ctr), hipMemcpyDeviceToHost, c->stream));
+  ESL_HIP_TRY(hipMemcpyAsync(ctr, k.ctr, DC_COUNT * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
   ESL_HIP_TRY(hipStreamSynchronize(c->stream));   // the caller's arrays are free again
-  d.n_samples += (long long)ctr[DC_USED];
-  d.n_voxels = (long long)ctr[DC_VOXELS]; d.n_pairs = (long long)ctr[DC_PAIRS];
-  d.status = ctr[DC_STATUS] ? 3 : 0;
-  if (out) {
-    out->n_sampled = (int64_t)ctr[DC_SAMPLED]; out->n_zero = (int64_t)ctr[DC_ZERO]; out->n_depth_out = (int64_t)ctr[DC_DEPTH_OUT];
-    out->n_key_out = (int64_t)ctr[DC_KEY_OUT]; out->n_used = (int64_t)ctr[DC_USED]; out->status = d.status; out->pad = 0;
+  if (remove) d.n_samples -= (long long)ctr[DC_USED]; else d.n_samples += (long long)ctr[DC_USED];
+  if (audit) {
+    d.n_voxels = (long long)ctr[DC_LIVE_V]; d.n_pairs = (long long)ctr[DC_LIVE_P];
+    d.dead_voxels = (long long)ctr[DC_DEAD_V]; d.dead_pairs = (long long)ctr[DC_DEAD_P];
+  } else {
+    d.n_voxels = (long long)ctr[DC_VOXELS]; d.n_pairs = (long long)ctr[DC_PAIRS];
   }
+  d.status = ctr[DC_STATUS] ? 3 : (audit && (ctr[DC_BAD] || (remove && ctr[DC_MISSING]))) ? 4 : 0;
+  return ESL_OK;
+}
+
+void dense_add_counts(const u64 ctr[DC_COUNT], int status, esl_dense_add_result* out) {
+  out->n_sampled = (int64_t)ctr[DC_SAMPLED]; out->n_zero = (int64_t)ctr[DC_ZERO]; out->n_depth_out = (int64_t)ctr[DC_DEPTH_OUT];
+  out->n_key_out = (int64_t)ctr[DC_KEY_OUT]; out->n_used = (int64_t)ctr[DC_USED]; out->status = status; out->pad = 0;
+}
+
+void dense_remove_counts(const u64 ctr[DC_COUNT], long long emptied, int status, esl_dense_remove_result* out) {
+  out->n_sampled = (int64_t)ctr[DC_SAMPLED]; out->n_zero = (int64_t)ctr[DC_ZERO]; out->n_depth_out = (int64_t)ctr[DC_DEPTH_OUT];
+  out->n_key_out = (int64_t)ctr[DC_KEY_OUT]; out->n_used = (int64_t)ctr[DC_USED]; out->n_missing = (int64_t)ctr[DC_MISSING];
+  out->n_emptied = emptied; out->status = status; out->pad = 0;
+}
+
+void dense_slots_of(const DenseState& d, esl_dense_slots* out) {
+  if (d.status) { out->voxel_slots = out->dead_voxels = out->pair_slots = out->dead_pairs = -1; return; }
+  out->voxel_slots = d.n_voxels + d.dead_voxels; out->dead_voxels = d.dead_voxels;
+  out->pair_slots = d.n_pairs + d.dead_pairs; out->dead_pairs = d.dead_pairs;
+}
+
+}  // namespace
+
+extern "C" int esl_dense_add_frames(esl_ctx* c, const double* cams, int32_t F, const double K[4], int32_t rows, int32_t cols,
+                                    const uint16_t* depth, const uint8_t* bgr, const int32_t* inst, esl_dense_add_result* out) {
+  const char* who = "esl_dense_add_frames";
+  if (const int rc = dense_frames_check(c, who, F, K, rows, cols, depth, bgr, inst, !cams)) return rc;
+  DenseState& d = *c->dense;
+  if (out) { std::memset(out, 0, sizeof(*out)); out->status = d.status; }
+  if (F == 0 || d.status) return ESL_OK;   // nothing to add; or an invalid map: nothing more is added until the next esl_dense_begin
+  ESL_HIP_TRY(hipSetDevice(c->device));
+  // the poses: R and t of every frame on the host, before anything is added
+  if (const int rc = dense_frames_poses(c, who, cams, F, d.cams, d.pose)) return rc;
+  if (d.n_samples + dense_per_frame(d, rows, cols) * F >= (1ll << 31)) return dense_fail(ESL_ERR_INVALID, who, "n_samples would reach 2^31");
+  ScratchSet<DB_COUNT>& s = d.set;
+  const size_t n_img = (size_t)F * rows * cols;
+  DenseArgs k;
+  dense_frames_args(d, k, F, K, rows, cols);
+  if (const int rc = upload(c, s, DB_POSE, (const double*)d.pose.data(), (size_t)F * kDensePose * sizeof(double), &k.pose)) return rc;
+  if (const int rc = upload(c, s, DB_DEPTH, depth, n_img * sizeof(uint16_t), &k.depth)) return rc;
+  if (d.with_color) { if (const int rc = upload(c, s, DB_BGR, bgr, n_img * 3, &k.bgr)) return rc; }
+  if (d.with_inst) { if (const int rc = upload(c, s, DB_INST, inst, n_img * sizeof(int32_t), &k.inst)) return rc; }
+  u64 ctr[DC_COUNT];
+  if (const int rc = dense_pass(c, d, k, false, ctr)) return rc;
+  if (out) dense_add_counts(ctr, d.status, out);
+  return ESL_OK;
+}
+
+extern "C" int esl_dense_remove_frames(esl_ctx* c, const double* cams, int32_t F, const double K[4], int32_t rows, int32_t cols,
+                                       const uint16_t* depth, const uint8_t* bgr, const int32_t* inst, esl_dense_remove_result* out) {
+  const char* who = "esl_dense_remove_frames";
+  if (const int rc = dense_frames_check(c, who, F, K, rows, cols, depth, bgr, inst, !cams)) return rc;
+  DenseState& d = *c->dense;
+  if (out) { std::memset(out, 0, sizeof(*out)); out->status = d.status; }
+  if (F == 0 || d.status) return ESL_OK;   // nothing to remove; or an invalid map: nothing more is removed until the next esl_dense_begin
+  ESL_HIP_TRY(hipSetDevice(c->device));
+  if (const int rc = dense_frames_poses(c, who, cams, F, d.cams, d.pose)) return rc;
+  if (dense_per_frame(d, rows, cols) * F >= (1ll << 31)) return dense_fail(ESL_ERR_INVALID, who, "more samples than a map holds: 2^31");
+  ScratchSet<DB_COUNT>& s = d.set;
+  const size_t n_img = (size_t)F * rows * cols;
+  DenseArgs k;
+  dense_frames_args(d, k, F, K, rows, cols);
+  if (const int rc = upload(c, s, DB_POSE, (const double*)d.pose.data(), (size_t)F * kDensePose * sizeof(double), &k.pose)) return rc;
+  if (const int rc = upload(c, s, DB_DEPTH, depth, n_img * sizeof(uint16_t), &k.depth)) return rc;
+  if (d.with_color) { if (const int rc = upload(c, s, DB_BGR, bgr, n_img * 3, &k.bgr)) return rc; }
+  if (d.with_inst) { if (const int rc = upload(c, s, DB_INST, inst, n_img * sizeof(int32_t), &k.inst)) return rc; }
+  const long long dead_before = d.dead_voxels;
+  u64 ctr[DC_COUNT];
+  if (const int rc = dense_pass(c, d, k, true, ctr)) return rc;
+  if (out) dense_remove_counts(ctr, d.dead_voxels - dead_before, d.status, out);
+  return ESL_OK;
+}
+
+extern "C" int esl_dense_move_frames(esl_ctx* c, const double* cams_old, const double* cams_new, int32_t F, const double K[4], int32_t rows,
+                                     int32_t cols, const uint16_t* depth, const uint8_t* bgr, const int32_t* inst,
+                                     esl_dense_move_result* out) {
+  const char* who = "esl_dense_move_frames";
+  if (c && F > 0 && !cams_old) return dense_fail(ESL_ERR_INVALID, who, "null cams_old");
+  if (const int rc = dense_frames_check(c, who, F, K, rows, cols, depth, bgr, inst, !cams_new)) return rc;
+  DenseState& d = *c->dense;
+  if (out) { std::memset(out, 0, sizeof(*out)); out->removed.status = out->added.status = d.status; }
+  if (F == 0 || d.status) return ESL_OK;
+  ESL_HIP_TRY(hipSetDevice(c->device));
+  // every check before anything changes: all poses of both sets, then the frames that move and the samples they could add
+  if (const int rc = dense_frames_poses(c, who, cams_new, F, d.cams2, d.pose2)) return rc;
+  if (const int rc = dense_frames_poses(c, who, cams_old, F, d.cams, d.pose)) return rc;
+  d.moved.clear();
+  for (int f = 0; f < F; ++f) {
+    if (std::memcmp(d.cams.data() + (size_t)f * 7, d.cams2.data() + (size_t)f * 7, 7 * sizeof(double)) != 0) d.moved.push_back(f);
+  }
+  const int Fm = (int)d.moved.size();
+  if (d.n_samples + dense_per_frame(d, rows, cols) * Fm >= (1ll << 31)) return dense_fail(ESL_ERR_INVALID, who, "n_samples would reach 2^31");
+  if (out) { out->n_frames_moved = Fm; out->n_frames_same = F - Fm; }
+  if (Fm == 0) return ESL_OK;
+  // the moved frames' poses and images, packed in their order and uploaded once
+  for (int m = 0; m < Fm; ++m) {
+    const size_t f = (size_t)d.moved[(size_t)m];
+    if (f == (size_t)m) continue;
+    std::memmove(d.pose.data() + (size_t)m * kDensePose, d.pose.data() + f * kDensePose, kDensePose * sizeof(double));
+    std::memmove(d.pose2.data() + (size_t)m * kDensePose, d.pose2.data() + f * kDensePose, kDensePose * sizeof(double));
+  }
+  ScratchSet<DB_COUNT>& s = d.set;
+  const size_t px = (size_t)rows * cols, n_img = (size_t)Fm * px;
+  DenseArgs k;
+  dense_frames_args(d, k, Fm, K, rows, cols);
+  const double* pose_new = nullptr;
+  if (const int rc = upload(c, s, DB_POSE, (const double*)d.pose.data(), (size_t)Fm * kDensePose * sizeof(double), &k.pose)) return rc;
+  if (const int rc = upload(c, s, DB_POSE2, (const double*)d.pose2.data(), (size_t)Fm * kDensePose * sizeof(double), &pose_new)) return rc;
+  if (const int rc = s.grow(c, DB_DEPTH, n_img * sizeof(uint16_t))) return rc;
+  if (d.with_color) { if (const int rc = s.grow(c, DB_BGR, n_img * 3)) return rc; }
+  if (d.with_inst) { if (const int rc = s.grow(c, DB_INST, n_img * sizeof(int32_t))) return rc; }
+  for (int m = 0; m < Fm;) {   // one copy per run of consecutive frames
+    int e = m + 1;
+    while (e < Fm && d.moved[(size_t)e] == d.moved[(size_t)e - 1] + 1) ++e;
+    const size_t f = (size_t)d.moved[(size_t)m], cnt = (size_t)(e - m) * px;
+    ESL_HIP_TRY(hipMemcpyAsync(s.at<uint16_t>(DB_DEPTH) + (size_t)m * px, depth + f * px, cnt * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+    if (d.with_color) ESL_HIP_TRY(hipMemcpyAsync(s.at<uint8_t>(DB_BGR) + (size_t)m * px * 3, bgr + f * px * 3, cnt * 3, hipMemcpyHostToDevice, c->stream));
+    if (d.with_inst) ESL_HIP_TRY(hipMemcpyAsync(s.at<int32_t>(DB_INST) + (size_t)m * px, inst + f * px, cnt * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    m = e;
+  }
+  k.depth = s.at<unsigned short>(DB_DEPTH);
+  if (d.with_color) k.bgr = s.at<unsigned char>(DB_BGR);
+  if (d.with_inst) k.inst = s.at<int>(DB_INST);
+  const long long dead_before = d.dead_voxels;
+  u64 ctr[DC_COUNT];
+  if (const int rc = dense_pass(c, d, k, true, ctr)) return rc;
+  if (out) dense_remove_counts(ctr, d.dead_voxels - dead_before, d.status, &out->removed);
+  if (d.status) {   // the removal left an inconsistent map: nothing is added
+    if (out) out->added.status = d.status;
+    return ESL_OK;
+  }
+  k.pose = pose_new;
+  if (const int rc = dense_pass(c, d, k, false, ctr)) return rc;
+  if (out) dense_add_counts(ctr, d.status, &out->added);
+  return ESL_OK;
+}
+
+extern "C" int esl_dense_slots_get(esl_ctx* c, esl_dense_slots* out) {
+  const char* who = "esl_dense_slots_get";
+  if (!c || !out) return dense_fail(ESL_ERR_INVALID, who, "null pointer");
+  if (!c->dense || !c->dense->begun) return dense_fail(ESL_ERR_STATE, who, "no esl_dense_begin before");
+  dense_slots_of(*c->dense, out);
+  return ESL_OK;
+}
+
+extern "C" int esl_dense_purge(esl_ctx* c, esl_dense_slots* before, esl_dense_slots* after) {
+  const char* who = "esl_dense_purge";
+  if (!c) return dense_fail(ESL_ERR_INVALID, who, "null ctx");
+  if (!c->dense || !c->dense->begun) return dense_fail(ESL_ERR_STATE, who, "no esl_dense_begin before");
+  DenseState& d = *c->dense;
+  if (before) dense_slots_of(d, before);
+  if (after) dense_slots_of(d, after);
+  if (d.status || (d.dead_voxels == 0 && d.dead_pairs == 0)) return ESL_OK;   // an invalid map is left alone; nothing dead: nothing to do
+  ESL_HIP_TRY(hipSetDevice(c->device));
+  ScratchSet<DB_COUNT>& s = d.set;
+  const size_t nv = (size_t)d.n_voxels, np = d.with_inst ? (size_t)d.n_pairs : 0, H = (size_t)d.H;
+  if (const int rc = s.grow(c, DB_XKEY, nv * sizeof(u64))) return rc;
+  if (const int rc = s.grow(c, DB_XREC, nv * sizeof(DenseRec))) return rc;
+  if (const int rc = s.grow(c, DB_XPKEY, np * sizeof(u64))) return rc;
+  if (const int rc = s.grow(c, DB_XPID, np * sizeof(unsigned int))) return rc;
+  if (const int rc = s.grow(c, DB_XPCNT, np * sizeof(unsigned int))) return rc;
+  DensePurgeArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.keys = s.at<u64>(DB_KEYS); a.rec = s.at<DenseRec>(DB_REC);
+  if (d.with_inst) { a.pkeys = s.at<u64>(DB_PKEYS); a.pcnt = s.at<unsigned int>(DB_PCNT); }
+  a.H = d.H; a.P = 2 * d.H; a.ctr = s.at<u64>(DB_CTR);
+  a.xkey = s.at<u64>(DB_XKEY); a.xrec = s.at<DenseRec>(DB_XREC); a.xv_cap = (u64)nv;
+  a.xpkey = s.at<u64>(DB_XPKEY); a.xpid = s.at<unsigned int>(DB_XPID); a.xpcnt = s.at<unsigned int>(DB_XPCNT); a.xp_cap = (u64)np;
+  const u64 claimed[2] = {(u64)nv, (u64)np};   // DC_VOXELS, DC_PAIRS: afterwards claimed = live
+  ESL_HIP_TRY(hipMemsetAsync(a.ctr + DC_XV, 0, 2 * sizeof(u64), c->stream));
+  {
+    ProfScope ps(c, 4);
+    hipLaunchKernelGGL(k_dense_export, dim3(dense_blocks(d.with_inst ? a.P : a.H)), dim3(kDenseThreads), 0, c->stream, a);
+    ESL_HIP_TRY(hipMemsetAsync(s.buf[DB_KEYS], 0xFF, H * sizeof(u64), c->stream));
+    ESL_HIP_TRY(hipMemsetAsync(s.buf[DB_REC], 0, H * sizeof(DenseRec), c->stream));
+    if (d.with_inst) {
+      ESL_HIP_TRY(hipMemsetAsync(s.buf[DB_PKEYS], 0xFF, 2 * H * sizeof(u64), c->stream));
+      ESL_HIP_TRY(hipMemsetAsync(s.buf[DB_PCNT], 0, 2 * H * sizeof(unsigned int), c->stream));
+    }
+    if (nv) hipLaunchKernelGGL(k_dense_reinsert, dim3(dense_blocks((u64)nv)), dim3(kDenseThreads), 0, c->stream, a);
+    if (np) hipLaunchKernelGGL(k_dense_reinsert_pairs, dim3(dense_blocks((u64)np)), dim3(kDenseThreads), 0, c->stream, a);
+  }
+  ESL_HIP_TRY(hipGetLastError());
+  ESL_HIP_TRY(hipMemcpyAsync(a.ctr + DC_VOXELS, claimed, sizeof(claimed), hipMemcpyHostToDevice, c->stream));
+  ESL_HIP_TRY(hipStreamSynchronize(c->stream));
+  d.dead_voxels = 0; d.dead_pairs = 0;
+  if (after) dense_slots_of(d, after);
   return ESL_OK;
 }
 
@@ -965,7 +1358,7 @@ extern "C" int esl_dense_extract(esl_ctx* c, int64_t cap, int32_t* key_out, doub
   if (!n_voxels) return dense_fail(ESL_ERR_INVALID, who, "null n_voxels");
   if (!c->dense || !c->dense->begun) return dense_fail(ESL_ERR_STATE, who, "no esl_dense_begin before");
   DenseState& d = *c->dense;
-  if (d.status) { *n_voxels = -1; return ESL_OK; }   // over capacity: the map is invalid, nothing is written
+  if (d.status) { *n_voxels = -1; return ESL_OK; }   // over capacity or inconsistent: the map is invalid, nothing is written
   *n_voxels = d.n_voxels;
   const long long n = d.n_voxels, nw = std::min<long long>(n, cap);
   const bool any = key_out || xyz_out || count_out || bgr_out || inst_out || votes_out;
@@ -1034,7 +1427,7 @@ extern "C" int esl_dense_objects(esl_ctx* c, int32_t N, const double ground_worl
   DenseState& d = *c->dense;
   if (!d.with_inst) return dense_fail(ESL_ERR_STATE, who, "the map was begun without labels");
   std::memset(out, 0, sizeof(*out));
-  if (d.status) { out->status = 3; out->n_voxels = -1; return ESL_OK; }   // over capacity: the map is invalid, nothing is written
+  if (d.status) { out->status = d.status; out->n_voxels = -1; return ESL_OK; }   // over capacity or inconsistent: the map is invalid, nothing is written
   const long long n = d.n_voxels;
   const long long n_comp_w_max = comp_cap, n_vox_w = std::min<long long>(n, voxel_cap);
   out->n_voxels = (int32_t)n;
@@ -1259,7 +1652,7 @@ extern "C" int esl_dense_planes(esl_ctx* c, const esl_dense_plane_params* pp, do
   if (!c->dense || !c->dense->begun) return dense_fail(ESL_ERR_STATE, who, "no esl_dense_begin before");
   DenseState& d = *c->dense;
   std::memset(out, 0, sizeof(*out));
-  if (d.status) { out->status = 3; out->n_voxels = -1; return ESL_OK; }   // over capacity: the map is invalid, nothing is written
+  if (d.status) { out->status = d.status; out->n_voxels = -1; return ESL_OK; }   // over capacity or inconsistent: the map is invalid, nothing is written
   const long long n = d.n_voxels, n_vox_w = std::min<long long>(n, voxel_cap);
   const int Hn = p.n_hypotheses, P = p.max_planes;
   out->n_voxels = (int32_t)n; out->ground_index = -1; out->stop_reason = 1;

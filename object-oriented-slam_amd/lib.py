@@ -32,6 +32,7 @@ EXPORTS = [
     "esl_dense_params_default", "esl_dense_begin", "esl_dense_add_frames", "esl_dense_info_get", "esl_dense_extract", "esl_dense_end",
     "esl_debug_dense_allocs", "esl_dense_obj_params_default", "esl_dense_objects",
     "esl_dense_plane_params_default", "esl_dense_planes", "esl_debug_dense_planes_layout",
+    "esl_dense_remove_frames", "esl_dense_move_frames", "esl_dense_slots_get", "esl_dense_purge",
 ]
 
 
@@ -758,12 +759,16 @@ class Context:
     def dense_add_frames(self, cams, K, rows, cols, depth, bgr=None, inst=None):
         """esl_dense_add_frames: add F frames.  cams (F, 7) Tcw or None for the resident camera states; depth (F, rows, cols) uint16,
         bgr (F, rows, cols, 3) uint8, inst (F, rows, cols) int32 (< 0 = unlabelled).  Returns the call's counts as a dict."""
+        return self._dense_frames("esl_dense_add_frames", abi.EslDenseAddResult(), (cams,), K, rows, cols, depth, bgr, inst)
+
+    def _dense_frames(self, name, res, cam_sets, K, rows, cols, depth, bgr, inst):
+        """the frame calls of the dense map: cam_sets = the call's pose arrays, the last of which may be None (the resident states)"""
         rows, cols = int(rows), int(cols)
-        if cams is None:
-            F, cp = self.graph_sizes()["n_cams"], None
-        else:
-            cams = np.ascontiguousarray(cams, dtype=np.float64).reshape(-1, 7)
-            F, cp = len(cams), (cams.ctypes.data_as(_dp) if len(cams) else None)
+        sets = [None if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 7) for a in cam_sets]
+        F = self.graph_sizes()["n_cams"] if sets[-1] is None else len(sets[-1])
+        if any(a is not None and len(a) != F for a in sets):
+            raise ValueError("the pose sets differ in length")
+        cps = [a.ctypes.data_as(_dp) if a is not None and len(a) else None for a in sets]
 
         def img(a, dt, t, tail=()):
             if a is None:
@@ -776,12 +781,38 @@ class Context:
         bgr, bptr = img(bgr, np.uint8, C.POINTER(C.c_uint8), (3,))
         inst, iptr = img(inst, np.int32, C.POINTER(C.c_int32))
         Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(4)
-        res = abi.EslDenseAddResult()
         t0 = time.perf_counter()
-        rc = load().esl_dense_add_frames(self._h, cp, F, Kc.ctypes.data_as(_dp), rows, cols, dptr, bptr, iptr, C.byref(res))
+        rc = getattr(load(), name)(self._h, *cps, F, Kc.ctypes.data_as(_dp), rows, cols, dptr, bptr, iptr, C.byref(res))
         self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
-        _check(rc, "esl_dense_add_frames")
+        _check(rc, name)
         return res.as_dict()
+
+    def dense_remove_frames(self, cams, K, rows, cols, depth, bgr=None, inst=None):
+        """esl_dense_remove_frames: subtract F frames, given exactly as they were added (cams None = the resident camera states).
+        Returns the call's counts as a dict, n_missing and n_emptied among them; status 4 = the map is inconsistent."""
+        return self._dense_frames("esl_dense_remove_frames", abi.EslDenseRemoveResult(), (cams,), K, rows, cols, depth, bgr, inst)
+
+    def dense_move_frames(self, cams_old, cams_new, K, rows, cols, depth, bgr=None, inst=None):
+        """esl_dense_move_frames: remove the frames with cams_old and add them with cams_new (None = the resident camera states) in one
+        call; frames whose pose did not change in any bit are skipped.  Returns dict(removed, added, n_frames_moved, n_frames_same)."""
+        if cams_old is None:
+            raise ValueError("cams_old may not be None")
+        return self._dense_frames("esl_dense_move_frames", abi.EslDenseMoveResult(), (cams_old, cams_new), K, rows, cols, depth, bgr, inst)
+
+    def dense_slots(self):
+        """esl_dense_slots_get as a dict: voxel_slots, dead_voxels, pair_slots, dead_pairs (claimed slots and the dead among them)"""
+        out = abi.EslDenseSlots()
+        _check(load().esl_dense_slots_get(self._h, C.byref(out)), "esl_dense_slots_get")
+        return out.as_dict()
+
+    def dense_purge(self):
+        """esl_dense_purge: rebuild the tables from the live voxels and pairs.  Returns (slots before, slots after) as dicts."""
+        b, a = abi.EslDenseSlots(), abi.EslDenseSlots()
+        t0 = time.perf_counter()
+        rc = load().esl_dense_purge(self._h, C.byref(b), C.byref(a))
+        self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
+        _check(rc, "esl_dense_purge")
+        return b.as_dict(), a.as_dict()
 
     def dense_info(self):
         """esl_dense_info_get as a dict: n_samples, n_voxels, n_pairs, status, with_color, with_inst"""
