@@ -390,6 +390,7 @@ int esl_lm_os_counts(esl_ctx* ctx, double counts[ESL_OS_COUNTS]);
  *        ellipsoid (bbox edges first, 3-D edges from n_bbox on); zero for edges of fixed cameras.
  *        10 the 6 x 6 diagonal blocks of S (n_free_cams x 36, row-major) exactly as the preconditioner of the last ESL_SOLVER_PCG
  *        trial used them, before inversion; ESL_ERR_STATE when the last trial ran another solver.
+ *        An ellipsoid that takes no step -- fixed, or without any edge and gravity prior -- reads as zeros in 2 and as its state in 7.
  *        count = number of doubles the caller's buffer holds. */
 int esl_lm_download(esl_ctx* ctx, int32_t which, double* dst, int64_t count);
 

@@ -473,6 +473,8 @@ __device__ __forceinline__ void obj_solve_one(const DevGraph& g, const ChunkTabl
   if (c0 == c1 && ngrav == 0) {  // inactive vertex: never touched (sparse_optimizer.cpp:236-257)
     ell_store(e, objs_trial + 10 * o);
     part[o * 4 + 0] = 0; part[o * 4 + 2] = 0; part[o * 4 + 3] = 1;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) xo[(size_t)o * 9 + i] = 0;   // its step reads as zero (esl_lm_download), not as an earlier graph's
     return;   // contributes cg = 0, scale = 0, ok = 1
   }
   double hb[54];
@@ -904,6 +906,8 @@ static __global__ __launch_bounds__(64 * kStepWaves) __attribute__((amdgpu_waves
       okd = ok ? 1.0 : 0.0;
       e = ell_oplus(e, x);
       if (ngrav > 0) { rg_trial = res_grav(e, g.grav_n); cg = wg0 * rg_trial * rg_trial; }   // chi2 of the gravity prior at the trial state
+    } else if (lane < 9) {
+      xo[(size_t)o * 9 + lane] = 0;   // its step reads as zero (esl_lm_download), not as an earlier graph's
     }
     if (lane == 0) ell_store(e, objs_trial + 10 * (size_t)o);
     if (ROBUST && ngrav > 0) { double w = 0; robust_grav<ROBUST>(g, ngrav, rg_trial, w, cg); }   // (e is dead here: no extra registers)
