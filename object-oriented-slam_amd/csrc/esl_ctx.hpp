@@ -141,7 +141,7 @@ void reloc_release(esl_ctx* c);   // esl_reloc.hip
 void assoc_release(esl_ctx* c);   // esl_assoc.hip
 void merge_release(esl_ctx* c);   // esl_merge.hip
 void render_release(esl_ctx* c);  // esl_render.hip
-void dense_release(esl_ctx* c);   // esl_dense.hip
+void dense_release(esl_ctx* c);   // esl_dense.hip: the map and its two extractors
 void init_batch_release(esl_ctx* c);   // esl_init.hip
 // esl_debug_scratch_allocs: each owner's counters, written only when its state exists
 void reloc_scratch_stats(const esl_ctx* c, int64_t* allocs, int64_t* bytes);
@@ -250,7 +250,7 @@ struct esl_ctx {
   esl::AssocState* assoc = nullptr;                               // esl_predict_boxes / esl_associate_boxes: their buffers (esl_assoc.hip AssocState)
   esl::MergeState* merge = nullptr;                               // esl_map_overlaps / esl_map_merge: their buffers (esl_merge.hip MergeState)
   esl::RenderState* render = nullptr;                             // esl_render_map: its buffers (esl_render.hip RenderState)
-  esl::DenseState* dense = nullptr;                               // esl_dense_*: the map's tables and the calls' buffers (esl_dense.hip DenseState)
+  esl::DenseState* dense = nullptr;                               // esl_dense_*: the map's tables and the calls' buffers (esl_dense_int.hpp DenseState)
   esl::InitBatchState* init_batch = nullptr;                     // esl_init_quadrics: its buffers (esl_init.hip InitBatchState)
   void* fit_graph_cache = nullptr;                         // captured launch sequences (std::vector<FitGraphEntry>)
   bool parts_fresh = false;      // host_part holds the last trial's scalars already (slam_try_step fetched them with the solver's flag)

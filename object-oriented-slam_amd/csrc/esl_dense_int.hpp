@@ -1,0 +1,156 @@
+// esl_dense_int.hpp — what the three units of the dense map share: esl_dense.hip (the map), esl_dense_objects.hip and
+// esl_dense_planes.hip (the two extractors that read it).  The record and the counters, the map's state and its buffers, the probes of
+// the voxel table, the sorted list of the live voxels (DenseOutArgs, dense_list_grow / _launch: defined in esl_dense.hip, whose
+// kernels they launch) and the entries' small helpers.  Internal: only those three units include it.
+// The rule of all three: every store to global memory is a vector store or an atomic in plain C++; no loop waits for another thread: a
+// probe that finds no slot within the table's size, or a map over its capacity, raises the sticky status 3 and gives up.
+#pragma once
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "esl_ctx.hpp"
+#include "esl_dense_key.hpp"
+
+namespace esl {
+
+static_assert(sizeof(esl_dense_params) == 40, "include/esl.h states this size");
+static_assert(sizeof(esl_dense_add_result) == 48, "include/esl.h states this size");
+static_assert(sizeof(esl_dense_info) == 32, "include/esl.h states this size");
+static_assert(sizeof(esl_dense_remove_result) == 64, "include/esl.h states this size");
+static_assert(sizeof(esl_dense_move_result) == 120, "include/esl.h states this size");
+static_assert(sizeof(esl_dense_slots) == 32, "include/esl.h states this size");
+static_assert(sizeof(esl_dense_obj_params) == 32, "include/esl.h states this size");
+static_assert(sizeof(esl_dense_obj_result) == 32, "include/esl.h states this size");
+static_assert(sizeof(esl_dense_plane_params) == 80, "include/esl.h states this size");
+static_assert(sizeof(esl_dense_plane_result) == 32, "include/esl.h states this size");
+
+constexpr int kDenseThreads = 256;
+typedef unsigned long long u64;
+
+struct DenseRec { long long S[3]; u64 col[3]; u64 count; u64 best; };
+static_assert(sizeof(DenseRec) == 64, "one record per 64-byte segment");
+
+// the device counters: this call's five counts, then what lives as long as the map
+// (DC_VOXELS / DC_PAIRS count the slots CLAIMED since esl_dense_begin or the last purge), then a removing call's n_missing, the audit's
+// five words and the purge's two list lengths
+enum { DC_SAMPLED, DC_ZERO, DC_DEPTH_OUT, DC_KEY_OUT, DC_USED, DC_VOXELS, DC_PAIRS, DC_STATUS, DC_LIST,
+       DC_MISSING, DC_LIVE_V, DC_DEAD_V, DC_LIVE_P, DC_DEAD_P, DC_BAD, DC_XV, DC_XP, DC_COUNT };
+
+// the map's buffers: the tables, a call's uploads, the sorted list and esl_dense_extract's outputs, then esl_dense_move_frames' second
+// pose set and esl_dense_purge's live records and pairs.  Each extractor keeps a set of its own, its slots named in its unit.
+enum { DB_KEYS, DB_REC, DB_PKEYS, DB_PCNT, DB_CTR, DB_POSE, DB_DEPTH, DB_BGR, DB_INST, DB_LKEY, DB_LVAL, DB_SKEY, DB_SVAL, DB_TEMP,
+       DB_OKEY, DB_OXYZ, DB_OCNT, DB_OBGR, DB_OINST, DB_OVOTES, DB_POSE2, DB_XKEY, DB_XREC, DB_XPKEY, DB_XPID, DB_XPCNT, DB_COUNT };
+constexpr int kDobjBufs = 17, kDplBufs = 12;   // the lengths of the extractors' own enums (asserted there)
+struct DenseState {
+  ScratchSet<DB_COUNT> set;
+  ScratchSet<kDobjBufs> obj_set;   // esl_dense_objects
+  ScratchSet<kDplBufs> pl_set;     // esl_dense_planes
+  bool begun = false, combine = true;
+  esl_dense_params p;
+  int with_color = 0, with_inst = 0;
+  u64 H = 0;
+  long long n_samples = 0, n_voxels = 0, n_pairs = 0;   // n_voxels, n_pairs: LIVE slots (what k_dense_compact lists, what votes)
+  long long dead_voxels = 0, dead_pairs = 0;             // claimed slots whose count is 0 (steps 9 to 11); claimed = live + dead
+  int status = 0;
+  std::vector<double> cams, pose, cams2, pose2;   // host staging of a call's poses (esl_dense_move_frames: both sets)
+  std::vector<int> moved;                         // esl_dense_move_frames: the frames whose pose changed
+};
+
+__device__ __forceinline__ u64 dense_hash(u64 k) {   // hash64 of esl_fit.hip
+  k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
+  return k;
+}
+__device__ __forceinline__ void dense_overflow(u64* ctr) { atomicMax(&ctr[DC_STATUS], 3ull); }
+__device__ __forceinline__ bool dense_over(const u64* ctr) {
+  return __hip_atomic_load(&ctr[DC_STATUS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+}
+
+// The slot of `key` in a table of n (a power of two) slots, claimed if new; -1 when the map is over its capacity.  A new key counts
+// in ctr[which] and raises status 3 beyond `limit`.  At most n probes; every 32nd one looks at the status, so that a table filling up
+// ends the call's remaining probes early.
+__device__ __forceinline__ long long dense_find(u64* keys, u64 n, u64 key, u64* ctr, int which, u64 limit) {
+  u64 slot = dense_hash(key) & (n - 1);
+  for (u64 it = 0; it < n; ++it) {
+    u64 cur = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == kDenseEmpty) {
+      cur = atomicCAS(&keys[slot], kDenseEmpty, key);
+      if (cur == kDenseEmpty) {
+        if (atomicAdd(&ctr[which], 1ull) >= limit) dense_overflow(ctr);
+        return (long long)slot;
+      }
+    }
+    if (cur == key) return (long long)slot;
+    if ((it & 31) == 31 && dense_over(ctr)) return -1;
+    slot = (slot + 1) & (n - 1);
+  }
+  dense_overflow(ctr);
+  return -1;
+}
+
+// The slot of `key`, or -1 when it is not in the table: dense_find's hash and probe without the CAS.  Nothing is claimed; at most n
+// probes, ending at the first empty slot (slots keep their key until a purge, so a chain never loses a link).
+__device__ __forceinline__ long long dense_lookup(const u64* keys, u64 n, u64 key) {
+  u64 slot = dense_hash(key) & (n - 1);
+  for (u64 it = 0; it < n; ++it) {
+    const u64 cur = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == key) return (long long)slot;
+    if (cur == kDenseEmpty) return -1;
+    slot = (slot + 1) & (n - 1);
+  }
+  return -1;
+}
+
+// segmented sum towards the first lane of every run: rid = the run's number (non-decreasing along the wave)
+template <class T>
+__device__ __forceinline__ T dense_run_sum(T v, int rid, int lane) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const T o = __shfl_down(v, off, 64);
+    const int orid = __shfl_down(rid, off, 64);
+    if (lane + off < 64 && orid == rid) v += o;
+  }
+  return v;
+}
+
+struct DenseOutArgs {
+  const u64* keys; DenseRec* rec; const u64* pkeys; const unsigned int* pcnt;
+  u64 H, P;
+  u64* ctr;
+  u64* lkey; unsigned int* lval; u64 list_cap;          // compact
+  const u64* skey; const unsigned int* sval; long long n_write;   // gather
+  int with_color;
+  int* okey; double* oxyz; int* ocnt; unsigned char* obgr; int* oinst; int* ovotes;   // null: not asked for
+};
+
+// The map's voxels as a list of (packed key, slot) in ascending key order, shared by esl_dense_extract and the two extractors.
+// dense_list_grow: the list's buffers and the table pointers of `k`; dense_list_launch (inside the caller's ProfScope, after
+// ctr[DC_LIST] was cleared on the stream): k_dense_compact, k_dense_vote when asked for, the radix sort.
+int dense_list_grow(esl_ctx* c, DenseState& d, DenseOutArgs& k, size_t* temp_bytes);
+int dense_list_launch(esl_ctx* c, DenseState& d, DenseOutArgs& k, bool vote, size_t temp_bytes);
+
+// esl_dense_planes' U_r: the indices i < n with state[i] == -2, ascending, into `list`, their number into *count (a stable rocprim
+// select; with tmp == nullptr only tmp_bytes is set).  Defined in esl_dense.hip beside the list's sort, for the reason given there.
+int dense_select_free(esl_ctx* c, void* tmp, size_t& tmp_bytes, const int* state, int* list, u64* count, size_t n);
+
+inline int dense_fail(int rc, const char* who, const char* what) {
+  set_error(std::string(who) + ": " + what);
+  return rc;
+}
+
+// the state of a map that was begun, or null with the error set (the caller returns ESL_ERR_STATE)
+inline DenseState* dense_begun(esl_ctx* c, const char* who) {
+  if (c->dense && c->dense->begun) return c->dense;
+  dense_fail(ESL_ERR_STATE, who, "no esl_dense_begin before");
+  return nullptr;
+}
+
+inline unsigned dense_blocks(u64 n) { return (unsigned)((n + kDenseThreads - 1) / kDenseThreads); }
+
+struct DenseSlot { int slot; size_t bytes; };   // a row of an extractor's table of the buffers it grows, in order
+
+}  // namespace esl

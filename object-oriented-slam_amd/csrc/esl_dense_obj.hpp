@@ -1,18 +1,22 @@
 // esl_dense_obj.hpp — the arithmetic of esl_dense_objects (include/esl.h, "per-instance ellipsoids from the dense map"; the steps'
-// numbers below are the header's): the normalised plane, a voxel's centre and height (step 1), the guard of the moments (step 5), the
+// numbers below are the header's): the normalised plane, a voxel's centre and height (step 1), the host's choice of a component per
+// label and an object's status (steps 3 to 5: dobj_choose, dobj_status), the guard of the moments (step 5), the
 // gravity basis and the frame of a component (step 6), the projections and the order-preserving encoding their minima and maxima are
 // reduced in (step 7), and the output row (step 8).  Plain C++ for host and device like esl_dense_key.hpp, no HIP include:
 // tests/dense_obj_main.cpp compiles it with an ordinary compiler.  Every translation unit that includes it is built with
 // -ffp-contract=off.  What is `inline` only runs on the host: one compiler decides every bit of the frame.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <vector>
 
 #include "esl_dense_key.hpp"
 
 namespace esl {
 
 constexpr int kDobjMoments = 9;   // s_x s_y s_z, M_xx M_xy M_xz M_yy M_yz M_zz
+constexpr int kDobjRow = 8;       // a row of the component table on the device: label, size, samples, root, kx, ky, kz, 0
 constexpr long long kDobjGuard = 1ll << 62;
 
 struct DobjPlane { double n[3], d, u[3], v[3]; };   // n^, d^ (step 1); u, v (step 6)
@@ -58,6 +62,43 @@ ESL_DENSE_HD double dobj_dec(unsigned long long e) {
   union { double d; unsigned long long u; } b;
   b.u = (e >> 63) ? (e & 0x7FFFFFFFFFFFFFFFull) : ~e;
   return b.d;
+}
+
+// Steps 3 and 4 on the host, from the table of the components of min_component voxels or more as the device left it: R rows of
+// kDobjRow ints in any order, every label below N.  order: the rows sorted by label, then size descending, then the root's index
+// (the order of the packed keys).  Per sorted row its root and the object it is chosen for or -1; per label its chosen sorted row or
+// -1 (the first of its rows) and the number of its rows; the first comp_cap sorted rows go to comp_out (6 ints each).
+struct DobjChoice { std::vector<int> order, rowroot, rowobj, chosen, nrows; };
+inline void dobj_choose(const int* tab, long long R, int N, long long comp_cap, int32_t* comp_out, DobjChoice& c) {
+  c.order.resize((size_t)R);
+  for (long long r = 0; r < R; ++r) c.order[(size_t)r] = (int)r;
+  std::sort(c.order.begin(), c.order.end(), [&](int x, int y) {
+    const int* tx = tab + (size_t)x * kDobjRow; const int* ty = tab + (size_t)y * kDobjRow;
+    if (tx[0] != ty[0]) return tx[0] < ty[0];
+    if (tx[1] != ty[1]) return tx[1] > ty[1];
+    return tx[3] < ty[3];
+  });
+  c.rowroot.assign((size_t)R, 0); c.rowobj.assign((size_t)R, -1); c.chosen.assign((size_t)N, -1); c.nrows.assign((size_t)N, 0);
+  for (long long r = 0; r < R; ++r) {
+    const int* t = tab + (size_t)c.order[(size_t)r] * kDobjRow;
+    c.rowroot[(size_t)r] = t[3];
+    ++c.nrows[(size_t)t[0]];
+    if (c.chosen[(size_t)t[0]] < 0) { c.chosen[(size_t)t[0]] = (int)r; c.rowobj[(size_t)r] = t[0]; }
+    if (r < comp_cap) {
+      int32_t* co = comp_out + 6 * r;
+      co[0] = t[0]; co[1] = t[1]; co[2] = t[2]; co[3] = t[4]; co[4] = t[5]; co[5] = t[6];
+    }
+  }
+}
+
+// steps 4 and 5: an object's status -- 1: no voxel of its label is kept, 2: no component of min_component voxels, 6: the guard of
+// the moments over the chosen component's size and its box kb = kmin, kmax; 0 otherwise
+inline int dobj_status(int labkept, int chosen, const int kb[6], long long size) {
+  if (labkept == 0) return 1;
+  if (chosen < 0) return 2;
+  long long span = 1;
+  for (int e = 0; e < 3; ++e) span = std::max<long long>(span, (long long)kb[3 + e] - kb[e] + 1);
+  return dobj_guard(size, span) ? 6 : 0;
 }
 
 // a^T C b of the symmetric C = {c00, c01, c02, c11, c12, c22}: rows summed left to right, then the three rows left to right

@@ -1,6 +1,6 @@
 // esl_dense_planes.hpp — the arithmetic of esl_dense_planes (include/esl.h, "dominant planes and the ground from the dense map"; the
 // steps' numbers below are the header's): the sampler and the validity of a hypothesis with its plane (step 3), the inlier test (step
-// 4), the winner's order (step 5), the guard, the Jacobi and the refit (step 6), the centroid and the two orientation rules (steps 8
+// 4), the winner (step 5), the guard, the Jacobi, the refit and its acceptance (step 6), the centroid and the two orientation rules (steps 8
 // and 9) and the ground choice (step 9).  Plain C++ for host and device like esl_dense_obj.hpp, no HIP include:
 // tests/dense_planes_main.cpp compiles it with an ordinary compiler.  Every translation unit that includes it is built with
 // -ffp-contract=off.  What is `inline` only runs on the host: one compiler decides every bit of a plane.  The device uses
@@ -62,6 +62,22 @@ inline bool dpl_better(long long n_in, long long samples, int h, long long best_
   if (samples != best_s) return samples > best_s;
   return h < best_h;
 }
+
+// step 5: the winner among the n_hyp hypotheses of a round, or -1 when none is valid; hacc: per hypothesis its inlier voxels and its
+// inlier samples.  hyp_out (or null): the round's rows  valid, inlier voxels, inlier samples.
+inline int dpl_winner(const int* valid, const unsigned long long* hacc, int n_hyp, int64_t* hyp_out) {
+  int win = -1;
+  for (int h = 0; h < n_hyp; ++h) {
+    if (hyp_out) { hyp_out[3 * h] = valid[h]; hyp_out[3 * h + 1] = (int64_t)hacc[2 * h]; hyp_out[3 * h + 2] = (int64_t)hacc[2 * h + 1]; }
+    if (!valid[h]) continue;
+    if (win < 0 || dpl_better((long long)hacc[2 * h], (long long)hacc[2 * h + 1], h, (long long)hacc[2 * win], (long long)hacc[2 * win + 1], win))
+      win = h;
+  }
+  return win;
+}
+
+// step 6: the refit (n inlier voxels, s samples) is kept when it holds no fewer voxels than the winner, and with as many no fewer samples
+inline bool dpl_refit_kept(long long n, long long s, long long win_n, long long win_s) { return n > win_n || (n == win_n && s >= win_s); }
 
 // step 6: the eigenvector of the smallest eigenvalue (ties to the lowest index) of the symmetric C = {c00, c01, c02, c11, c12, c22}
 // by a cyclic Jacobi: kDplSweeps sweeps over the pivots (0,1), (0,2), (1,2), only + - * / sqrt; the vector is re-normalised

@@ -1,5 +1,5 @@
 // esl_uf.hpp — the lock-free union-find walks over a forest in global memory, shared by the single-frame fit's Euclidean clustering
-// (esl_fit.hip, cl_union / cl_stats) and the dense map's component labelling (esl_dense.hip, k_dobj_union / k_dobj_roots).
+// (esl_fit.hip, cl_union / cl_stats) and the dense map's component labelling (esl_dense_objects.hip, k_dobj_union / k_dobj_roots).
 // Linking is by index (the larger root goes under the smaller one, by a CAS on the root's own word), so a component's final root is
 // its smallest member.  Device code only.
 #pragma once

@@ -1,14 +1,18 @@
-// A stand-alone program over csrc/esl_dense_obj.hpp (the host side of the header esl_dense.hip compiles for esl_dense_objects).
+// A stand-alone program over csrc/esl_dense_obj.hpp (the host side of the header esl_dense_objects.hip compiles).
 //   no argument: self-checks on hand-computed cases -- the plane and its gravity basis, a voxel's centre and height, the guard of the
 //                moments at its boundary (no GPU test can reach status 6), the order-preserving encoding, the quaternion branches, the
 //                frame and the output row of a solid 12 x 8 x 6 block; exit status 0 when all hold.
 //   "guard":     reads lines  n span  from stdin and prints the predicate (0 / 1) per line.
 //   "frames":    reads  ground(4) leaf count  then per line  n mom(9) min(3) max(3) ; prints the nine axis numbers and the ten numbers
 //                of the output row with 17 significant digits: the CPU test compares them with the numpy statement.
+//   "table":     reads  R N comp_cap , N kept-voxel counts, R table rows of kDobjRow ints as the device leaves them (any order) and N
+//                boxes kmin(3) kmax(3); prints the lines  order / rowroot / rowobj / chosen / nrows  (dobj_choose), the first
+//                min(R, comp_cap) rows of comp_out as  comp  lines, and  status  (dobj_status per object).
 // Built and run by tests/test_dense_objects_ref.py, also under -fsanitize=address,undefined.  Compile with -ffp-contract=off.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 #include "../object-oriented-slam_amd/csrc/esl_dense_obj.hpp"
 
@@ -110,8 +114,40 @@ static int frames() {
   return 0;
 }
 
+static void put_ints(const char* name, const std::vector<int>& v) {
+  std::printf("%s", name);
+  for (int x : v) std::printf(" %d", x);
+  std::printf("\n");
+}
+
+static int tables() {
+  long long R, comp_cap;
+  int N;
+  if (std::scanf("%lld %d %lld", &R, &N, &comp_cap) != 3 || R < 0 || N < 0 || comp_cap < 0) return 2;
+  std::vector<int> labkept((size_t)N), tab((size_t)R * kDobjRow), kbox((size_t)N * 6);
+  for (int& v : labkept) if (std::scanf("%d", &v) != 1) return 2;
+  for (int& v : tab) if (std::scanf("%d", &v) != 1) return 2;
+  for (int& v : kbox) if (std::scanf("%d", &v) != 1) return 2;
+  const long long cw = R < comp_cap ? R : comp_cap;
+  std::vector<int32_t> comp((size_t)cw * 6, -7);
+  DobjChoice ch;
+  dobj_choose(tab.data(), R, N, comp_cap, comp.data(), ch);
+  put_ints("order", ch.order); put_ints("rowroot", ch.rowroot); put_ints("rowobj", ch.rowobj);
+  put_ints("chosen", ch.chosen); put_ints("nrows", ch.nrows);
+  for (long long r = 0; r < cw; ++r) put_ints("comp", std::vector<int>(comp.begin() + 6 * r, comp.begin() + 6 * r + 6));
+  std::vector<int> status((size_t)N);
+  for (int o = 0; o < N; ++o) {
+    const int row = ch.chosen[(size_t)o];
+    const long long size = row >= 0 ? tab[(size_t)ch.order[(size_t)row] * kDobjRow + 1] : 0;
+    status[(size_t)o] = dobj_status(labkept[(size_t)o], row, kbox.data() + (size_t)o * 6, size);
+  }
+  put_ints("status", status);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc > 1 && !std::strcmp(argv[1], "guard")) return guards();
+  if (argc > 1 && !std::strcmp(argv[1], "table")) return tables();
   if (argc > 1 && !std::strcmp(argv[1], "frames")) return frames();
   self_checks();
   if (fails) return 1;

@@ -1,4 +1,4 @@
-// A stand-alone program over csrc/esl_dense_planes.hpp (the host side of the header esl_dense.hip compiles for esl_dense_planes).
+// A stand-alone program over csrc/esl_dense_planes.hpp (the host side of the header esl_dense_planes.hip compiles).
 //   no argument: self-checks on hand-computed cases -- the sampler's first values, a lattice triple's plane, the validity tests at
 //                their boundaries, the inlier test, the winner's order, the Jacobi of a diagonal and of a known matrix, the refit of a
 //                lattice slab, both orientation rules and the ground choice; exit status 0 when all hold.
@@ -8,6 +8,9 @@
 //   "refit":     leaf, then lines  kmin(3) mom(11)  ->  the plane's four and the centroid's three bit patterns.
 //   "orient":    lines of four doubles  ->  the oriented plane's bit patterns.
 //   "ground":    up(3) up_min_cos n, then n lines  plane(4) n_in  ->  the index and the ground's four bit patterns.
+//   "winner":    lines  n_hyp, then n_hyp triples  valid inlier_voxels inlier_samples  ->  the winner's index (dpl_winner) and the
+//                hyp_out rows it wrote, flattened.
+//   "kept":      lines  n s win_n win_s  ->  dpl_refit_kept (0 / 1).
 // Doubles are read with 17 significant digits (a round trip) and printed as bit patterns: the CPU test compares them with the numpy
 // statement bit for bit.  Built and run by tests/test_dense_planes_ref.py, also under -fsanitize=address,undefined.  Compile with
 // -ffp-contract=off.
@@ -169,8 +172,31 @@ static int grounds() {
   return 0;
 }
 
+static int winners() {
+  int n;
+  while (std::scanf("%d", &n) == 1 && n >= 0) {
+    std::vector<int> valid((size_t)n);
+    std::vector<unsigned long long> hacc((size_t)n * 2);
+    std::vector<int64_t> rows((size_t)n * 3, -7);
+    for (int h = 0; h < n; ++h) if (std::scanf("%d %llu %llu", &valid[(size_t)h], &hacc[(size_t)h * 2], &hacc[(size_t)h * 2 + 1]) != 3) return 2;
+    std::printf("%d", dpl_winner(valid.data(), hacc.data(), n, rows.data()));
+    for (int64_t v : rows) std::printf(" %lld", (long long)v);
+    std::printf("\n");
+    if (dpl_winner(valid.data(), hacc.data(), n, nullptr) != dpl_winner(valid.data(), hacc.data(), n, rows.data())) return 3;
+  }
+  return 0;
+}
+
+static int kepts() {
+  long long n, s, wn, ws;
+  while (std::scanf("%lld %lld %lld %lld", &n, &s, &wn, &ws) == 4) std::printf("%d\n", dpl_refit_kept(n, s, wn, ws) ? 1 : 0);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc > 1 && !std::strcmp(argv[1], "sample")) return samples();
+  if (argc > 1 && !std::strcmp(argv[1], "winner")) return winners();
+  if (argc > 1 && !std::strcmp(argv[1], "kept")) return kepts();
   if (argc > 1 && !std::strcmp(argv[1], "hyp")) return hyps();
   if (argc > 1 && !std::strcmp(argv[1], "jacobi")) return jacobis();
   if (argc > 1 && !std::strcmp(argv[1], "refit")) return refits();

@@ -153,6 +153,21 @@ def ground(planes, n_in, uh, up_min_cos):
     return g, ([-x for x in pl] if proj(pl, uh) < 0 else pl)
 
 
+def winner(rows):
+    """step 5 on a round's rows (valid, inlier voxels, inlier samples): the valid row with the most voxels, then the most samples, then
+    the smallest index; None when no row is valid"""
+    best = None
+    for h, (valid, n_in, smp) in enumerate(rows):
+        if valid and (best is None or (n_in, smp) > (rows[best][1], rows[best][2])):          # ascending h: a tie keeps the smaller h
+            best = h
+    return best
+
+
+def refit_kept(n2, s2, win_n, win_s):
+    """step 6: the refit is kept with no fewer inlier voxels, and with as many no fewer samples"""
+    return (n2, s2) >= (win_n, win_s)
+
+
 def planes(ext, leaf, voxel_cap=None, **over):
     """ext = DenseMap.extract() (all voxels).  Returns what Context.dense_planes(hyp=True) returns."""
     p = dict(DEFAULTS); p.update(over)
@@ -189,7 +204,7 @@ def planes(ext, leaf, voxel_cap=None, **over):
             XU, cU, kU = X[U], count[U], keys[U]
             rows = np.zeros((Hn, 3), np.int64)
             hyp.append(rows)
-            best = None          # (n_in, samples, h, plane)
+            pls = {}
             for h in range(Hn):
                 i = [index(p["seed"], r, Hn, h, k, n_r) for k in range(3)]
                 a, b, c = ([int(x) for x in kU[j]] for j in i)
@@ -198,12 +213,12 @@ def planes(ext, leaf, voxel_cap=None, **over):
                     continue
                 _, n_in, smp = score(pl, XU, cU, p["dist_tol"])
                 rows[h] = (1, n_in, smp)
-                if best is None or (n_in, smp) > best[:2]:          # ascending h: a tie keeps the smaller h
-                    best = (n_in, smp, h, pl)
-            if best is None:
+                pls[h] = pl
+            win_h = winner(rows.tolist())
+            if win_h is None:
                 stop = 2
                 break
-            win_n, win_s, win_h, fin = best
+            win_n, win_s, fin = int(rows[win_h, 1]), int(rows[win_h, 2]), pls[win_h]
             fin_n, refined = win_n, 0
             if p["refine"]:
                 if guard(win_n, span):
@@ -212,7 +227,7 @@ def planes(ext, leaf, voxel_cap=None, **over):
                     inl, _, _ = score(fin, XU, cU, p["dist_tol"])
                     re = refit(moments(kU[inl], cU[inl], kmin), kmin, leaf)
                     _, n2, s2 = score(re, XU, cU, p["dist_tol"])
-                    if (n2, s2) >= (win_n, win_s):
+                    if refit_kept(n2, s2, win_n, win_s):
                         refined, fin, fin_n = 1, re, n2
                     else:
                         refined = 2

@@ -1,6 +1,7 @@
 """The numpy statement of esl_dense_objects (tests/dense_objects_ref.py) held against independent checks, and csrc/esl_dense_obj.hpp --
 the header the kernels and the host side compile -- held to hand-computed cases and to the statement (tests/dense_obj_main.cpp).  No GPU."""
 import ctypes
+import functools
 import os
 import re
 import shutil
@@ -95,16 +96,21 @@ def test_components_against_breadth_first_search(seed, reach):
     assert not set(offs) & {(-x, -y, -z) for x, y, z in offs}          # every pair from one side
 
 
-def test_statement_on_a_random_labelled_map():
-    """the whole statement against the independent labelling: table order, statuses 0, 1, 2, voxel rows, caps, status 3"""
+@functools.lru_cache(maxsize=None)
+def random_labelled_extract():
+    """the extract of a map of four blocks and dust with three labels, unlabelled voxels and labels beyond N = 4; shared, not changed"""
     rng = np.random.default_rng(5)
     keys = np.unique(np.concatenate([block((9, 5, 4), (0, 0, 2)), block((4, 4, 4), (20, 0, 2)), block((4, 4, 4), (-20, 3, 2)),
                                      block((2, 2, 2), (0, 20, 2)), rng.integers(-30, 30, (60, 3))]), axis=0)
     lab = np.where(keys[:, 1] >= 15, 2, np.where(np.abs(keys[:, 0]) >= 15, 1, 0))
     lab[rng.random(len(keys)) < 0.05] = -1
     lab[-3:] = 7          # beyond N
-    m = map_of(keys, 0.05, lab)
-    e = m.extract()
+    return map_of(keys, 0.05, lab).extract()
+
+
+def test_statement_on_a_random_labelled_map():
+    """the whole statement against the independent labelling: table order, statuses 0, 1, 2, voxel rows, caps, status 3"""
+    e = random_labelled_extract()
     N = 4
     r = dor.objects(e, 0.05, N, FLOOR, reach=1, min_component=20)
     h = (e["key"][:, 2] + 0.5) * 0.05
@@ -196,3 +202,80 @@ def test_obj_header_matches_the_statement(tmp_path, flags):
     out = subprocess.run([exe, "frames"], input=head + "\n".join(lines) + "\n", capture_output=True, text=True, check=True).stdout
     got = np.array([[float(v) for v in ln.split()] for ln in out.strip().split("\n")])
     assert got.shape == (40, 19) and np.abs(got - np.array(want)).max() <= 1e-13
+
+
+# ---- steps 3 and 4 on the host: dobj_choose and dobj_status on a component table as the device leaves it -----------------------------------------
+NO_BOX = [2**31 - 1] * 3 + [-2**31] * 3          # the box of an object without a chosen component, as the entry initialises it
+
+
+def run_table(exe, N, labkept, table, kbox, comp_cap):
+    """-> the program's output lines as {name: [ints]} and the list of its comp rows"""
+    text = f"{len(table)} {N} {comp_cap}\n" + "".join(" ".join(str(int(v)) for v in row) + "\n" for row in [labkept] + list(table) + list(kbox))
+    out = {"comp": []}
+    for ln in subprocess.run([exe, "table"], input=text, capture_output=True, text=True, check=True).stdout.strip().split("\n"):
+        name, *vals = ln.split()
+        if name == "comp":
+            out["comp"].append([int(v) for v in vals])
+        else:
+            out[name] = [int(v) for v in vals]
+    return out
+
+
+def device_table(e, N, reach, min_component, shuffle):
+    """what k_dobj_table leaves and what k_dobj_box adds, from the independent labelling: rows (label, size, samples, the root's index in
+    the sorted list, its key, 0) in a shuffled order, the kept voxels per label, and per label the box of its largest component"""
+    kept = (e["inst"] >= 0) & (e["inst"] < N) & ((e["key"][:, 2] + 0.5) * 0.05 >= 0.05)
+    ki = np.flatnonzero(kept)
+    keys = e["key"].astype(np.int64)
+    kc = bfs_components(keys[ki], e["inst"][ki], reach)
+    rows, box = [], {}
+    for root in np.unique(kc):
+        mem = ki[kc == root]
+        if len(mem) >= min_component:
+            rows.append([int(e["inst"][ki[root]]), len(mem), int(e["count"][mem].sum()), int(ki[root]), *keys[ki[root]].tolist(), 0])
+            box[int(ki[root])] = keys[mem].min(axis=0).tolist() + keys[mem].max(axis=0).tolist()
+    labkept = [int((e["inst"][ki] == o).sum()) for o in range(N)]
+    kbox = []
+    for o in range(N):
+        mine = [t for t in rows if t[0] == o]
+        kbox.append(box[min(mine, key=lambda t: (-t[1], t[3]))[3]] if mine else NO_BOX)
+    return [rows[i] for i in np.random.default_rng(shuffle).permutation(len(rows))], labkept, kbox
+
+
+@pytest.mark.parametrize("flags", [(), ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan")],
+                         ids=["plain", "asan_ubsan"])
+def test_table_choice_and_statuses_match_the_statement(tmp_path, flags):
+    exe = build_obj_prog(tmp_path, flags)
+    # the random labelled map: the component table and the per-object stats of the statement
+    e, N = random_labelled_extract(), 4
+    r = dor.objects(e, 0.05, N, FLOOR, reach=1, min_component=20)
+    table, labkept, kbox = device_table(e, N, 1, 20, shuffle=11)
+    R = len(table)
+    assert R == len(r["comp"]) == 3 and [t[3] for t in table] != sorted(t[3] for t in table)          # handed over out of order
+    got = run_table(exe, N, labkept, table, kbox, comp_cap=R)
+    assert got["comp"] == r["comp"].tolist()
+    st = r["stats"]
+    assert got["status"] == st[:, 0].tolist() == [0, 0, 2, 1] and labkept == st[:, 1].tolist()
+    assert got["nrows"] == st[:, 2].tolist() and got["chosen"] == st[:, 3].tolist()
+    srt = [table[i] for i in got["order"]]
+    assert [[t[0], t[1], t[2], *t[4:7]] for t in srt] == r["comp"].tolist() and got["rowroot"] == [t[3] for t in srt]
+    assert [srt[c][1:3] if c >= 0 else [0, 0] for c in got["chosen"]] == st[:, 4:6].tolist()
+    assert got["rowobj"] == [t[0] if got["chosen"][t[0]] == i else -1 for i, t in enumerate(srt)]
+    assert (dr.pack(e["key"].astype(np.int64)[got["rowroot"]]) == dr.pack(r["comp"][:, 3:])).all()          # a row's root IS its key's voxel
+    assert run_table(exe, N, labkept, table, kbox, comp_cap=1)["comp"] == r["comp"][:1].tolist()
+    # a hand-built table of six rows, N = 6, comp_cap 4 < R.  Label 0: two rows of 50 voxels (the lower root, 7, wins over 40) and one of
+    # 30; label 1: kept voxels, no row; label 2: nothing kept; labels 3 and 4: the box spans 2^21 keys, so 2^20 voxels trip the guard
+    # (2^20 2^42 = 2^62) and 2^20 - 1 do not; label 5: an ordinary row
+    big = 1 << 20
+    table = [[5, 25, 60, 90, 1, 2, 3, 0], [0, 50, 70, 40, 4, 4, 4, 0], [3, big, big, 11, -5, 0, 0, 0], [0, 30, 30, 3, 0, 0, 1, 0],
+             [0, 50, 55, 7, 0, 1, 1, 0], [4, big - 1, 2 * big, 12, 9, 9, 9, 0]]
+    wide = [-big, 0, 0, big - 1, 5, 5]
+    assert dor.guard(big, 2 * big) and not dor.guard(big - 1, 2 * big)
+    got = run_table(exe, 6, [130, 5, 0, big, big - 1, 25], table, [[0, 0, 0, 9, 9, 9], NO_BOX, NO_BOX, wide, wide, [1, 2, 3, 4, 5, 6]], comp_cap=4)
+    assert got == dict(order=[4, 1, 3, 2, 5, 0], rowroot=[7, 40, 3, 11, 12, 90], rowobj=[0, -1, -1, 3, 4, 5], chosen=[0, -1, -1, 3, 4, 5],
+                       nrows=[3, 0, 0, 1, 1, 1], status=[0, 2, 1, 6, 0, 0],
+                       comp=[[0, 50, 55, 0, 1, 1], [0, 50, 70, 4, 4, 4], [0, 30, 30, 0, 0, 1], [3, big, big, -5, 0, 0]])
+    # no row at all (R = 0): kept labels have status 2; and no object at all (N = 0)
+    got = run_table(exe, 3, [4, 0, 2], [], [NO_BOX] * 3, comp_cap=5)
+    assert got == dict(order=[], rowroot=[], rowobj=[], chosen=[-1, -1, -1], nrows=[0, 0, 0], status=[2, 1, 2], comp=[])
+    assert run_table(exe, 0, [], [], [], comp_cap=0) == dict(order=[], rowroot=[], rowobj=[], chosen=[], nrows=[], status=[], comp=[])

@@ -317,3 +317,18 @@ def test_planes_header_matches_the_statement(tmp_path, flags):
         g, pl = dpr.ground(P, n_in, dpr.up_unit(up), cosv)
         text = " ".join(repr(x) for x in up) + f" {cosv!r} {n}\n" + "".join(" ".join(repr(x) for x in p) + f" {c}\n" for p, c in zip(P, n_in))
         assert run(exe, "ground", text) == [f"{g} " + " ".join(bits(x) for x in pl)]
+    # step 5, the winner over a round's (valid, inlier voxels, inlier samples), and the rows of hyp_out it writes
+    rounds = {"unique best": ([(1, 40, 90), (1, 70, 10), (1, 69, 500), (0, 0, 0)], 1),
+              "samples break a tie on voxels": ([(1, 70, 10), (1, 12, 900), (1, 70, 11), (1, 70, 10)], 2),
+              "the index breaks a full tie": ([(0, 70, 11), (1, 5, 5), (1, 70, 11), (1, 70, 11)], 2),
+              "an invalid row holds the best numbers": ([(1, 3, 3), (0, 1 << 40, 1 << 50), (1, 4, 1), (1, 3, 9)], 2),
+              "the only valid row is the last": ([(0, 9, 9), (0, 0, 0), (0, 7, 70), (1, 0, 0)], 3),
+              "no valid row": ([(0, 9, 9), (0, 8, 8)], None)}
+    text = "".join(f"{len(rows)}\n" + "".join("%d %d %d\n" % r for r in rows) for rows, _ in rounds.values())
+    for (name, (rows, want)), line in zip(rounds.items(), run(exe, "winner", text)):
+        assert dpr.winner(rows) == want, name
+        assert [int(x) for x in line.split()] == [-1 if want is None else want] + [v for r in rows for v in r], name
+    # step 6, the refit's acceptance at its three boundaries: more voxels, as many voxels with as many / fewer samples, fewer voxels
+    cases = [(71, 0, 70, 11), (70, 11, 70, 11), (70, 12, 70, 11), (70, 10, 70, 11), (69, 1 << 40, 70, 11)]
+    assert [dpr.refit_kept(*c) for c in cases] == [True, True, True, False, False]
+    assert run(exe, "kept", "".join("%d %d %d %d\n" % c for c in cases)) == ["1", "1", "1", "0", "0"]
