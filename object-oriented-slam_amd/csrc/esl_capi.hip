@@ -137,6 +137,7 @@ int esl_ctx_create(int device_id, esl_ctx** out) {
   { const char* ov = std::getenv("ESL_CF_OVERLAP"); c->sw_cf_overlap = (ov && ov[0] >= '0' && ov[0] <= '4') ? ov[0] - '0' : 4; }
   { const char* ok = std::getenv("ESL_CF_OS_KERNEL"); c->sw_cf_os_kernel = (ok && ok[0] == '0') ? 0 : 1; }
   { const char* ol = std::getenv("ESL_CF_OS_LIST"); c->sw_cf_os_list = (ol && ol[0] == '0') ? 0 : 1; }
+  { const char* sp = std::getenv("ESL_CF_SWEEP"); c->sw_cf_sweep = (sp && sp[0] == '0') ? 0 : 1; }
   { const char* fp = std::getenv("ESL_CF_FWD_PARTS"); const int v = fp ? std::atoi(fp) : 0; if (v == 2 || v == 4 || v == 8) c->sw_cf_fwd_parts = v; }
   { const char* sd = std::getenv("ESL_CF_STRIDE"); const int v = sd ? std::atoi(sd) : 0; c->sw_cf_stride = (v == 16 || v == 32 || v == 48) ? v : 0; }
   auto init = [&]() -> int {

@@ -31,6 +31,7 @@
 //
 // The layout decisions (dense or sparse X, form, segment length, T's order, every table's offsets; kCfFwdCh and the other layout
 // constants) are host-only code in esl_cf_plan.hpp; esl_slam.hip ships the plan (cf_ensure_impl) and enqueues one schedule per form.
+// esl_cf_sweep.hpp: form 3 without the interior slab -- Y from one two-directional sweep per segment (the default; ESL_CF_SWEEP).
 #pragma once
 #include "esl_cf_plan.hpp"   // the layout decisions: kCfFwdCh, kCfSyT, kCfSegRows, kCfMaxStride, cf_stride_choose
 #include "esl_kernels_map.hpp"
@@ -566,7 +567,7 @@ static __global__ __launch_bounds__(64) void k_cf_sep_rhs(int nf, int n_o, int s
                                                           const double* __restrict__ vy, const double* __restrict__ Gfac,
                                                           const double* __restrict__ LiS, const double* __restrict__ Xt, long ldx,
                                                           double* __restrict__ R, const int* __restrict__ cmap /* null: X dense in Xt */,
-                                                          CfSegs sg) {
+                                                          CfSegs sg, const double* __restrict__ XL = nullptr, long long xl_rows = 1) {
   const int j = blockIdx.x * 64 + threadIdx.x, k = blockIdx.y;
   if (j > n_o) return;
   const bool rhs = j == n_o;
@@ -595,7 +596,12 @@ static __global__ __launch_bounds__(64) void k_cf_sep_rhs(int nf, int n_o, int s
     const int ob = rhs ? N1 - 1 : (sg.unrank ? sg.unrank[tb2] : tb2);
     has_acc = has_acc && cmap[(size_t)(k + 1) * N1 + ob] >= 0;
     const int e = cmap[(size_t)k * N1 + ob];
-    if (e >= 0) {
+    if (e >= 0 && XL) {   // no slab (esl_cf_sweep.hpp): the last interior slot's rows alone, six per segment
+      const double* src = XL + (size_t)(sg.xoff[k] / xl_rows) * 6 + (size_t)(9 * (e & 0xFFFFFF) + bb);
+      const size_t ld = (size_t)sg.xld[k];
+#pragma unroll
+      for (int r = 0; r < 6; ++r) xl[r] = src[(size_t)r * ld];
+    } else if (e >= 0) {
       const double* src = Xt + (size_t)sg.xoff[k] + (size_t)(9 * (e & 0xFFFFFF) + bb);
       const size_t ld = (size_t)sg.xld[k];
 #pragma unroll
@@ -840,11 +846,12 @@ static __global__ __launch_bounds__(256) void k_cf_T_sparse(int N, int nw, const
 
 // z = y - X x_o with the interior rows in the slabs: one workgroup per row (slot i, component a)
 // xo_t: x_o in T's column order (= xo unless T's ellipsoids are permuted, CfSegs::rank): what a separator's dense row meets
+// sep_only (no slab, esl_cf_sweep.hpp): workgroup = row of a SEPARATOR (separator blockIdx.x / 6), the interior rows are k_cf_z_fwd's
 static __global__ __launch_bounds__(256) void k_cf_z_sparse(int n_o, const double* __restrict__ Xs, long ldx, CfSegs sg, const double* __restrict__ Xc,
                                                             const double* __restrict__ xo, const double* __restrict__ xo_t, double* __restrict__ z,
-                                                            int stride) {
+                                                            int stride, int sep_only = 0) {
   __shared__ double red[4];
-  const int t = blockIdx.x, i = t / 6, a = t - 6 * i;
+  const int t = sep_only ? 6 * (((int)blockIdx.x / 6) * stride + stride - 1) + (int)blockIdx.x % 6 : (int)blockIdx.x, i = t / 6, a = t - 6 * i;
   const int p = i / stride, pos = i - p * stride;
   double s = 0, y;
   if (pos == stride - 1) {   // separator p: a dense row

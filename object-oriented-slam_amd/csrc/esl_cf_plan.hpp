@@ -69,6 +69,7 @@ struct CfSwitches {
   int stride = 0;          // ESL_CF_STRIDE: 16, 32 or 48 forces form 3's segment length, 0 = by cf_stride_choose
   int os_kernel = 1;       // ESL_CF_OS_KERNEL: 0 = the per-lane gather (k_cf_T_onesided) whatever the offsets' size
   int os_list = 1;         // ESL_CF_OS_LIST: 0 = the assembly's list walks the row side over every entry, twins apart (A/B: the bits of that list)
+  int sweep = 1;           // ESL_CF_SWEEP: 0 = form 3 keeps the interior slab (k_cf_forward<2> + k_cf_seg_back + the slab's z: A/B, the parent's bits)
 };
 
 // The sparse form's tables for segments of S slots (the last slot of a segment is its separator): what cf_walk returns.
@@ -121,6 +122,12 @@ struct CfPlan : CfSegTables {
   std::vector<int> os_run, os_heads;
   size_t osm_npairs = 0, osm_row_npairs = 0, os_list_npairs = 0;
   double osm_flops = 0;
+  // Form 3 without the interior slab (esl_cf_sweep.hpp; ESL_CF_SWEEP).  The by-slot index of the entry lists, for z's W_I x_o:
+  // sl_ent[q] = the entry (position in os / ou) that is the q-th of the per-camera lists cu_start / cu_obj, which give the slot's
+  // range and the entry's ellipsoid.  xl_len: the last interior slot's six rows of every segment (sum of 6 xld).
+  bool sweep = false;
+  std::vector<int> sl_ent;
+  size_t xl_len = 0;
   // T's ellipsoids in the order of their first free camera (sparse form): column block rank[o] of T / R / Xs belongs to ellipsoid o;
   // kfirst[g] = first row of Xs that can be non-zero in columns [64 g, 64 g + 64) (the rank-K update skips the rest);
   // upd_flops = what the dense update executes with the staircase
@@ -374,6 +381,16 @@ inline bool cf_plan_build(int N, int nf, size_t EU, const std::vector<int>& star
     cf_os_sides(pl, start);
     pl.os_list = sw.os_list != 0;
     pl.os_list_npairs = pl.os_list ? pl.osm_npairs : pl.os_npairs;
+    pl.sweep = sw.sweep != 0;
+    if (pl.sweep) {   // cf_entry_lists' walk again: entry `at` of the ellipsoid's list is the q-th of its camera's
+      std::vector<int> cur(start.begin(), start.end() - 1);
+      pl.sl_ent.assign((size_t)cu_start[nf], 0);
+      for (int sl = 0; sl < nf; ++sl)
+        for (int q = cu_start[sl]; q < cu_start[sl + 1]; ++q) pl.sl_ent[(size_t)q] = cur[cu_obj[q]]++;
+      long long cols = 0;
+      for (int x : pl.xld) cols += x;
+      pl.xl_len = 6 * (size_t)cols;
+    }
   }
   return true;
 }

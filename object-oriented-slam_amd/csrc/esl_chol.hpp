@@ -180,25 +180,26 @@ struct CholRuntime {
   void* prof_user = nullptr;
   // camera-first elimination (esl_slam.hip): the separators' chain runs here beside the interior rows' pipeline, then the segments'
   // products beside the separators' forward recurrence and the rank-K update.  cf_ev_a: the separators' system is assembled (main
-  // stream); cf_ev_s: their chain's blocks are written (side); cf_ev_x: the slabs are complete (main); cf_ev_p: the products are (side)
+  // stream); cf_ev_s: their chain's blocks are written (side); cf_ev_x: the slabs are complete (main); cf_ev_p: the products are (side);
+  // cf_ev_c: the segments' chains are factored (main); cf_ev_t: the sweep's per-slot matrices are written (side; esl_cf_sweep.hpp)
   hipStream_t cf_side = nullptr;
-  hipEvent_t cf_ev_x = nullptr, cf_ev_p = nullptr, cf_ev_a = nullptr, cf_ev_s = nullptr;
+  hipEvent_t cf_ev_x = nullptr, cf_ev_p = nullptr, cf_ev_a = nullptr, cf_ev_s = nullptr, cf_ev_c = nullptr, cf_ev_t = nullptr;
   hipError_t cf_overlap_init() {
-    if (cf_side && cf_ev_x && cf_ev_p && cf_ev_a && cf_ev_s) return hipSuccess;
+    if (cf_side && cf_ev_x && cf_ev_p && cf_ev_a && cf_ev_s && cf_ev_c && cf_ev_t) return hipSuccess;
     if (cf_side) return hipErrorNotReady;   // (an earlier attempt failed half way: the serial order)
     // (a plain second stream.  Two full-size grids on two streams do not run side by side -- the second kernel's workgroups are placed
     //  when the first one's are all dispatched -- and with the side stream confined to every 2nd / 4th / 8th CU of every XCD
     //  (hipExtStreamCreateWithCUMask) the products simply ran later AND slower: the bracket around T's build 29.3 -> 32.9 / 40.7 / 57.2 ms.
     //  What the second stream does give: the products fill the update's last, partly empty round of tiles: 30.0 -> 29.3 ms.)
     hipError_t e = hipStreamCreateWithFlags(&cf_side, hipStreamNonBlocking); if (e != hipSuccess) return e;
-    for (hipEvent_t* ev : {&cf_ev_x, &cf_ev_p, &cf_ev_a, &cf_ev_s}) {
+    for (hipEvent_t* ev : {&cf_ev_x, &cf_ev_p, &cf_ev_a, &cf_ev_s, &cf_ev_c, &cf_ev_t}) {
       e = hipEventCreateWithFlags(ev, hipEventDisableTiming); if (e != hipSuccess) return e;
     }
     return hipSuccess;
   }
   void release() {
     if (cf_side) { (void)hipStreamSynchronize(cf_side); (void)hipStreamDestroy(cf_side); cf_side = nullptr; }
-    for (hipEvent_t* ev : {&cf_ev_x, &cf_ev_p, &cf_ev_a, &cf_ev_s})
+    for (hipEvent_t* ev : {&cf_ev_x, &cf_ev_p, &cf_ev_a, &cf_ev_s, &cf_ev_c, &cf_ev_t})
       if (*ev) { (void)hipEventDestroy(*ev); *ev = nullptr; }
     if (bs_flags) { (void)hipFree(bs_flags); bs_flags = nullptr; bs_flags_cap = 0; }
     if (d_tasks) { (void)hipFree(d_tasks); d_tasks = nullptr; d_tasks_cap = 0; }

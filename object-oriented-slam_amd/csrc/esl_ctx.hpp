@@ -295,6 +295,10 @@ struct esl_ctx {
   unsigned long long* cf_mask = nullptr;
   long long *cf_xoff = nullptr, *cf_boff = nullptr, *cf_roff = nullptr;
   double *cf_Xc = nullptr, *cf_Xs = nullptr, *cf_P = nullptr, *cf_Prhs = nullptr, *cf_Y = nullptr, *cf_Yr = nullptr;
+  // form 3 without the interior slab (esl_cf_sweep.hpp): the per-slot matrices of the backward direction and of the combination, the
+  // last interior slot's rows of x per segment, the entry of every place of the per-camera lists
+  double *cf_Pm = nullptr, *cf_Qm = nullptr, *cf_XL = nullptr;
+  int* cf_sl_ent = nullptr;
   // the one-sided assembly's pair list (k_cf_os_list): per block of T's lower triangle and of the b row where its (A record, B record)
   // pairs start and how many there are
   long long* cf_os_start = nullptr;
@@ -355,8 +359,12 @@ struct esl_ctx {
   // twins and walks the shorter side per block and segment; 0 the row side over every entry, from cf_V (the bits of that list)
   int sw_cf_os_list = 1;
   // ESL_CF_FWD_PARTS as read when the context was created (A/B and tests): 8 (default), 4 or 2 parts per chunk of the slab sweep
-  // k_cf_forward<2> (esl_cf.hpp): less LDS per one-wave workgroup, more waves per CU.  Same bits at every value.
+  // k_cf_forward<2> (esl_cf.hpp) and of k_cf_sweep (esl_cf_sweep.hpp): less LDS per one-wave workgroup, more waves per CU.  Same bits at
+  // every value.
   int sw_cf_fwd_parts = 8;
+  // ESL_CF_SWEEP as read when the context was created (A/B and tests): 1 (default) form 3 builds Y in one two-directional sweep per
+  // segment and never stores the interior slab (esl_cf_sweep.hpp); 0 the parent's k_cf_forward<2> + k_cf_seg_back + slab z, its bits
+  int sw_cf_sweep = 1;
   // ESL_CF_STRIDE as read when the context was created: 16, 32 or 48 forces the segment length of the sparse form where T is
   // assembled one-sided (form 3); 0 (unset) = chosen at layout time from the graph's counts (esl_cf_plan.hpp, cf_stride_cost)
   int sw_cf_stride = 0;

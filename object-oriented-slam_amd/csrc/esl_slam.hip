@@ -12,6 +12,7 @@
 #include <cstring>
 
 #include "esl_cf.hpp"
+#include "esl_cf_sweep.hpp"
 #include "esl_chol.hpp"
 #include "esl_fixed.hpp"
 #include "esl_kernels_slam.hpp"
@@ -305,6 +306,7 @@ static void cf_forget(esl_ctx* c) {
   c->cf_Zt = c->cf_Hs = c->cf_Bs = c->cf_LfacS = c->cf_GS = c->cf_LiS = c->cf_MS = c->cf_NS = c->cf_R = nullptr;
   c->cf_Xc = c->cf_Xs = c->cf_P = c->cf_Prhs = c->cf_Xt = c->cf_Y = c->cf_Yr = nullptr;
   c->cf_os_start = nullptr; c->cf_os_cnt = c->cf_os_pairs = c->cf_os_run = c->cf_os_heads = nullptr; c->cf_Vm = nullptr;
+  c->cf_Pm = c->cf_Qm = c->cf_XL = nullptr; c->cf_sl_ent = nullptr;
   c->cf_rank = c->cf_unrank = c->cf_kfirst = nullptr; c->cf_xo_t = nullptr;
   c->cf_plan = CfPlan{};
   c->cf_ready = false;
@@ -339,6 +341,7 @@ static int cf_ensure_impl(esl_ctx* c) {
   sw.no_nd = std::getenv("ESL_CF_NO_ND") != nullptr;
   static const int nd_min = [] { const char* e = std::getenv("ESL_CF_ND_MIN"); return e ? std::atoi(e) : 48; }();
   sw.nd_min = nd_min; sw.stride = c->sw_cf_stride; sw.os_kernel = c->sw_cf_os_kernel; sw.os_list = c->sw_cf_os_list;
+  sw.sweep = c->sw_cf_sweep;
   size_t free_b = 0, total_b = 0;   // (the TOTAL decides between forms 1 and 2, never what happens to be free)
   if (nfi >= kCfSparseMinCams) ESL_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
   CfPlan& pl = c->cf_plan;
@@ -347,6 +350,7 @@ static int cf_ensure_impl(esl_ctx* c) {
     return ESL_ERR_ALLOC;
   }
   const bool sp = pl.sparse, os3 = sp && pl.form == 3, osm = os3 && pl.os_list;   // (osm: twins merged, shorter side)
+  const bool swp = os3 && pl.sweep;   // Y in one sweep per segment: no interior slab (esl_cf_sweep.hpp)
   const int nch = pl.n_chunks, nseg = pl.nseg, nw = pl.nw, N1 = N + 1;
   const size_t n_inc = pl.p.size();
   const size_t y_recs = std::max<size_t>(n_inc, 1) * (size_t)(pl.S - 1), nb = (size_t)N * (N + 1) / 2 + N;   // (Y's records; blocks of T's lower triangle + the b row)
@@ -365,6 +369,7 @@ static int cf_ensure_impl(esl_ctx* c) {
     ship(&c->cf_xoff, pl.xoff); ship(&c->cf_boff, pl.boff); ship(&c->cf_roff, pl.roff); ship(&d_fw_off, pl.fw_off); ship(&d_tw_off, pl.tw_off);
   }
   if (osm) { ship(&c->cf_os_run, pl.os_run); ship(&c->cf_os_heads, pl.os_heads); }
+  if (swp) ship(&c->cf_sl_ent, pl.sl_ent);
   st.work(&c->cf_oe_cst, (size_t)std::max(N, 1) * (nch + 1));
   if (sp) {
     st.work(&c->cf_cmap, (size_t)nseg * N1); st.work(&c->cf_mask, (size_t)N1 * nw); st.work(&c->cf_seg_obj, n_inc); st.work(&c->cf_seg_first, n_inc);
@@ -382,12 +387,14 @@ static int cf_ensure_impl(esl_ctx* c) {
     st.work(&c->cf_R, ns * 6 * (size_t)pl.ldx);
   }
   if (sp) {
-    st.work(&c->cf_Xc, pl.xc_len); st.work(&c->cf_Xs, (size_t)pl.ldx * (size_t)pl.kpad_s);
+    if (!swp) st.work(&c->cf_Xc, pl.xc_len);
+    st.work(&c->cf_Xs, (size_t)pl.ldx * (size_t)pl.kpad_s);
     if (pl.form == 1) { st.work(&c->cf_P, pl.p_blocks * 81); st.work(&c->cf_Prhs, pl.prhs_len); }
     if (pl.form == 3) {
       st.work(&c->cf_Y, y_recs * 54); st.work(&c->cf_Yr, std::max<size_t>(nf, 1) * 6);
       st.work(&c->cf_os_start, nb + 1); st.work(&c->cf_os_cnt, nb); st.work(&c->cf_os_pairs, 2 * std::max<size_t>(pl.os_list_npairs, 1));
       if (osm) st.work(&c->cf_Vm, EU * 54);
+      if (swp) { st.work(&c->cf_Pm, nf * 36); st.work(&c->cf_Qm, nf * 36); st.work(&c->cf_XL, std::max<size_t>(pl.xl_len, 1)); }
     }
   } else {
     st.work(&c->cf_Xt, (size_t)pl.ldx * (size_t)pl.kpad);
@@ -442,7 +449,7 @@ static int cf_ensure_impl(esl_ctx* c) {
   if (sp) {
     // slabs: pad columns and rows 90 .. 95 stay zero; Xs: rows 6 n_sep .. kpad_s (the K padding of the rank-K update) stay zero;
     // T: the blocks above the diagonal are never written
-    ESL_HIP_TRY(hipMemsetAsync(c->cf_Xc, 0, std::max<size_t>(pl.xc_len, 1) * sizeof(double), c->stream));
+    if (!swp) ESL_HIP_TRY(hipMemsetAsync(c->cf_Xc, 0, std::max<size_t>(pl.xc_len, 1) * sizeof(double), c->stream));
     ESL_HIP_TRY(hipMemsetAsync(c->cf_Xs, 0, (size_t)pl.ldx * (size_t)pl.kpad_s * sizeof(double), c->stream));
     ESL_HIP_TRY(hipMemsetAsync(c->cf_T, 0, (size_t)pl.ldt * n_o * sizeof(double), c->stream));
     if (pl.form == 3) {   // (the records of slots behind a short last segment's end are never written and never read)
@@ -481,11 +488,12 @@ struct CfTrial {
   const int st, ns, nseg;   // dissection: stride, separators, segments
   const bool nd, dist;      // dist: replicated-graph communicator, this rank builds its outer panels of T only
   const unsigned cg;        // groups of 64 columns of [X | y]
+  const bool swp;           // form 3 without the interior slab (esl_cf_sweep.hpp)
   const hipStream_t main;
   CfSideJoin join;
   CfTrial(esl_ctx* c_, CholRuntime& rt_, double lambda_)
       : c(c_), rt(rt_), pl(c_->cf_plan), g(c_->g), lambda(lambda_), N(g.n_objs), nf(g.n_free_cams), n_o(9 * N), ldx((long)pl.ldx), ldt((long)pl.ldt),
-        st(pl.stride), ns(pl.n_sep), nseg(pl.n_seg), nd(st > 0 && ns > 0), dist(cf_dist(c_)), cg((unsigned)((n_o + 1 + 63) / 64)), main(c_->stream),
+        st(pl.stride), ns(pl.n_sep), nseg(pl.n_seg), nd(st > 0 && ns > 0), dist(cf_dist(c_)), cg((unsigned)((n_o + 1 + 63) / 64)), swp(pl.sparse && pl.form == 3 && pl.sweep), main(c_->stream),
         join{rt_, c_->stream, false} {}
   CfSegs segs() const { return CfSegs{c->cf_fwork, c->cf_seg_start, c->cf_seg_obj, c->cf_xoff, c->cf_xld, c->cf_rank, c->cf_unrank}; }
   int edge_blocks() const { return (int)(((long)pl.n_list * 9 + nf + 255) / 256); }
@@ -507,8 +515,10 @@ struct CfTrial {
                        c->cf_V, c->cf_vy, cls, st);
   }
   // nested dissection (esl_cf.hpp), first half: the segments' chains in parallel and the separators' system assembled from them
-  void segment_chains() const {
+  // after_chain: enqueued straight behind the chains' launch (the sweep's per-slot matrices need L_ii and G alone)
+  template <class F> void segment_chains(F after_chain) const {
     hipLaunchKernelGGL(k_cf_chain, dim3((unsigned)nseg), dim3(64), 0, main, nf, c->Hcc, c->cf_B, lambda, c->cf_Lfac, c->cf_G, c->chol_info, st, st - 1);
+    after_chain();
     hipLaunchKernelGGL(k_cf_factor_blocks, dim3((unsigned)((nf + 63) / 64)), dim3(64), 0, main, nf, c->cf_Lfac, c->cf_G, c->cf_Linv, c->cf_M, c->cf_N, st);
     if (nseg > 1) hipLaunchKernelGGL(k_cf_zt, dim3((unsigned)(nseg - 1)), dim3(64), 0, main, nf, st, c->cf_Linv, c->cf_M, c->cf_B, c->cf_Zt);
     hipLaunchKernelGGL(k_cf_sep_assemble, dim3((unsigned)((ns * 36 + 255) / 256)), dim3(256), 0, main, nf, st, ns, c->Hcc, lambda, c->cf_G, c->cf_Zt,
@@ -526,7 +536,23 @@ struct CfTrial {
   // cf_overlap_init) -- beside V and vy of the INTERIOR slots, which need L_ii^-1 of the segments' chains alone; the separator slots'
   // are then left to the caller, behind cf_ev_s (the separators' blocks exist)
   int slabs(bool beside) {
-    segment_chains();
+    // no slab (esl_cf_sweep.hpp): P and Q of the backward direction, one wave per segment and stride - 1 serial steps -- on the side
+    // stream beside the rest of the chains' launches and V (cf_ev_c -> cf_ev_t), else in stream order
+    auto twist = [&](hipStream_t s) {
+      hipLaunchKernelGGL(k_cf_twist, dim3((unsigned)nseg), dim3(64), 0, s, nf, st, c->Hcc, lambda, c->cf_Lfac, c->cf_G, c->cf_Pm, c->cf_Qm, c->chol_info);
+    };
+    hipError_t e_tw = hipSuccess;
+    segment_chains([&] {
+      if (!swp) return;
+      if (!beside) { twist(main); return; }
+      e_tw = hipEventRecord(rt.cf_ev_c, main);
+      if (e_tw == hipSuccess) e_tw = hipStreamWaitEvent(rt.cf_side, rt.cf_ev_c, 0);
+      if (e_tw != hipSuccess) return;
+      join.armed = true;
+      twist(rt.cf_side);
+      e_tw = hipEventRecord(rt.cf_ev_t, rt.cf_side);
+    });
+    ESL_HIP_TRY(e_tw);
     if (beside) {
       ESL_HIP_TRY(hipEventRecord(rt.cf_ev_a, main));
       ESL_HIP_TRY(hipStreamWaitEvent(rt.cf_side, rt.cf_ev_a, 0));
@@ -534,6 +560,19 @@ struct CfTrial {
     }
     sep_chain(beside ? rt.cf_side : main);
     if (beside) ESL_HIP_TRY(hipEventRecord(rt.cf_ev_s, rt.cf_side));
+    if (swp) {   // Y, the sums in R and the last slot's rows in one sweep
+      edge_scale(beside ? 1 : 0, main);
+      if (beside) ESL_HIP_TRY(hipStreamWaitEvent(main, rt.cf_ev_t, 0));
+      auto sweep = [&](auto parts) {
+        hipLaunchKernelGGL((k_cf_sweep<decltype(parts)::value>), dim3((unsigned)pl.n_fwork), dim3(64), 0, main, nf, n_o, pl.n_chunks, c->cf_oe_cst, c->cf_oe_slot,
+                           c->cf_V, c->cf_vy, c->cf_M, (const double*)c->cf_Zt, c->cf_Pm, c->cf_Qm, c->cf_R, ldx, st, segs(), c->cf_Y, c->cf_Yr, c->cf_XL,
+                           (long long)(st == kCfFwdCh ? kCfSegRows : 6 * (st - 1)));
+      };
+      if (c->sw_cf_fwd_parts == 8) sweep(std::integral_constant<int, 8>{});
+      else if (c->sw_cf_fwd_parts == 4) sweep(std::integral_constant<int, 4>{});
+      else sweep(std::integral_constant<int, 2>{});
+      return ESL_OK;
+    }
     edge_scale(beside ? 1 : 0, main);
     auto forward = [&](auto parts) {   // (the parts of a chunk, ESL_CF_FWD_PARTS: LDS per workgroup, so the waves in flight; same bits)
       hipLaunchKernelGGL((k_cf_forward<2, decltype(parts)::value>), dim3((unsigned)pl.n_fwork), dim3(64), 0, main, nf, n_o, pl.n_chunks, c->cf_oe_cst, c->cf_oe_slot,
@@ -547,7 +586,8 @@ struct CfTrial {
   // the separators' right-hand sides from the slabs (sp; else from the dense X), the sums and their own V ...
   void sep_rhs(hipStream_t s, bool sp = true) const {
     hipLaunchKernelGGL(k_cf_sep_rhs, dim3(cg, (unsigned)ns), dim3(64), 0, s, nf, n_o, st, pl.n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V, c->cf_vy,
-                       c->cf_G, c->cf_LiS, sp ? c->cf_Xc : c->cf_Xt, ldx, c->cf_R, sp ? (const int*)c->cf_cmap : nullptr, sp ? segs() : CfSegs{});
+                       c->cf_G, c->cf_LiS, sp ? c->cf_Xc : c->cf_Xt, ldx, c->cf_R, sp ? (const int*)c->cf_cmap : nullptr, sp ? segs() : CfSegs{},
+                       (const double*)(sp && swp ? c->cf_XL : nullptr), (long long)(st == kCfFwdCh ? kCfSegRows : 6 * (st - 1)));
   }
   // ... and the separators' dense rows: into Xs (row block k = separator k), else into X at their slots; one wave per 64 columns
   void sep_forward(hipStream_t s, bool sp = true) const {
@@ -593,7 +633,7 @@ struct CfTrial {
       hipLaunchKernelGGL(k_cf_forward<0>, dim3(cg), dim3(64), 0, main, nf, n_o, pl.n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V, c->cf_vy,
                          c->cf_M, c->cf_Xt, ldx, nf, nf, (const double*)nullptr, (double*)nullptr, 0, CfSegs{});
     } else {   // segments in parallel, then the separators' own short chain
-      segment_chains();
+      segment_chains([] {});
       sep_chain(main);
       edge_scale_T();
       hipLaunchKernelGGL(k_cf_forward<0>, dim3(cg, (unsigned)nseg), dim3(64), 0, main, nf, n_o, pl.n_chunks, c->cf_oe_cst, c->cf_oe_slot, c->cf_V,
@@ -693,7 +733,10 @@ struct CfTrial {
   // T = D - sum (assign), then T -= Xs^T Xs.  Hazards across trials: as in build_stored_side, with cf_ev_p = Xs is complete.
   // k_cf_v_merge reads cf_V on the main stream while edge_scale(2) may still write cf_V on the side stream: disjoint records -- a run
   // is an ellipsoid's entries of one INTERIOR slot (os_run is 0 elsewhere), class 2 writes the entries of separator slots only; the
-  // interior ones were written by edge_scale(1) in front of it on the main stream.  cf_Vm is written and read on the main stream. ----
+  // interior ones were written by edge_scale(1) in front of it on the main stream.  cf_Vm is written and read on the main stream.
+  // Without the interior slab (swp, esl_cf_sweep.hpp; ESL_CF_SWEEP != 0) slabs() leaves Y, the sums in R and the last interior slots'
+  // rows (cf_XL, which k_cf_sep_rhs reads on the side stream: covered like the slabs were, by cf_ev_x and cf_ev_p) and no k_cf_seg_back
+  // follows; k_cf_twist's cf_Pm / cf_Qm are written on the side stream behind cf_ev_c and read on the main one behind cf_ev_t. ----
   int build_onesided(bool beside) {
     const hipStream_t sst = beside ? rt.cf_side : main;   // the separators' stream
     if (int rc = slabs(beside)) return rc;
@@ -711,9 +754,11 @@ struct CfTrial {
         hipLaunchKernelGGL(k_cf_seg_back<decltype(mch)::value>, dim3((unsigned)pl.n_fwork), dim3(64), 0, main, nf, c->cf_fwork, c->cf_seg_start, c->cf_xoff,
                            c->cf_xld, c->cf_Xc, c->cf_Linv, c->cf_G, c->cf_Y, c->cf_Yr);
       };
-      if (st == 3 * kCfFwdCh) seg_back(std::integral_constant<int, 3>{});
-      else if (st == 2 * kCfFwdCh) seg_back(std::integral_constant<int, 2>{});
-      else seg_back(std::integral_constant<int, 1>{});
+      if (!swp) {   // (else Y is the sweep's, written by slabs())
+        if (st == 3 * kCfFwdCh) seg_back(std::integral_constant<int, 3>{});
+        else if (st == 2 * kCfFwdCh) seg_back(std::integral_constant<int, 2>{});
+        else seg_back(std::integral_constant<int, 1>{});
+      }
       // twins merged (esl_cf.hpp k_cf_os_list): the runs' sums of V, which the list's pairs name; ESL_CF_OS_LIST=0: V itself
       if (pl.os_list && pl.n_list > 0)
         hipLaunchKernelGGL(k_cf_v_merge, dim3((unsigned)(((long)pl.n_list * 9 + 255) / 256)), dim3(256), 0, main, pl.n_list, (const int*)c->cf_os_run, c->cf_V, c->cf_Vm);
@@ -742,7 +787,12 @@ struct CfTrial {
         ESL_HIP_TRY(chol_factor_solve(c->cf_T, ldt, n_o, c->cf_Linv_ws, c->z_ws, xsol, c->chol_info, main, rt));
       }
       if (xsol != c->xo) hipLaunchKernelGGL(k_cf_xo_unpermute, dim3((unsigned)((n_o + 255) / 256)), dim3(256), 0, main, N, c->cf_rank, xsol, c->xo);
-      if (pl.sparse)
+      if (swp) {   // interior rows: d = vy - W_I x_o slot by slot, then the segments' forward recurrence on it; the separators' dense rows as ever
+        hipLaunchKernelGGL(k_cf_wxo, dim3((unsigned)nf), dim3(64), 0, main, st, g.cu_start, (const int*)c->cf_sl_ent, g.cu_obj, c->cf_V, c->cf_vy, c->xo, c->cf_z);
+        hipLaunchKernelGGL(k_cf_z_fwd, dim3((unsigned)nseg), dim3(64), 0, main, nf, st, c->cf_M, c->cf_z);
+        if (ns > 0)
+          hipLaunchKernelGGL(k_cf_z_sparse, dim3((unsigned)(6 * ns)), dim3(256), 0, main, n_o, c->cf_Xs, ldx, segs(), (const double*)nullptr, c->xo, xsol, c->cf_z, st, 1);
+      } else if (pl.sparse)
         hipLaunchKernelGGL(k_cf_z_sparse, dim3((unsigned)(6 * nf)), dim3(256), 0, main, n_o, c->cf_Xs, ldx, segs(), c->cf_Xc, c->xo, xsol, c->cf_z, st);
       else
         hipLaunchKernelGGL(k_cf_z, dim3((unsigned)(6 * nf)), dim3(256), 0, main, c->cf_Xt, ldx, n_o, c->xo, c->cf_z);
