@@ -55,7 +55,8 @@ extern "C" {
                              *    (esl_map_overlaps, esl_map_merge), and the per-pixel rendering of a map (esl_render_map), and the voxel-fused
                              *    dense map of many RGB-D frames (esl_dense_begin / _add_frames / _info_get / _extract / _end) with its
                              *    per-instance ellipsoids (esl_dense_objects) and its dominant planes and ground (esl_dense_planes), and
-                             *    its exact de-integration (esl_dense_remove_frames / _move_frames / _purge / _slots_get) */
+                             *    its exact de-integration (esl_dense_remove_frames / _move_frames / _purge / _slots_get), and its
+                             *    view from any pose, checked against measured depth (esl_dense_render) */
 #define ESL_MAX_TRACE 32
 
 typedef enum {
@@ -1139,6 +1140,76 @@ int esl_dense_planes(esl_ctx* ctx, const esl_dense_plane_params* p /* NULL = def
                      esl_dense_plane_result* out);
 /* the score kernel's layout: entries of U_r per LDS tile and hypotheses per workgroup (tests place list lengths around them) */
 int esl_debug_dense_planes_layout(int32_t* tile_out, int32_t* group_out);
+
+/* ---- viewing the dense map: per-pixel depth, colour, label and voxel from any pose, checked on depth (additive part of ABI 5: detect by the symbol) ---
+ * The reference builds its dense map to show it (src/dense_builder, the Pangolin viewer).  esl_dense_render gives the dense map what
+ * esl_render_map gives the ellipsoid map: every live voxel is splatted as a square of its leaf into every frame, the nearest voxel
+ * wins each pixel, and against a measured depth image every won pixel is counted as agreeing, nearer or farther -- per frame (does the
+ * map explain the images after a move?) and per voxel (which voxels do later frames see through?).  The call only counts: it does not
+ * change the map.  Everything is FP64 and integers; every choice is a strict comparison or a total order and the only atomics are
+ * integer atomics, so runs are bit-reproducible.
+ *  1. Voxels.  The live voxels of the map in ascending packed-key order: the list, and the index i, that esl_dense_extract would give
+ *     at this moment.  Each carries extract's xyz ((double)S_a / 2^30 / (double)count), count, bgr and inst (dense-map step 7).  A voxel
+ *     with count < min_count is skipped in every frame; it counts in n_small, once per call.
+ *  2. Camera point.  Poses are Tcw = (t, q); they are validated and turned into R on the host exactly as step 2 of the dense map does
+ *     (an invalid pose gives ESL_ERR_INVALID before anything runs).  p_c[a] = ((R[a][0] p0 + R[a][1] p1) + R[a][2] p2) + t[a]; no product
+ *     is contracted with a sum.  z = p_c[2].  The voxel is not drawn in this frame unless z >= depth_min && z <= depth_max (a NaN
+ *     fails): such voxels count in the frame's n_depth_out.
+ *  3. Footprint.  e = footprint leaf / 2, one double computed on the host.  With x = p_c[0]: u = (fx x) / z + cx, u0 = (fx (x - e)) / z +
+ *     cx, u1 = (fx (x + e)) / z + cx; the same with fy, p_c[1], cy for v, v0, v1: multiply, then divide, then add.  If any of the six is
+ *     not finite or exceeds 2^30 in magnitude the voxel counts in the frame's n_outside (the values are compared as doubles, never
+ *     converted).  col = floor(u + 0.5), c0 = min(col, ceil(u0)), c1 = max(col, floor(u1)): the pixels whose centre lies inside the
+ *     projected square, and always the pixel nearest the centroid.  Then c0 = max(c0, col - max_radius), c1 = min(c1, col +
+ *     max_radius), then both are clipped to [0, cols - 1]; rows alike.  An empty range on either axis counts in n_outside; otherwise
+ *     the voxel counts in n_drawn.
+ *  4. Pixel.  zq = llrint(z 2^20) (depth_max <= 4095 keeps zq < 2^32).  Every pixel of the footprint receives the candidate
+ *     zq << 32 | i and keeps the smallest: the nearest voxel, ties to the lowest index.  The stored depth is the winner's own z, not zq.
+ *  5. Images.  depth_out = the winner's z, voxel_out = i, bgr_out / inst_out = the winner's colour and label as esl_dense_extract
+ *     reports them (0 / -1 on a map without colour / labels).  A pixel without a winner gets NaN, -1, 0, -1.
+ *  6. Depth comparison at every pixel with a winner: step 6 of esl_render_map word for word (no data, agree, nearer, farther, with this
+ *     call's depth_scale, depth_min, depth_max and depth_tol).  frame_out[8 f ..] = n_drawn, n_depth_out, n_outside, covered (the pixels
+ *     with a winner), agree, nearer, farther, no data; the last four sum to covered and are 0 without depth_meas.  vox_out[4 i ..] =
+ *     won (the pixels voxel i wins), agree, nearer, farther, summed over the call's frames, for the first vox_cap voxels; the last
+ *     three are 0 without depth_meas.
+ *  7. Memory.  The candidates of a chunk of frames live in a buffer of at most zbuf_bytes: the frames are processed in chunks of
+ *     max(1, floor(zbuf_bytes / (8 rows cols))), n_chunks = ceil(F / that).  No result depends on the chunking.
+ *  8. Map status.  On a map whose status is not 0 the call returns ESL_OK, the result reports that status and n_voxels = -1, and
+ *     nothing else is written -- as esl_dense_extract, esl_dense_objects and esl_dense_planes do. */
+typedef struct {
+  double  depth_scale;  /* 5000: raw units per metre of depth_meas; finite, > 0 */
+  double  depth_min;    /* 0.1: the gate of a voxel's z (step 2) and of a measured sample (step 6); finite, >= 0 */
+  double  depth_max;    /* 6.0: finite, >= depth_min, <= 4095 */
+  double  depth_tol;    /* 0.05 m: |z_meas - z| <= depth_tol agrees; finite, >= 0 */
+  double  footprint;    /* 1.0: the side of a voxel's square in leaves; 0 = the nearest pixel only; finite, >= 0 */
+  int32_t max_radius;   /* 8: a footprint reaches at most this many pixels from its centre pixel; 0 .. 64 */
+  int32_t min_count;    /* 1: voxels with fewer samples are not drawn; >= 1 */
+  int64_t zbuf_bytes;   /* 268435456: the most the per-pixel candidates of one chunk of frames may take; >= 8 rows cols */
+} esl_dense_render_params;   /* 56 bytes; design choices, not values tuned on real data */
+void esl_dense_render_params_default(esl_dense_render_params* p);
+
+typedef struct { int32_t status, n_voxels, n_small, n_chunks; } esl_dense_render_result; /* 16 bytes */
+
+/* ESL_ERR_INVALID: null ctx, K or out; negative F or vox_cap, vox_cap > 0 with vox_out NULL; rows or cols < 1 or > 16384; fx or fy not
+ * finite or <= 0; depth_scale not finite or <= 0; depth_min, depth_max or depth_tol not finite or negative; depth_min > depth_max;
+ * depth_max > 4095; footprint not finite or < 0; max_radius < 0 or > 64; min_count < 1; zbuf_bytes < 8 rows cols; an invalid pose
+ * (step 2); F differing from the resident graph's n_cams when cams == NULL.  The comparison counts of frame_out and vox_out are always
+ * written (zero without depth_meas), so no output needs depth_meas.  ESL_ERR_STATE: no esl_dense_begin before; cams == NULL without a
+ * resident graph and states.  F = 0, an empty map and all outputs NULL are valid.  An output that is not asked for is neither computed
+ * nor allocated.  The call changes nothing in the map except the best words and the shared sorted list, which the extracting calls
+ * rebuild too.  Its buffers are a set of its own beside the dense map's (grow-only; a warm call of the same shape allocates nothing:
+ * esl_debug_dense_allocs counts them; at most zbuf_bytes + a chunk's images + 40 bytes per voxel); one GPU, no collective, launches
+ * bracketed as kernel class 4. */
+int esl_dense_render(esl_ctx* ctx,
+                     const double* cams /* F x 7 Tcw, NULL = resident camera states (F must equal n_cams) */, int32_t F,
+                     const double K[4], int32_t rows, int32_t cols,
+                     const uint16_t* depth_meas /* F x rows x cols or NULL */, const esl_dense_render_params* p /* NULL = defaults */,
+                     double* depth_out  /* F x rows x cols or NULL: z of the winning voxel, NaN where none */,
+                     int32_t* voxel_out /* F x rows x cols or NULL: its index in esl_dense_extract's order, -1 where none */,
+                     uint8_t* bgr_out   /* F x rows x cols x 3 or NULL: its colour, 0 where none */,
+                     int32_t* inst_out  /* F x rows x cols or NULL: its label, -1 where none */,
+                     int32_t* frame_out /* F x 8 or NULL: n_drawn, n_depth_out, n_outside, covered, agree, nearer, farther, no data */,
+                     int64_t vox_cap, int32_t* vox_out /* vox_cap x 4 or NULL: won, agree, nearer, farther; the first min(vox_cap, n_voxels) rows written */,
+                     esl_dense_render_result* out);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------*/
 /* Dense FP64-MFMA Cholesky factor + solve (the reduced-camera solver of SLAM mode) on a procedurally generated,

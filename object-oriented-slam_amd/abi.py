@@ -358,9 +358,42 @@ def default_dense_plane_params(**kw):
     return p
 
 
+class EslDenseRenderParams(C.Structure):
+    """esl_dense_render_params: the depth gates, the footprint and the z-buffer's size of esl_dense_render."""
+    _fields_ = [("depth_scale", C.c_double), ("depth_min", C.c_double), ("depth_max", C.c_double), ("depth_tol", C.c_double),
+                ("footprint", C.c_double), ("max_radius", C.c_int32), ("min_count", C.c_int32), ("zbuf_bytes", C.c_int64)]
+
+
+class EslDenseRenderResult(C.Structure):
+    """esl_dense_render_result: status 3 / 4 = an invalid map (n_voxels = -1); n_small = voxels below min_count; n_chunks = chunks of frames."""
+    _fields_ = [("status", C.c_int32), ("n_voxels", C.c_int32), ("n_small", C.c_int32), ("n_chunks", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert C.sizeof(EslDenseRenderParams) == 56 and C.sizeof(EslDenseRenderResult) == 16
+
+
+def default_dense_render_params(**kw):
+    """esl_dense_render_params_default: design choices, not values tuned on real data (include/esl.h)"""
+    p = EslDenseRenderParams(depth_scale=5000.0, depth_min=0.1, depth_max=6.0, depth_tol=0.05, footprint=1.0, max_radius=8, min_count=1,
+                             zbuf_bytes=268435456)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
 def dense_argtypes(L):
     """the esl_dense_* calls take nullable pointers: declared, so that None passes as NULL and a wrong type raises"""
     dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    L.esl_dense_render_params_default.argtypes = [C.POINTER(EslDenseRenderParams)]
+    L.esl_dense_render_params_default.restype = None
+    L.esl_dense_render.argtypes = [C.c_void_p, dp, C.c_int32, dp, C.c_int32, C.c_int32, C.POINTER(C.c_uint16), C.POINTER(EslDenseRenderParams),
+                                   dp, ip, C.POINTER(C.c_uint8), ip, ip, C.c_int64, ip, C.POINTER(EslDenseRenderResult)]
+    L.esl_dense_render.restype = C.c_int
     L.esl_dense_params_default.argtypes = [C.POINTER(EslDenseParams)]
     L.esl_dense_params_default.restype = None
     L.esl_dense_begin.argtypes = [C.c_void_p, C.POINTER(EslDenseParams), C.c_int32, C.c_int32]

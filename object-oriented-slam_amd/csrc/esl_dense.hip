@@ -21,8 +21,8 @@
 //   k_dense_vote      extract: per live pair one atomicMax of (votes << 32 | ~id) into its voxel's best word: most votes, ties to
 //                     the lowest id.  Done at extract time over the whole pair table, so incremental adds stay exact.
 //   rocprim radix sort of (packed key, slot), then k_dense_gather writes the first `cap` voxels in key order.
-// esl_dense_objects.hip and esl_dense_planes.hip work on that sorted list; what they share with this unit, and the rule that every
-// kernel of the three keeps, is esl_dense_int.hpp's.
+// esl_dense_objects.hip, esl_dense_planes.hip and esl_dense_render.hip work on that sorted list; what they share with this unit, and
+// the rule that every kernel of the four keeps, is esl_dense_int.hpp's.
 #include "esl_dense_int.hpp"
 
 #include <rocprim/rocprim.hpp>   // after <cstring>: its headers call memset unqualified
@@ -349,12 +349,12 @@ static __global__ __launch_bounds__(kDenseThreads) void k_dense_gather(DenseOutA
 void dense_scratch_stats(const esl_ctx* c, int64_t* allocs, int64_t* bytes) {
   if (!c->dense) return;
   const DenseState& d = *c->dense;
-  *allocs = d.set.allocs() + d.obj_set.allocs() + d.pl_set.allocs();
-  *bytes = (int64_t)(d.set.held() + d.obj_set.held() + d.pl_set.held());
+  *allocs = d.set.allocs() + d.obj_set.allocs() + d.pl_set.allocs() + d.rn_set.allocs();
+  *bytes = (int64_t)(d.set.held() + d.obj_set.held() + d.pl_set.held() + d.rn_set.held());
 }
 
 void dense_release(esl_ctx* c) {   // called by esl_ctx_destroy
-  if (c->dense) { c->dense->set.release(); c->dense->obj_set.release(); c->dense->pl_set.release(); }
+  if (c->dense) { c->dense->set.release(); c->dense->obj_set.release(); c->dense->pl_set.release(); c->dense->rn_set.release(); }
   delete c->dense;
   c->dense = nullptr;
 }
@@ -386,6 +386,10 @@ int dense_list_launch(esl_ctx* c, DenseState& d, DenseOutArgs& k, bool vote, siz
   ESL_HIP_TRY(rocprim::radix_sort_pairs(s.buf[DB_TEMP], temp_bytes, s.at<u64>(DB_LKEY), s.at<u64>(DB_SKEY),
                                         s.at<unsigned int>(DB_LVAL), s.at<unsigned int>(DB_SVAL), (size_t)d.n_voxels, 0, 63, c->stream));
   return ESL_OK;
+}
+
+void dense_gather_launch(esl_ctx* c, const DenseOutArgs& k) {
+  hipLaunchKernelGGL(k_dense_gather, dim3(dense_blocks((u64)k.n_write)), dim3(kDenseThreads), 0, c->stream, k);
 }
 
 // esl_dense_planes' select (esl_dense_int.hpp).  It stays in this unit: without rocprim::select's device code beside them the
@@ -479,6 +483,26 @@ extern "C" int esl_dense_info_get(esl_ctx* c, esl_dense_info* out) {
   return ESL_OK;
 }
 
+namespace esl {
+
+// step 2 on the host (esl_dense_int.hpp): R and t of every frame, from the given poses or the resident camera states
+int dense_frames_poses(esl_ctx* c, const char* who, const double* cams, int F, std::vector<double>& host, std::vector<double>& pose) {
+  host.resize((size_t)F * 7);
+  if (cams) std::memcpy(host.data(), cams, (size_t)F * 7 * sizeof(double));
+  else {
+    ESL_HIP_TRY(hipMemcpyAsync(host.data(), c->cams, (size_t)F * 7 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    ESL_HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  pose.resize((size_t)F * kDensePose);
+  for (int f = 0; f < F; ++f) {
+    if (!dense_pose(host.data() + (size_t)f * 7, pose.data() + (size_t)f * kDensePose))
+      return dense_fail(ESL_ERR_INVALID, who, "a pose with a non-finite number or a quaternion of norm 0");
+  }
+  return ESL_OK;
+}
+
+}  // namespace esl
+
 namespace {
 
 // what esl_dense_add_frames, _remove_frames and _move_frames check alike, case by case and in this order; res_cams: the poses (of
@@ -498,22 +522,6 @@ int dense_frames_check(esl_ctx* c, const char* who, int32_t F, const double K[4]
   if (F > 0 && d->with_color && !bgr) return dense_fail(ESL_ERR_STATE, who, "null bgr on a map begun with colour");
   if (F > 0 && d->with_inst && !inst) return dense_fail(ESL_ERR_STATE, who, "null inst on a map begun with labels");
   return resident_source_check(c, who, res_cams && F > 0, F, false, 0);
-}
-
-// step 2 on the host: R and t of every frame, from the given poses or the resident camera states
-int dense_frames_poses(esl_ctx* c, const char* who, const double* cams, int F, std::vector<double>& host, std::vector<double>& pose) {
-  host.resize((size_t)F * 7);
-  if (cams) std::memcpy(host.data(), cams, (size_t)F * 7 * sizeof(double));
-  else {
-    ESL_HIP_TRY(hipMemcpyAsync(host.data(), c->cams, (size_t)F * 7 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    ESL_HIP_TRY(hipStreamSynchronize(c->stream));
-  }
-  pose.resize((size_t)F * kDensePose);
-  for (int f = 0; f < F; ++f) {
-    if (!dense_pose(host.data() + (size_t)f * 7, pose.data() + (size_t)f * kDensePose))
-      return dense_fail(ESL_ERR_INVALID, who, "a pose with a non-finite number or a quaternion of norm 0");
-  }
-  return ESL_OK;
 }
 
 long long dense_per_frame(const DenseState& d, int rows, int cols) {
@@ -770,7 +778,7 @@ extern "C" int esl_dense_extract(esl_ctx* c, int64_t cap, int32_t* key_out, doub
   {
     ProfScope ps(c, 4);
     if (const int rc = dense_list_launch(c, d, k, vote, temp_bytes)) return rc;
-    hipLaunchKernelGGL(k_dense_gather, dim3(dense_blocks((u64)nw)), dim3(kDenseThreads), 0, c->stream, k);
+    dense_gather_launch(c, k);
   }
   ESL_HIP_TRY(hipGetLastError());
   if (key_out) ESL_HIP_TRY(hipMemcpyAsync(key_out, k.okey, (size_t)nw * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));

@@ -1,8 +1,8 @@
-// esl_dense_int.hpp — what the three units of the dense map share: esl_dense.hip (the map), esl_dense_objects.hip and
-// esl_dense_planes.hip (the two extractors that read it).  The record and the counters, the map's state and its buffers, the probes of
+// esl_dense_int.hpp — what the four units of the dense map share: esl_dense.hip (the map), esl_dense_objects.hip and
+// esl_dense_planes.hip (the two extractors that read it) and esl_dense_render.hip (the view of it).  The record and the counters, the map's state and its buffers, the probes of
 // the voxel table, the sorted list of the live voxels (DenseOutArgs, dense_list_grow / _launch: defined in esl_dense.hip, whose
-// kernels they launch) and the entries' small helpers.  Internal: only those three units include it.
-// The rule of all three: every store to global memory is a vector store or an atomic in plain C++; no loop waits for another thread: a
+// kernels they launch) and the entries' small helpers.  Internal: only those four units include it.
+// The rule of all four: every store to global memory is a vector store or an atomic in plain C++; no loop waits for another thread: a
 // probe that finds no slot within the table's size, or a map over its capacity, raises the sticky status 3 and gives up.
 #pragma once
 #include <algorithm>
@@ -28,6 +28,8 @@ static_assert(sizeof(esl_dense_obj_params) == 32, "include/esl.h states this siz
 static_assert(sizeof(esl_dense_obj_result) == 32, "include/esl.h states this size");
 static_assert(sizeof(esl_dense_plane_params) == 80, "include/esl.h states this size");
 static_assert(sizeof(esl_dense_plane_result) == 32, "include/esl.h states this size");
+static_assert(sizeof(esl_dense_render_params) == 56, "include/esl.h states this size");
+static_assert(sizeof(esl_dense_render_result) == 16, "include/esl.h states this size");
 
 constexpr int kDenseThreads = 256;
 typedef unsigned long long u64;
@@ -45,11 +47,12 @@ enum { DC_SAMPLED, DC_ZERO, DC_DEPTH_OUT, DC_KEY_OUT, DC_USED, DC_VOXELS, DC_PAI
 // pose set and esl_dense_purge's live records and pairs.  Each extractor keeps a set of its own, its slots named in its unit.
 enum { DB_KEYS, DB_REC, DB_PKEYS, DB_PCNT, DB_CTR, DB_POSE, DB_DEPTH, DB_BGR, DB_INST, DB_LKEY, DB_LVAL, DB_SKEY, DB_SVAL, DB_TEMP,
        DB_OKEY, DB_OXYZ, DB_OCNT, DB_OBGR, DB_OINST, DB_OVOTES, DB_POSE2, DB_XKEY, DB_XREC, DB_XPKEY, DB_XPID, DB_XPCNT, DB_COUNT };
-constexpr int kDobjBufs = 17, kDplBufs = 12;   // the lengths of the extractors' own enums (asserted there)
+constexpr int kDobjBufs = 17, kDplBufs = 12, kDrnBufs = 14;   // the lengths of the other units' own enums (asserted there)
 struct DenseState {
   ScratchSet<DB_COUNT> set;
   ScratchSet<kDobjBufs> obj_set;   // esl_dense_objects
   ScratchSet<kDplBufs> pl_set;     // esl_dense_planes
+  ScratchSet<kDrnBufs> rn_set;     // esl_dense_render
   bool begun = false, combine = true;
   esl_dense_params p;
   int with_color = 0, with_inst = 0;
@@ -132,6 +135,12 @@ struct DenseOutArgs {
 // ctr[DC_LIST] was cleared on the stream): k_dense_compact, k_dense_vote when asked for, the radix sort.
 int dense_list_grow(esl_ctx* c, DenseState& d, DenseOutArgs& k, size_t* temp_bytes);
 int dense_list_launch(esl_ctx* c, DenseState& d, DenseOutArgs& k, bool vote, size_t temp_bytes);
+// esl_dense_extract's gather of the first k.n_write voxels of the sorted list into the non-null outputs of `k` (after dense_list_launch,
+// inside the caller's ProfScope); esl_dense_render points them at buffers of its own
+void dense_gather_launch(esl_ctx* c, const DenseOutArgs& k);
+// step 2 on the host: R and t of every frame, from the given poses or (cams == nullptr) the resident camera states; an invalid pose
+// gives ESL_ERR_INVALID.  host / pose: the caller's staging vectors
+int dense_frames_poses(esl_ctx* c, const char* who, const double* cams, int F, std::vector<double>& host, std::vector<double>& pose);
 
 // esl_dense_planes' U_r: the indices i < n with state[i] == -2, ascending, into `list`, their number into *count (a stable rocprim
 // select; with tmp == nullptr only tmp_bytes is set).  Defined in esl_dense.hip beside the list's sort, for the reason given there.

@@ -33,6 +33,7 @@ EXPORTS = [
     "esl_debug_dense_allocs", "esl_dense_obj_params_default", "esl_dense_objects",
     "esl_dense_plane_params_default", "esl_dense_planes", "esl_debug_dense_planes_layout",
     "esl_dense_remove_frames", "esl_dense_move_frames", "esl_dense_slots_get", "esl_dense_purge",
+    "esl_dense_render_params_default", "esl_dense_render",
 ]
 
 
@@ -909,6 +910,73 @@ class Context:
         t, g = C.c_int32(0), C.c_int32(0)
         _check(load().esl_debug_dense_planes_layout(C.byref(t), C.byref(g)), "esl_debug_dense_planes_layout")
         return t.value, g.value
+
+    DENSE_RENDER_OUTPUTS = ("depth", "voxel", "bgr", "inst", "frame", "vox")
+
+    def dense_render(self, cams, K, rows, cols, depth_meas=None, params=None, want=DENSE_RENDER_OUTPUTS, vox_cap=None):
+        """esl_dense_render: the dense map's live voxels splatted into F frames, the nearest voxel kept per pixel, and the winners compared
+        with a measured depth.  cams (F, 7) Tcw or None for the resident camera states; depth_meas (F, rows, cols) uint16 or None; want
+        names the outputs to compute; vox_cap None = room for every voxel.  Returns a dict: result (status, n_voxels, n_small,
+        n_chunks) and, per name of want, depth (F, rows, cols) NaN where no voxel is drawn, voxel (F, rows, cols) index in
+        dense_extract's order or -1, bgr (F, rows, cols, 3) uint8, inst (F, rows, cols) label or -1, frame (F, 8) int32 n_drawn /
+        n_depth_out / n_outside / covered / agree / nearer / farther / no data, vox (min(vox_cap, n_voxels), 4) int32 won / agree /
+        nearer / farther; on an invalid map (result n_voxels = -1) the arrays are as they were allocated and vox is empty."""
+        p = params if params is not None else abi.default_dense_render_params()
+        want = set(want)
+        unknown = want - set(self.DENSE_RENDER_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        _ip, _up, _bp = C.POINTER(C.c_int32), C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)
+        if cams is None:
+            F, cp = self.graph_sizes()["n_cams"], None
+        else:
+            cams = np.ascontiguousarray(cams, dtype=np.float64).reshape(-1, 7)
+            F, cp = len(cams), (cams.ctypes.data_as(_dp) if len(cams) else None)
+        Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(4)
+        rows, cols = int(rows), int(cols)
+        mp = None
+        if depth_meas is not None:
+            depth_meas = np.ascontiguousarray(depth_meas, dtype=np.uint16)
+            if depth_meas.shape != (F, rows, cols):
+                raise ValueError(f"depth_meas has shape {depth_meas.shape}, expected {(F, rows, cols)}")
+            mp = depth_meas.ctypes.data_as(_up)          # an empty array has a valid address too
+        r, c = (rows, cols) if rows > 0 and cols > 0 else (0, 0)          # the library refuses such a shape before it writes
+        out = {}
+        if "depth" in want:
+            out["depth"] = np.full((F, r, c), np.nan)
+        if "voxel" in want:
+            out["voxel"] = np.full((F, r, c), -1, dtype=np.int32)
+        if "bgr" in want:
+            out["bgr"] = np.zeros((F, r, c, 3), dtype=np.uint8)
+        if "inst" in want:
+            out["inst"] = np.full((F, r, c), -1, dtype=np.int32)
+        if "frame" in want:
+            out["frame"] = np.zeros((F, 8), dtype=np.int32)
+        if "vox" in want:
+            if vox_cap is None:
+                vox_cap = max(self.dense_info()["n_voxels"], 0) if self._dense_begun() else 0
+            vox_cap = int(vox_cap)
+            out["vox"] = np.zeros((max(vox_cap, 0), 4), dtype=np.int32)
+        else:
+            vox_cap = 0
+
+        def optr(k, t):
+            return out[k].ctypes.data_as(t) if k in out and out[k].size else None
+        res = abi.EslDenseRenderResult()
+        t0 = time.perf_counter()
+        rc = load().esl_dense_render(self._h, cp, F, Kc.ctypes.data_as(_dp), rows, cols, mp, C.byref(p), optr("depth", _dp),
+                                     optr("voxel", _ip), optr("bgr", _bp), optr("inst", _ip), optr("frame", _ip), vox_cap,
+                                     optr("vox", _ip), C.byref(res))
+        self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
+        _check(rc, "esl_dense_render")
+        out["result"] = res.as_dict()
+        if "vox" in out:
+            out["vox"] = out["vox"][:min(vox_cap, max(res.n_voxels, 0))]
+        return out
+
+    def _dense_begun(self):
+        """whether esl_dense_info_get answers, i.e. a map was begun on this context"""
+        return load().esl_dense_info_get(self._h, C.byref(abi.EslDenseInfo())) == 0
 
     def dense_end(self):
         """esl_dense_end: forget the map (the buffers stay with the context)"""
