@@ -56,7 +56,8 @@ extern "C" {
                              *    dense map of many RGB-D frames (esl_dense_begin / _add_frames / _info_get / _extract / _end) with its
                              *    per-instance ellipsoids (esl_dense_objects) and its dominant planes and ground (esl_dense_planes), and
                              *    its exact de-integration (esl_dense_remove_frames / _move_frames / _purge / _slots_get), and its
-                             *    view from any pose, checked against measured depth (esl_dense_render) */
+                             *    view from any pose, checked against measured depth (esl_dense_render), and its per-voxel normals
+                             *    (esl_dense_normals) and the poses refined against it (esl_dense_align_frames) */
 #define ESL_MAX_TRACE 32
 
 typedef enum {
@@ -1210,6 +1211,109 @@ int esl_dense_render(esl_ctx* ctx,
                      int32_t* frame_out /* F x 8 or NULL: n_drawn, n_depth_out, n_outside, covered, agree, nearer, farther, no data */,
                      int64_t vox_cap, int32_t* vox_out /* vox_cap x 4 or NULL: won, agree, nearer, farther; the first min(vox_cap, n_voxels) rows written */,
                      esl_dense_render_result* out);
+
+/* ---- normals of the dense map (additive part of ABI 5: detect by the symbol) -------------------------------------------------------------
+ * Per live voxel, in esl_dense_extract's order: a unit normal, a curvature, a neighbour count and a valid flag, from the centroids of
+ * the voxel's neighbourhood.  For shading, meshing and plane patches, and what esl_dense_align_frames matches against.  The call reads
+ * the map and does not change it.  FP64 and integers; one voxel's sums are taken in one fixed order, so runs are bit-reproducible.
+ *  N1. Eligibility.  A voxel is eligible when it is live (dense-map step 9) and count >= min_count.  A live voxel that is not eligible
+ *      reports a zero normal, a NaN curvature, 0 neighbours and valid = 0.
+ *  N2. Neighbours.  The neighbours of an eligible voxel i are the eligible voxels among the (2 radius + 1)^3 keys around its key whose
+ *      components lie within +-(2^20 - 1), itself included; they are visited in ascending packed-key order.  A dead slot is no
+ *      neighbour (dense-map step 10).
+ *  N3. Moments.  c = the centroid of step 7 ((double)S_a / 2^30 / (double)count).  d_j = c_j - c_i; m = the number of neighbours;
+ *      s = the sum of d_j; M = the sum of d_j d_j^T as six entries xx, xy, xz, yy, yz, zz: all summed in visit order from 0, one product
+ *      and one add at a time.  u = s / m; C_ab = M_ab / m - u_a u_b; trace C = (C_xx + C_yy) + C_zz.
+ *  N4. Normal.  n = the eigenvector of the smallest eigenvalue of C by the cyclic Jacobi of esl_dense_planes' step 6 (8 sweeps over the
+ *      pivots (0,1), (0,2), (1,2); ties to the lowest index; re-normalised), turned so that its first non-zero component is positive.
+ *      lambda = n . (C n), each row of C n and the final product summed left to right; curvature = lambda / trace C.
+ *  N5. Validity.  valid = m >= min_neighbors and trace C > 0 and curvature <= max_curvature (the Jacobi runs only when the first two
+ *      hold).  An invalid voxel reports a zero normal, a NaN curvature and its m. */
+typedef struct {
+  double  max_curvature;  /* 0.05: lambda / trace above this (an edge, a corner, noise) is no surface; finite, >= 0 */
+  int32_t radius;         /* 1: the neighbourhood reaches this many keys on every axis; 1 or 2 */
+  int32_t min_count;      /* 1: voxels with fewer samples are neither given a normal nor counted as neighbours; >= 1 */
+  int32_t min_neighbors;  /* 5: fewer neighbours (the voxel included) give no normal; >= 1 */
+} esl_dense_normal_params;   /* 24 bytes; design choices, not values tuned on real data */
+void esl_dense_normal_params_default(esl_dense_normal_params* p);
+
+typedef struct { int32_t status, n_voxels, n_eligible, n_valid; } esl_dense_normal_result; /* 16 bytes */
+
+/* ESL_ERR_INVALID: null ctx or out; negative cap; max_curvature not finite or negative; radius outside 1 .. 2; min_count < 1;
+ * min_neighbors < 1.  ESL_ERR_STATE: no esl_dense_begin before.  The first min(cap, n_voxels) rows of every non-NULL output are written;
+ * n_voxels reports all.  On a map whose status is not 0 the call returns ESL_OK, the result reports that status and n_voxels = -1, and
+ * nothing else is written.  The buffers are a set of its own beside the dense map's, shared with esl_dense_align_frames (grow-only; a
+ * warm call allocates nothing: esl_debug_dense_allocs counts them; 61 bytes per voxel and 4 per table slot); one GPU, no collective,
+ * launches bracketed as kernel class 4. */
+int esl_dense_normals(esl_ctx* ctx, const esl_dense_normal_params* p /* NULL = defaults */, int64_t cap,
+                      double* normal_out /* cap x 3 or NULL */, double* curvature_out /* cap or NULL */,
+                      int32_t* neighbors_out /* cap or NULL */, uint8_t* valid_out /* cap or NULL */, esl_dense_normal_result* out);
+
+/* ---- aligning frames to the dense map: frame-to-model pose refinement (additive part of ABI 5: detect by the symbol) -------------------
+ * Given depth frames and pose guesses, find the poses at which the frames lie on the map: point-to-plane Gauss-Newton against the
+ * voxel centroids and their normals (steps N1 to N5, recomputed at the start of every call).  The step between esl_dense_render (does
+ * the map explain the image?) and esl_dense_move_frames (apply a new pose).  H of the last pass is the information matrix of the pose
+ * up to the residual's variance: a caller can put it into the graph as a prior.  The call reads the map and does not change it.  FP64
+ * and integers; every reduction over samples is an integer sum, so the call is bit-reproducible and a frame's result does not depend
+ * on the other frames of the call or on their order.  Per frame and per pass it = 0 .. iters (the last pass only evaluates):
+ *  a. Samples are formed by dense-map steps 1 to 3, exactly as esl_dense_add_frames forms them, with the map's own esl_dense_params but
+ *     this call's stride.  n_sampled, n_zero, n_depth_out, n_key_out and n_used mean what they mean there.
+ *  b. Match.  Candidates are the valid voxels (step N5) among the (2 reach + 1)^3 keys around the sample's key whose components lie
+ *     within +-(2^20 - 1).  d2 = ((p_w - c)_x^2 + (p_w - c)_y^2) + (p_w - c)_z^2.  The match is the candidate with the smallest d2, ties
+ *     to the smallest packed key.  No candidate counts in n_nomatch; d2 > max_dist^2 counts in n_far (max_dist = 0 means (reach + 1)
+ *     leaf; the square is one double computed on the host); the rest count in n_inlier.
+ *  c. Terms of an inlier.  o = R^T (0 - t), the camera centre (step 2 of the dense map at p_c = 0); q = p_w - o; r = p_w - c;
+ *     e = (n_x r_x + n_y r_y) + n_z r_z; J = (n, q x n) with (q x n)_x = q_y n_z - q_z n_y and so on.  The increment delta = (v, omega)
+ *     moves the centre by v and turns the frame about its centre by omega, in world axes: e changes by J . delta.  The 21 products
+ *     J_a J_b (a <= b, row after row), the 6 products J_a e and e^2 are each added as llrint(x 2^30) into an int64, the inlier count
+ *     beside them.  These 29 integers and the eight counts of steps a and b are the pass's row of 37 words.  Before anything runs:
+ *     Q = max(1, max_dist, depth_max sqrt(1 + X^2 + Y^2)) (1 + 2^-20), X = max(|cx|, |cols - 1 - cx|) / fx, Y alike, bounds |q|, |J_a| and
+ *     |e|; a call with (sampled pixels of a frame) (Q^2 2^30 + 1) >= 2^62 returns ESL_ERR_INVALID.
+ *  d. Step (host).  H_ab and g_a are the sums as doubles divided by 2^30.  If n_inlier < min_inliers the frame stops as too few.
+ *     A = H with A_aa = H_aa + damping H_aa; A = L L^T by Cholesky, every sum taken term after term; a pivot that is not > 0 or is below
+ *     min_pivot_ratio times the largest A_aa stops the frame as degenerate (a camera that sees one wall slides along it).  A stopped
+ *     frame keeps the pose this pass started from, and this pass is its evaluation.  Otherwise L L^T delta = -g; the quaternion is
+ *     divided by its norm as step 2 divides it; dq = (omega / 2, 1) divided by its norm; q_new = q (x) conj(dq) (Hamilton product);
+ *     o_new = o + v; t_new = -(R_new o_new) with R_new by step 2's formula.  No sine or cosine anywhere.  |v| <= tol_t and
+ *     |omega| <= tol_r stops the frame as converged: one more pass evaluates it at its new pose.  A frame that has stopped is skipped
+ *     by the later passes.
+ *  e. Outputs.  cams_out = the final poses.  frames_out: status (0 all iters taken, 1 converged, 2 too few, 3 degenerate), the steps
+ *     taken, the eight counts, sum_e2 = (the e^2 sum) / 2^30 and H of the frame's last pass, which is at its final pose, and |v|, |omega| of
+ *     its last step.  iter_out: per frame and pass the row of 37 words (zero for a pass the frame skipped).  On a map whose status is
+ *     not 0 the call returns ESL_OK, the result reports that status and n_voxels = -1, and nothing else is written. */
+typedef struct {
+  double  max_dist;         /* 0 = (reach + 1) leaf: a match farther than this is no inlier; finite, >= 0 */
+  double  damping;          /* 0: Levenberg's lambda on diag H; finite, >= 0 */
+  double  min_pivot_ratio;  /* 1e-6: a Cholesky pivot below this times the largest diagonal entry = degenerate; finite, >= 0 */
+  double  tol_t;            /* 1e-5 m; finite, >= 0 */
+  double  tol_r;            /* 1e-5 rad; finite, >= 0 */
+  int32_t iters;            /* 4: Gauss-Newton steps at most; 0 .. 64 (0 only evaluates) */
+  int32_t stride;           /* 2: every stride-th row and column from 0; >= 1 */
+  int32_t reach;            /* 1: the match is sought this many keys around the sample's; 0 .. 2 */
+  int32_t min_inliers;      /* 100; >= 1 */
+  esl_dense_normal_params normals;   /* steps N1 to N5 */
+} esl_dense_align_params;   /* 80 bytes; design choices, not values tuned on real data */
+void esl_dense_align_params_default(esl_dense_align_params* p);
+
+typedef struct {
+  int32_t status, iters;
+  int64_t n_sampled, n_zero, n_depth_out, n_key_out, n_used, n_nomatch, n_far, n_inlier;
+  double  sum_e2, H[36], step_t, step_r;
+} esl_dense_align_frame;    /* 384 bytes */
+typedef struct { int32_t status, n_voxels, n_valid, n_passes; } esl_dense_align_result; /* 16 bytes */
+
+/* Errors follow esl_dense_add_frames, case by case: ESL_ERR_STATE: no esl_dense_begin before; cams == NULL without a resident graph
+ * and states.  ESL_ERR_INVALID: null ctx, K, depth (with F > 0) or out; negative F; rows or cols < 1 or > 16384; fx or fy not finite or
+ * <= 0; an invalid pose (step 2); F differing from the resident graph's n_cams when cams == NULL; (sampled pixels of a frame) F reaching
+ * 2^31; a parameter outside the range its comment names; the bound of step c.  bgr and inst are not asked for.  F = 0 is valid.  The
+ * buffers are esl_dense_normals' set (a warm call of the same shape allocates nothing; 2 bytes per pixel, 296 per frame and pass
+ * beside the normals'); per pass the host uploads 12 doubles and a flag per frame and reads back 37 words per frame; one GPU, no
+ * collective, launches bracketed as kernel class 4. */
+int esl_dense_align_frames(esl_ctx* ctx, const double* cams /* F x 7 Tcw, the start poses; NULL = resident camera states */, int32_t F,
+                           const double K[4], int32_t rows, int32_t cols, const uint16_t* depth /* F x rows x cols */,
+                           const esl_dense_align_params* p /* NULL = defaults */, double* cams_out /* F x 7 or NULL */,
+                           esl_dense_align_frame* frames_out /* F or NULL */,
+                           int64_t* iter_out /* F x (iters + 1) x 37 or NULL */, esl_dense_align_result* out);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------*/
 /* Dense FP64-MFMA Cholesky factor + solve (the reduced-camera solver of SLAM mode) on a procedurally generated,

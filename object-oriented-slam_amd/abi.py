@@ -386,6 +386,74 @@ def default_dense_render_params(**kw):
     return p
 
 
+class EslDenseNormalParams(C.Structure):
+    """esl_dense_normal_params: the curvature gate, the neighbourhood and the counts of esl_dense_normals (steps N1 to N5)."""
+    _fields_ = [("max_curvature", C.c_double), ("radius", C.c_int32), ("min_count", C.c_int32), ("min_neighbors", C.c_int32), ("pad", C.c_int32)]
+
+
+class EslDenseNormalResult(C.Structure):
+    """esl_dense_normal_result: status 3 / 4 = an invalid map (n_voxels = -1); the eligible voxels and those with a valid normal."""
+    _fields_ = [("status", C.c_int32), ("n_voxels", C.c_int32), ("n_eligible", C.c_int32), ("n_valid", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class EslDenseAlignParams(C.Structure):
+    """esl_dense_align_params: the match gate, the step's guards, the stopping rule, the sampling and the normals of esl_dense_align_frames."""
+    _fields_ = [("max_dist", C.c_double), ("damping", C.c_double), ("min_pivot_ratio", C.c_double), ("tol_t", C.c_double), ("tol_r", C.c_double),
+                ("iters", C.c_int32), ("stride", C.c_int32), ("reach", C.c_int32), ("min_inliers", C.c_int32), ("normals", EslDenseNormalParams)]
+
+
+DENSE_ALIGN_COUNTS = ("n_sampled", "n_zero", "n_depth_out", "n_key_out", "n_used", "n_nomatch", "n_far", "n_inlier")
+DENSE_ALIGN_STATUS = {0: "max_iters", 1: "converged", 2: "too_few", 3: "degenerate"}
+DENSE_ALIGN_ROW = 37          # a frame's words per pass: 21 J J, 6 J e, e^2, the inlier count, the eight counts
+
+
+class EslDenseAlignFrame(C.Structure):
+    """esl_dense_align_frame: a frame's status, steps taken, the counts, sum e^2 and H of its last pass and the size of its last step."""
+    _fields_ = [("status", C.c_int32), ("iters", C.c_int32)] + [(k, C.c_int64) for k in DENSE_ALIGN_COUNTS] + [
+        ("sum_e2", C.c_double), ("H", C.c_double * 36), ("step_t", C.c_double), ("step_r", C.c_double)]
+
+
+class EslDenseAlignResult(C.Structure):
+    """esl_dense_align_result: status 3 / 4 = an invalid map (n_voxels = -1); the voxels with a valid normal; the passes run."""
+    _fields_ = [("status", C.c_int32), ("n_voxels", C.c_int32), ("n_valid", C.c_int32), ("n_passes", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert C.sizeof(EslDenseNormalParams) == 24 and C.sizeof(EslDenseNormalResult) == 16
+assert C.sizeof(EslDenseAlignParams) == 80 and C.sizeof(EslDenseAlignFrame) == 384 and C.sizeof(EslDenseAlignResult) == 16
+
+DENSE_NORMAL_DEFAULTS = dict(max_curvature=0.05, radius=1, min_count=1, min_neighbors=5)
+
+
+def default_dense_normal_params(**kw):
+    """esl_dense_normal_params_default: design choices, not values tuned on real data (include/esl.h)"""
+    p = EslDenseNormalParams(pad=0, **DENSE_NORMAL_DEFAULTS)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def default_dense_align_params(**kw):
+    """esl_dense_align_params_default (include/esl.h); a keyword that names a field of esl_dense_normal_params sets it in .normals"""
+    p = EslDenseAlignParams(max_dist=0.0, damping=0.0, min_pivot_ratio=1e-6, tol_t=1e-5, tol_r=1e-5, iters=4, stride=2, reach=1, min_inliers=100,
+                            normals=default_dense_normal_params())
+    for k, v in kw.items():
+        if k in DENSE_NORMAL_DEFAULTS:
+            setattr(p.normals, k, v)
+        elif k != "normals" and hasattr(p, k):
+            setattr(p, k, v)
+        else:
+            raise AttributeError(k)
+    return p
+
+
 def dense_argtypes(L):
     """the esl_dense_* calls take nullable pointers: declared, so that None passes as NULL and a wrong type raises"""
     dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
@@ -394,6 +462,16 @@ def dense_argtypes(L):
     L.esl_dense_render.argtypes = [C.c_void_p, dp, C.c_int32, dp, C.c_int32, C.c_int32, C.POINTER(C.c_uint16), C.POINTER(EslDenseRenderParams),
                                    dp, ip, C.POINTER(C.c_uint8), ip, ip, C.c_int64, ip, C.POINTER(EslDenseRenderResult)]
     L.esl_dense_render.restype = C.c_int
+    L.esl_dense_normal_params_default.argtypes = [C.POINTER(EslDenseNormalParams)]
+    L.esl_dense_normal_params_default.restype = None
+    L.esl_dense_normals.argtypes = [C.c_void_p, C.POINTER(EslDenseNormalParams), C.c_int64, dp, dp, ip, C.POINTER(C.c_uint8),
+                                    C.POINTER(EslDenseNormalResult)]
+    L.esl_dense_normals.restype = C.c_int
+    L.esl_dense_align_params_default.argtypes = [C.POINTER(EslDenseAlignParams)]
+    L.esl_dense_align_params_default.restype = None
+    L.esl_dense_align_frames.argtypes = [C.c_void_p, dp, C.c_int32, dp, C.c_int32, C.c_int32, C.POINTER(C.c_uint16), C.POINTER(EslDenseAlignParams),
+                                         dp, C.POINTER(EslDenseAlignFrame), lp, C.POINTER(EslDenseAlignResult)]
+    L.esl_dense_align_frames.restype = C.c_int
     L.esl_dense_params_default.argtypes = [C.POINTER(EslDenseParams)]
     L.esl_dense_params_default.restype = None
     L.esl_dense_begin.argtypes = [C.c_void_p, C.POINTER(EslDenseParams), C.c_int32, C.c_int32]

@@ -4,7 +4,7 @@
 // and 9) and the ground choice (step 9).  Plain C++ for host and device like esl_dense_obj.hpp, no HIP include:
 // tests/dense_planes_main.cpp compiles it with an ordinary compiler.  Every translation unit that includes it is built with
 // -ffp-contract=off.  What is `inline` only runs on the host: one compiler decides every bit of a plane.  The device uses
-// dobj_center / dobj_height (esl_dense_obj.hpp), dpl_inlier and the integer sampler.
+// dobj_center / dobj_height (esl_dense_obj.hpp), dpl_inlier, the integer sampler and, for esl_dense_normals, dpl_jacobi_min.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -80,12 +80,16 @@ inline int dpl_winner(const int* valid, const unsigned long long* hacc, int n_hy
 inline bool dpl_refit_kept(long long n, long long s, long long win_n, long long win_s) { return n > win_n || (n == win_n && s >= win_s); }
 
 // step 6: the eigenvector of the smallest eigenvalue (ties to the lowest index) of the symmetric C = {c00, c01, c02, c11, c12, c22}
-// by a cyclic Jacobi: kDplSweeps sweeps over the pivots (0,1), (0,2), (1,2), only + - * / sqrt; the vector is re-normalised
-inline void dpl_jacobi_min(const double C[6], double n[3]) {
+// by a cyclic Jacobi: kDplSweeps sweeps over the pivots (0,1), (0,2), (1,2), only + - * / sqrt; the vector is re-normalised.  Host
+// and device: esl_dense_normals runs it per voxel (esl_dense_align.hpp)
+ESL_DENSE_HD void dpl_jacobi_min(const double C[6], double n[3]) {
   double a[3][3] = {{C[0], C[1], C[2]}, {C[1], C[3], C[4]}, {C[2], C[4], C[5]}};
   double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
   const int P[3] = {0, 0, 1}, Q[3] = {1, 2, 2};
   for (int sweep = 0; sweep < kDplSweeps; ++sweep) {
+#if defined(__HIP_DEVICE_COMPILE__)   // constant pivots keep a and v in registers; the host's code is what it was
+#pragma unroll
+#endif
     for (int e = 0; e < 3; ++e) {
       const int p = P[e], q = Q[e];
       const double apq = a[p][q];
@@ -108,9 +112,9 @@ inline void dpl_jacobi_min(const double C[6], double n[3]) {
       }
     }
   }
-  int k = 0;
-  for (int e = 1; e < 3; ++e) if (a[e][e] < a[k][k]) k = e;
-  const double w[3] = {v[0][k], v[1][k], v[2][k]};
+  double lo = a[0][0], w[3] = {v[0][0], v[1][0], v[2][0]};   // the column of the smallest diagonal entry, the first of equals
+  for (int e = 1; e < 3; ++e)
+    if (a[e][e] < lo) { lo = a[e][e]; w[0] = v[0][e]; w[1] = v[1][e]; w[2] = v[2][e]; }
   const double nn = std::sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
   for (int e = 0; e < 3; ++e) n[e] = w[e] / nn;
 }

@@ -34,6 +34,7 @@ EXPORTS = [
     "esl_dense_plane_params_default", "esl_dense_planes", "esl_debug_dense_planes_layout",
     "esl_dense_remove_frames", "esl_dense_move_frames", "esl_dense_slots_get", "esl_dense_purge",
     "esl_dense_render_params_default", "esl_dense_render",
+    "esl_dense_normal_params_default", "esl_dense_normals", "esl_dense_align_params_default", "esl_dense_align_frames",
 ]
 
 
@@ -972,6 +973,66 @@ class Context:
         out["result"] = res.as_dict()
         if "vox" in out:
             out["vox"] = out["vox"][:min(vox_cap, max(res.n_voxels, 0))]
+        return out
+
+    def dense_normals(self, params=None, cap=None):
+        """esl_dense_normals: per live voxel, in dense_extract's order, the unit normal of its neighbourhood's centroids.  cap None = room
+        for every voxel.  Returns a dict: result (status, n_voxels, n_eligible, n_valid) and the first min(cap, n_voxels) rows of normal
+        (n, 3) (zero where invalid), curvature (n,) (NaN where invalid), neighbors (n,) int32 and valid (n,) uint8; on an invalid map
+        (result n_voxels = -1) the arrays are empty."""
+        p = params if params is not None else abi.default_dense_normal_params()
+        if cap is None:
+            cap = max(self.dense_info()["n_voxels"], 0) if self._dense_begun() else 0
+        cap = int(cap)
+        m = max(cap, 0)
+        nrm = np.zeros((m, 3)); curv = np.full(m, np.nan); nb = np.zeros(m, np.int32); val = np.zeros(m, np.uint8)
+        res = abi.EslDenseNormalResult()
+        t0 = time.perf_counter()
+        rc = load().esl_dense_normals(self._h, C.byref(p), cap, nrm.ctypes.data_as(_dp) if m else None, curv.ctypes.data_as(_dp) if m else None,
+                                      nb.ctypes.data_as(C.POINTER(C.c_int32)) if m else None,
+                                      val.ctypes.data_as(C.POINTER(C.c_uint8)) if m else None, C.byref(res))
+        self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
+        _check(rc, "esl_dense_normals")
+        n = min(m, max(res.n_voxels, 0))
+        return dict(result=res.as_dict(), normal=nrm[:n], curvature=curv[:n], neighbors=nb[:n], valid=val[:n])
+
+    def dense_align_frames(self, cams, K, rows, cols, depth, params=None, iters_out=True):
+        """esl_dense_align_frames: refine the poses of F depth frames against the dense map (point-to-plane Gauss-Newton on the voxels'
+        centroids and normals).  cams (F, 7) Tcw, the start poses, or None for the resident camera states; depth (F, rows, cols) uint16.
+        Returns a dict: result (status, n_voxels, n_valid, n_passes), cams (F, 7) the final poses, status / iters (F,) int32 (status 0 all
+        steps taken, 1 converged, 2 too few inliers, 3 degenerate), counts (F, 8) int64 in abi.DENSE_ALIGN_COUNTS' order, sum_e2 (F,),
+        H (F, 6, 6), step (F, 2) = |v|, |omega| of the last step, and with iters_out sums (F, iters + 1, 37) int64, a frame's words per
+        pass; on an invalid map (result n_voxels = -1) nothing was written and the arrays are as they were allocated."""
+        p = params if params is not None else abi.default_dense_align_params()
+        if cams is None:
+            F, cp = self.graph_sizes()["n_cams"], None
+        else:
+            cams = np.ascontiguousarray(cams, dtype=np.float64).reshape(-1, 7)
+            F, cp = len(cams), (cams.ctypes.data_as(_dp) if len(cams) else None)
+        Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(4)
+        rows, cols = int(rows), int(cols)
+        depth = np.ascontiguousarray(depth, dtype=np.uint16)
+        if depth.shape != (F, rows, cols):
+            raise ValueError(f"depth has shape {depth.shape}, expected {(F, rows, cols)}")
+        cams_out = np.zeros((F, 7))
+        fr = (abi.EslDenseAlignFrame * max(F, 1))()
+        sums = np.zeros((F, max(int(p.iters), 0) + 1, abi.DENSE_ALIGN_ROW), np.int64) if iters_out else None
+        res = abi.EslDenseAlignResult()
+        t0 = time.perf_counter()
+        rc = load().esl_dense_align_frames(self._h, cp, F, Kc.ctypes.data_as(_dp), rows, cols,
+                                           depth.ctypes.data_as(C.POINTER(C.c_uint16)) if F else None, C.byref(p),
+                                           cams_out.ctypes.data_as(_dp) if F else None, fr if F else None,
+                                           sums.ctypes.data_as(C.POINTER(C.c_int64)) if sums is not None and sums.size else None, C.byref(res))
+        self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
+        _check(rc, "esl_dense_align_frames")
+        out = dict(result=res.as_dict(), cams=cams_out,
+                   status=np.array([fr[f].status for f in range(F)], np.int32), iters=np.array([fr[f].iters for f in range(F)], np.int32),
+                   counts=np.array([[getattr(fr[f], k) for k in abi.DENSE_ALIGN_COUNTS] for f in range(F)], np.int64).reshape(F, 8),
+                   sum_e2=np.array([fr[f].sum_e2 for f in range(F)], np.float64),
+                   H=np.array([list(fr[f].H) for f in range(F)], np.float64).reshape(F, 6, 6),
+                   step=np.array([[fr[f].step_t, fr[f].step_r] for f in range(F)], np.float64).reshape(F, 2))
+        if sums is not None:
+            out["sums"] = sums
         return out
 
     def _dense_begun(self):

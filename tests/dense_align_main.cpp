@@ -1,0 +1,153 @@
+// dense_align_main.cpp — csrc/esl_dense_align.hpp on the host, without HIP: tests/test_dense_align_ref.py compiles it with the host
+// compiler (plain and with -fsanitize=address,undefined) and holds it to the numpy statement tests/dense_align_ref.py value by value.
+// Every number crosses as an integer: a double as its 64 bits, so that nothing is lost in print or scan.
+//   dense_align_main           self-checks of the classes, the gate and the bound; prints "dense_align ok"
+//   dense_align_main normal    stdin: "n min_neighbors max_curvature", then per voxel "k ci[3]" and k rows "cj[3]" (the neighbours in visit
+//                              order).  stdout per voxel: "m valid n[3] curvature"
+//   dense_align_main match     stdin: "n", then per sample "k pw[3]" and k rows "c[3]" (the candidates in visit order).  stdout per sample:
+//                              "best d2" (best = the candidate's position, -1 without one)
+//   dense_align_main terms     stdin: "n o[3]", then n rows "pw[3] c[3] n[3]".  stdout per row: the 28 terms
+//   dense_align_main step      stdin: "n", then per frame "T[28] n_inlier min_inliers damping min_pivot_ratio cam[7]".  stdout per frame:
+//                              "status H[36] g[6] delta[6] ok cam_new[7] |v| |omega|"
+#include <cinttypes>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../object-oriented-slam_amd/csrc/esl_dense_align.hpp"
+
+using namespace esl;
+
+#define CHECK(x)                                                       \
+  do {                                                                 \
+    if (!(x)) {                                                        \
+      std::printf("FAILED line %d: %s\n", __LINE__, #x);               \
+      return 1;                                                        \
+    }                                                                  \
+  } while (0)
+
+static bool get_i(long long* v) { return std::scanf("%lld", v) == 1; }
+static bool get_d(double* v) {
+  uint64_t b;
+  if (std::scanf("%" SCNu64, &b) != 1) return false;
+  std::memcpy(v, &b, 8);
+  return true;
+}
+static bool get_ds(double* v, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!get_d(v + i)) return false;
+  return true;
+}
+static void put_d(double v) {
+  uint64_t b;
+  std::memcpy(&b, &v, 8);
+  std::printf(" %" PRIu64, b);
+}
+
+static int self_check() {
+  CHECK(dal_class(false, 0.0, 1.0) == DAL_CLASS_NOMATCH && dal_class(true, 1.0, 1.0) == DAL_CLASS_INLIER && dal_class(true, 1.5, 1.0) == DAL_CLASS_FAR);
+  CHECK(dal_max_dist2(0.0, 1, 0.25) == 0.25 && dal_max_dist2(0.5, 2, 0.25) == 0.25 && dal_max_dist2(0.0, 0, 0.5) == 0.25);
+  const double K[4] = {1.0, 1.0, 0.0, 0.0};
+  CHECK(dal_bound(K, 1, 1, 0.5, 0.0) == 1.0 + 1.0 / 1048576.0);          // never below |n| = 1
+  CHECK(dal_bound(K, 1, 1, 4.0, 0.0) == 4.0 * (1.0 + 1.0 / 1048576.0));
+  CHECK(dal_sums_fit(1ll << 20, 2.0) && !dal_sums_fit(1ll << 30, 2.0) && !dal_sums_fit(1, std::nan("")));
+  const double pw[3] = {0.5, 0.25, 0.125}, o[3] = {0, 0, 0}, c[3] = {0.5, 0.25, 0.0}, n[3] = {0, 0, 1};
+  long long T[kDalSums];
+  dal_terms(pw, o, c, n, T);
+  CHECK(T[27] == (1ll << 30) / 64 && T[23] == (1ll << 30) / 8 && T[11] == (1ll << 30));          // e = 1/8: e^2, n_z e, n_z n_z
+  CHECK(T[15] == (1ll << 30) / 16 && T[18] == (1ll << 30) / 4);                                    // (q x n) = (1/4, -1/2, 0)
+  double s[3] = {0, 0, 0}, M[6] = {0, 0, 0, 0, 0, 0}, nn[3], curv;
+  int m = 0;
+  dnr_add(c, c, &m, s, M);
+  CHECK(m == 1 && !dnr_finish(m, s, M, 1, 1.0, nn, &curv) && nn[2] == 0 && curv != curv);          // trace 0: no normal
+  std::printf("dense_align ok\n");
+  return 0;
+}
+
+static int normal() {
+  long long n, min_neighbors;
+  double max_curv;
+  if (!get_i(&n) || !get_i(&min_neighbors) || !get_d(&max_curv) || n < 0) return 2;
+  for (long long i = 0; i < n; ++i) {
+    long long k;
+    double ci[3], cj[3], s[3] = {0, 0, 0}, M[6] = {0, 0, 0, 0, 0, 0}, nr[3], curv;
+    int m = 0;
+    if (!get_i(&k) || !get_ds(ci, 3) || k < 0) return 2;
+    for (long long j = 0; j < k; ++j) {
+      if (!get_ds(cj, 3)) return 2;
+      dnr_add(ci, cj, &m, s, M);
+    }
+    const bool ok = dnr_finish(m, s, M, (int)min_neighbors, max_curv, nr, &curv);
+    std::printf("%d %d", m, ok ? 1 : 0);
+    put_d(nr[0]); put_d(nr[1]); put_d(nr[2]); put_d(curv);
+    std::printf("\n");
+  }
+  return 0;
+}
+
+static int match() {
+  long long n;
+  if (!get_i(&n) || n < 0) return 2;
+  for (long long i = 0; i < n; ++i) {
+    long long k, best = -1;
+    double pw[3], c[3], best_d2 = 0;
+    if (!get_i(&k) || !get_ds(pw, 3) || k < 0) return 2;
+    for (long long j = 0; j < k; ++j) {
+      if (!get_ds(c, 3)) return 2;
+      const double d2 = dal_dist2(pw, c);
+      if (best < 0 || d2 < best_d2) { best = j; best_d2 = d2; }          // k_dal_accum's rule
+    }
+    std::printf("%lld", best);
+    put_d(best_d2);
+    std::printf("\n");
+  }
+  return 0;
+}
+
+static int terms() {
+  long long n;
+  double o[3];
+  if (!get_i(&n) || !get_ds(o, 3) || n < 0) return 2;
+  for (long long i = 0; i < n; ++i) {
+    double v[9];
+    long long T[kDalSums];
+    if (!get_ds(v, 9)) return 2;
+    dal_terms(v, o, v + 3, v + 6, T);
+    for (int k = 0; k < kDalSums; ++k) std::printf(k ? " %lld" : "%lld", T[k]);
+    std::printf("\n");
+  }
+  return 0;
+}
+
+static int step() {
+  long long n;
+  if (!get_i(&n) || n < 0) return 2;
+  for (long long i = 0; i < n; ++i) {
+    long long T[kDalSums], n_inlier, min_inliers;
+    double damping, ratio, cam[7], H[36], g[6], delta[6], next[7];
+    for (long long& t : T)
+      if (!get_i(&t)) return 2;
+    if (!get_i(&n_inlier) || !get_i(&min_inliers) || !get_d(&damping) || !get_d(&ratio) || !get_ds(cam, 7)) return 2;
+    dal_system(T, H, g);
+    const int st = dal_solve(H, g, n_inlier, (int)min_inliers, damping, ratio, delta);
+    const bool ok = dal_update(cam, delta, next);
+    std::printf("%d", st);
+    for (double v : H) put_d(v);
+    for (double v : g) put_d(v);
+    for (double v : delta) put_d(v);
+    std::printf(" %d", ok ? 1 : 0);
+    for (double v : next) put_d(v);
+    put_d(dal_norm3(delta)); put_d(dal_norm3(delta + 3));
+    std::printf(" %d\n", dal_converged(delta, 1e-5, 1e-5) ? 1 : 0);
+  }
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && std::strcmp(argv[1], "normal") == 0) return normal();
+  if (argc > 1 && std::strcmp(argv[1], "match") == 0) return match();
+  if (argc > 1 && std::strcmp(argv[1], "terms") == 0) return terms();
+  if (argc > 1 && std::strcmp(argv[1], "step") == 0) return step();
+  return self_check();
+}
