@@ -57,7 +57,8 @@ extern "C" {
                              *    per-instance ellipsoids (esl_dense_objects) and its dominant planes and ground (esl_dense_planes), and
                              *    its exact de-integration (esl_dense_remove_frames / _move_frames / _purge / _slots_get), and its
                              *    view from any pose, checked against measured depth (esl_dense_render), and its per-voxel normals
-                             *    (esl_dense_normals) and the poses refined against it (esl_dense_align_frames) */
+                             *    (esl_dense_normals) and the poses refined against it (esl_dense_align_frames), and the carving of the
+                             *    voxels that later frames see through (esl_dense_carve_frames) */
 #define ESL_MAX_TRACE 32
 
 typedef enum {
@@ -1314,6 +1315,93 @@ int esl_dense_align_frames(esl_ctx* ctx, const double* cams /* F x 7 Tcw, the st
                            const esl_dense_align_params* p /* NULL = defaults */, double* cams_out /* F x 7 or NULL */,
                            esl_dense_align_frame* frames_out /* F or NULL */,
                            int64_t* iter_out /* F x (iters + 1) x 37 or NULL */, esl_dense_align_result* out);
+
+/* ---- carving the dense map: drop the voxels that later frames see through (additive part of ABI 5: detect by the symbol) -----------------
+ * An object that stood in some frames and was moved stays in the dense map as a ghost: esl_dense_objects fits it, esl_dense_align_frames
+ * matches against it, esl_dense_render draws it.  esl_dense_carve_frames is the classical space-carving test per (voxel, frame): project
+ * the voxel into an observer frame, read the measured depth around that pixel, ask whether the camera saw past the voxel.  The map stays
+ * a function of the multiset of its samples (dense-map step 8 and what follows it): the call never clears a record.  It decides which
+ * voxels are seen through, finds the pixels of the OWNER frames whose samples lie in those voxels, hands back the owners' depth images
+ * without them and, when asked, removes exactly those samples by dense-map step 8.  Everything is FP64 and integers; every choice is a
+ * comparison and every sum an integer sum, so runs are bit-reproducible in any frame order and any split of the observers over calls.
+ *  C1. Voxels.  The live voxels of the map in ascending packed-key order: the list, the index i and the xyz that esl_dense_extract
+ *      would give at the moment of the call.
+ *  C2. Observation of voxel i in observer frame f.  Poses are validated and turned into R, t on the host as dense-map step 2 does.
+ *      p_c as step 2 of esl_dense_render; z = p_c[2] must pass z >= depth_min && z <= depth_max (a NaN fails), else the pair counts in
+ *      the frame's depth out.  u = (fx p_c[0]) / z + cx, v = (fy p_c[1]) / z + cy: multiply, then divide, then add.  If u or v is not
+ *      finite or exceeds 2^30 in magnitude the pair counts in the frame's outside.  col = floor(u + 0.5), row = floor(v + 0.5), compared
+ *      as doubles; the centre pixel must lie in the image (0 <= col <= cols - 1, 0 <= row <= rows - 1), else outside.  Otherwise the
+ *      pair is in view.  The window is [col - window, col + window] x [row - window, row + window] clipped to the image.  Every pixel of
+ *      the window is classed against z by step 6 of esl_render_map word for word (agree, nearer, farther, no data) with this call's
+ *      depth_scale, depth_min, depth_max and depth_tol.  The observation's class: agree if any pixel agrees; else nearer if any is
+ *      nearer (something stands in front: the voxel is occluded); else through if any is farther; else no data.  Exactly one class per
+ *      pair in view.
+ *  C3. Counts.  vox_out[4 i ..] = agree, nearer, through, no data of voxel i, summed over the observers.  obs_out[8 f ..] = in view,
+ *      depth out, outside, agree, nearer, through, no data, 0 of frame f, summed over the voxels.  All integer sums.
+ *  C4. Verdict.  Voxel i is carved iff through >= min_through and through >= through_per_agree agree (the product as a 64-bit
+ *      integer).  n_tested = the voxels with agree + nearer + through > 0.  A voxel's verdict depends on that voxel and the observers
+ *      alone, never on another voxel.
+ *  C5. Owners' samples.  Every owner frame's samples are formed by dense-map steps 1 to 3 exactly as esl_dense_add_frames forms them:
+ *      the map's own esl_dense_params and stride, cams_own and depth_own.  A used sample whose key has a live voxel counts in the
+ *      frame's found, one without in its not found; own_out[4 f ..] = used, found, carved, not found.  A found sample whose voxel is
+ *      carved is carved: mask_out = 1 and depth_kept_out = 0 at its pixel.  Every other pixel keeps its raw value and mask 0: unsampled
+ *      pixels, zero, out of range, not found, not carved.
+ *  C6. Apply.  With apply = 1 the call then performs dense-map step 8 on the owner frames with depth images that hold the raw value at
+ *      the carved pixels and 0 elsewhere, and bgr_own / inst_own as given; its result goes to `removed`.  The map is then the map of
+ *      esl_dense_begin plus one add of the owners with depth_kept_out, plus whatever other frames it held: the same bytes in extract,
+ *      objects, planes and info; only esl_dense_slots_get differs (the carved voxels' slots are dead until a purge).  A later
+ *      esl_dense_remove_frames / _move_frames of an owner takes its kept image.  vox_out / carved_out refer to the list before the
+ *      removal.  With apply = 0 the map is untouched but for the best words and the shared sorted list, as with every extracting call,
+ *      and `removed` is zero.
+ *  C7. Map status.  On a map whose status is not 0 the call returns ESL_OK, the result reports that status and n_voxels = -1, and
+ *      nothing else is written.
+ * Limits: window <= 4; rows, cols <= 16384; every count is an int32; F_obs <= 65535 (a voxel's four counts are accumulated as four
+ * 16-bit fields of one 64-bit word).  Not part of this call: carving by rendered visibility, a TSDF, a purge after the removal
+ * (esl_dense_purge), images kept on the device between calls, more than one GPU. */
+typedef struct {
+  double  depth_scale;        /* 5000: raw units per metre of depth_obs; finite, > 0 */
+  double  depth_min;          /* 0.1: the gate of a voxel's z and of a measured sample (step C2); finite, >= 0 */
+  double  depth_max;          /* 6.0: finite, >= depth_min, <= 4095 */
+  double  depth_tol;          /* 0.05 m: |z_meas - z| <= depth_tol agrees; finite, >= 0 */
+  int32_t window;             /* 1: the pixels read around the centre pixel reach this far; 0 .. 4 */
+  int32_t min_through;        /* 2: a carved voxel was seen through at least this often; >= 1 */
+  int32_t through_per_agree;  /* 1: and at least this many times per agreeing observation; >= 0 */
+  int32_t apply;              /* 0: 1 = remove the carved samples from the map (step C6); 0 or 1 */
+} esl_dense_carve_params;   /* 48 bytes; design choices, not values tuned on real data */
+void esl_dense_carve_params_default(esl_dense_carve_params* p);
+
+typedef struct {
+  int32_t status, n_voxels, n_tested, n_carved;
+  int64_t samples_found, samples_carved;   /* summed over the owner frames */
+  esl_dense_remove_result removed;          /* step C6; zeros when apply = 0 */
+} esl_dense_carve_result;   /* 96 bytes */
+
+/* Errors follow esl_dense_render and esl_dense_remove_frames, case by case and in this order.  ESL_ERR_INVALID: null ctx or out;
+ * negative F_obs or F_own; null K; rows or cols < 1 or > 16384; fx or fy not finite or <= 0; negative vox_cap; depth_scale not finite or
+ * <= 0; depth_min, depth_max or depth_tol not finite or negative; depth_min > depth_max; depth_max > 4095; window outside 0 .. 4;
+ * min_through < 1; through_per_agree < 0; apply not 0 or 1; F_obs > 65535; null depth_obs with F_obs > 0; null cams_own or depth_own
+ * with F_own > 0.  ESL_ERR_STATE: no esl_dense_begin before; with apply = 1 and F_own > 0, bgr_own or inst_own NULL when esl_dense_begin
+ * asked for them; cams_obs == NULL without a resident graph and states.  ESL_ERR_INVALID again: F_obs differing from the resident
+ * graph's n_cams when cams_obs == NULL; an invalid pose among the observers, then among the owners; the owners' sampled pixels reaching
+ * 2^31.  A refused call changes nothing.  F_obs = 0, F_own = 0 and an empty map are valid; any output may be NULL (vox_out and
+ * carved_out receive the first min(vox_cap, n_voxels) rows).  Its buffers are a set of its own beside the dense map's (grow-only; a warm
+ * call of the same shape allocates nothing: esl_debug_dense_allocs counts them; 2 bytes per observer pixel, 2 per owner pixel, 1 more with
+ * mask_out and 2 more with apply = 1, 49 per voxel, 1 per table slot); with apply = 1 the carved-depth images travel to the host and back through
+ * esl_dense_remove_frames' own upload.  One GPU, no collective, launches bracketed as kernel class 4. */
+int esl_dense_carve_frames(esl_ctx* ctx,
+                           const double* cams_obs /* F_obs x 7 Tcw, the frames that vote; NULL = resident camera states */, int32_t F_obs,
+                           const uint16_t* depth_obs /* F_obs x rows x cols */,
+                           const double* cams_own /* F_own x 7: frames that are in the map, with the poses they were added with */, int32_t F_own,
+                           const uint16_t* depth_own /* F_own x rows x cols, as added */,
+                           const uint8_t* bgr_own /* F_own x rows x cols x 3 or NULL */, const int32_t* inst_own /* F_own x rows x cols or NULL */,
+                           const double K[4], int32_t rows, int32_t cols, const esl_dense_carve_params* p /* NULL = defaults */,
+                           int64_t vox_cap, int32_t* vox_out /* vox_cap x 4 or NULL: agree, nearer, through, no data */,
+                           uint8_t* carved_out /* vox_cap or NULL */,
+                           int32_t* obs_out /* F_obs x 8 or NULL: in view, depth out, outside, agree, nearer, through, no data, 0 */,
+                           uint16_t* depth_kept_out /* F_own x rows x cols or NULL */,
+                           uint8_t* mask_out /* F_own x rows x cols or NULL: 1 = carved sample */,
+                           int32_t* own_out /* F_own x 4 or NULL: used, found, carved, not found */,
+                           esl_dense_carve_result* out);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------*/
 /* Dense FP64-MFMA Cholesky factor + solve (the reduced-camera solver of SLAM mode) on a procedurally generated,

@@ -454,9 +454,48 @@ def default_dense_align_params(**kw):
     return p
 
 
+class EslDenseCarveParams(C.Structure):
+    """esl_dense_carve_params: the depth gates, the window, the verdict's two thresholds and whether the carved samples are removed."""
+    _fields_ = [("depth_scale", C.c_double), ("depth_min", C.c_double), ("depth_max", C.c_double), ("depth_tol", C.c_double),
+                ("window", C.c_int32), ("min_through", C.c_int32), ("through_per_agree", C.c_int32), ("apply", C.c_int32)]
+
+
+class EslDenseCarveResult(C.Structure):
+    """esl_dense_carve_result: status 3 / 4 = an invalid map (n_voxels = -1); the voxels tested and carved, the owners' samples found and
+    carved, and the removal's own result (zeros with apply = 0)."""
+    _fields_ = [("status", C.c_int32), ("n_voxels", C.c_int32), ("n_tested", C.c_int32), ("n_carved", C.c_int32),
+                ("samples_found", C.c_int64), ("samples_carved", C.c_int64), ("removed", EslDenseRemoveResult)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "removed"}
+        d["removed"] = self.removed.as_dict()
+        return d
+
+
+assert C.sizeof(EslDenseCarveParams) == 48 and C.sizeof(EslDenseCarveResult) == 96
+
+DENSE_CARVE_DEFAULTS = dict(depth_scale=5000.0, depth_min=0.1, depth_max=6.0, depth_tol=0.05, window=1, min_through=2, through_per_agree=1, apply=0)
+
+
+def default_dense_carve_params(**kw):
+    """esl_dense_carve_params_default: design choices, not values tuned on real data (include/esl.h)"""
+    p = EslDenseCarveParams(**DENSE_CARVE_DEFAULTS)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
 def dense_argtypes(L):
     """the esl_dense_* calls take nullable pointers: declared, so that None passes as NULL and a wrong type raises"""
     dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    up, bp = C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)
+    L.esl_dense_carve_params_default.argtypes = [C.POINTER(EslDenseCarveParams)]
+    L.esl_dense_carve_params_default.restype = None
+    L.esl_dense_carve_frames.argtypes = [C.c_void_p, dp, C.c_int32, up, dp, C.c_int32, up, bp, ip, dp, C.c_int32, C.c_int32,
+                                         C.POINTER(EslDenseCarveParams), C.c_int64, ip, bp, ip, up, bp, ip, C.POINTER(EslDenseCarveResult)]
+    L.esl_dense_carve_frames.restype = C.c_int
     L.esl_dense_render_params_default.argtypes = [C.POINTER(EslDenseRenderParams)]
     L.esl_dense_render_params_default.restype = None
     L.esl_dense_render.argtypes = [C.c_void_p, dp, C.c_int32, dp, C.c_int32, C.c_int32, C.POINTER(C.c_uint16), C.POINTER(EslDenseRenderParams),

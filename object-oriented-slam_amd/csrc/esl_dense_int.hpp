@@ -1,9 +1,9 @@
-// esl_dense_int.hpp — what the five units of the dense map share: esl_dense.hip (the map), esl_dense_objects.hip and
-// esl_dense_planes.hip (the two extractors that read it), esl_dense_render.hip (the view of it) and esl_dense_align.hip (its normals
-// and the poses refined against it).  The record and the counters, the map's state and its buffers, the probes of
+// esl_dense_int.hpp — what the six units of the dense map share: esl_dense.hip (the map), esl_dense_objects.hip and
+// esl_dense_planes.hip (the two extractors that read it), esl_dense_render.hip (the view of it), esl_dense_align.hip (its normals
+// and the poses refined against it) and esl_dense_carve.hip (the voxels that later frames see through).  The record and the counters, the map's state and its buffers, the probes of
 // the voxel table, the sorted list of the live voxels (DenseOutArgs, dense_list_grow / _launch: defined in esl_dense.hip, whose
-// kernels they launch) and the entries' small helpers.  Internal: only those five units include it.
-// The rule of all five: every store to global memory is a vector store or an atomic in plain C++; no loop waits for another thread: a
+// kernels they launch) and the entries' small helpers.  Internal: only those six units include it.
+// The rule of all six: every store to global memory is a vector store or an atomic in plain C++; no loop waits for another thread: a
 // probe that finds no slot within the table's size, or a map over its capacity, raises the sticky status 3 and gives up.
 #pragma once
 #include <algorithm>
@@ -36,6 +36,8 @@ static_assert(sizeof(esl_dense_normal_result) == 16, "include/esl.h states this 
 static_assert(sizeof(esl_dense_align_params) == 80, "include/esl.h states this size");
 static_assert(sizeof(esl_dense_align_frame) == 384, "include/esl.h states this size");
 static_assert(sizeof(esl_dense_align_result) == 16, "include/esl.h states this size");
+static_assert(sizeof(esl_dense_carve_params) == 48, "include/esl.h states this size");
+static_assert(sizeof(esl_dense_carve_result) == 96, "include/esl.h states this size");
 
 constexpr int kDenseThreads = 256;
 typedef unsigned long long u64;
@@ -53,13 +55,14 @@ enum { DC_SAMPLED, DC_ZERO, DC_DEPTH_OUT, DC_KEY_OUT, DC_USED, DC_VOXELS, DC_PAI
 // pose set and esl_dense_purge's live records and pairs.  Each extractor keeps a set of its own, its slots named in its unit.
 enum { DB_KEYS, DB_REC, DB_PKEYS, DB_PCNT, DB_CTR, DB_POSE, DB_DEPTH, DB_BGR, DB_INST, DB_LKEY, DB_LVAL, DB_SKEY, DB_SVAL, DB_TEMP,
        DB_OKEY, DB_OXYZ, DB_OCNT, DB_OBGR, DB_OINST, DB_OVOTES, DB_POSE2, DB_XKEY, DB_XREC, DB_XPKEY, DB_XPID, DB_XPCNT, DB_COUNT };
-constexpr int kDobjBufs = 17, kDplBufs = 12, kDrnBufs = 14, kDalBufs = 11;   // the lengths of the other units' own enums (asserted there)
+constexpr int kDobjBufs = 17, kDplBufs = 12, kDrnBufs = 14, kDalBufs = 11, kDcvBufs = 14;   // the lengths of the other units' own enums (asserted there)
 struct DenseState {
   ScratchSet<DB_COUNT> set;
   ScratchSet<kDobjBufs> obj_set;   // esl_dense_objects
   ScratchSet<kDplBufs> pl_set;     // esl_dense_planes
   ScratchSet<kDrnBufs> rn_set;     // esl_dense_render
   ScratchSet<kDalBufs> al_set;     // esl_dense_normals, esl_dense_align_frames
+  ScratchSet<kDcvBufs> cv_set;     // esl_dense_carve_frames
   bool begun = false, combine = true;
   esl_dense_params p;
   int with_color = 0, with_inst = 0;
@@ -69,6 +72,8 @@ struct DenseState {
   int status = 0;
   std::vector<double> cams, pose, cams2, pose2;   // host staging of a call's poses (esl_dense_move_frames: both sets)
   std::vector<int> moved;                         // esl_dense_move_frames: the frames whose pose changed
+  std::vector<uint16_t> carved_depth;             // esl_dense_carve_frames with apply = 1: the images its removal takes
+  std::vector<int32_t> carve_own;                 // and the owner frames' four counts
 };
 
 __device__ __forceinline__ u64 dense_hash(u64 k) {   // hash64 of esl_fit.hip

@@ -35,6 +35,7 @@ EXPORTS = [
     "esl_dense_remove_frames", "esl_dense_move_frames", "esl_dense_slots_get", "esl_dense_purge",
     "esl_dense_render_params_default", "esl_dense_render",
     "esl_dense_normal_params_default", "esl_dense_normals", "esl_dense_align_params_default", "esl_dense_align_frames",
+    "esl_dense_carve_params_default", "esl_dense_carve_frames",
 ]
 
 
@@ -1033,6 +1034,82 @@ class Context:
                    step=np.array([[fr[f].step_t, fr[f].step_r] for f in range(F)], np.float64).reshape(F, 2))
         if sums is not None:
             out["sums"] = sums
+        return out
+
+    DENSE_CARVE_OUTPUTS = ("vox", "carved", "obs", "depth_kept", "mask", "own")
+
+    def dense_carve_frames(self, cams_obs, depth_obs, cams_own, depth_own, K, rows, cols, bgr_own=None, inst_own=None, params=None,
+                           want=DENSE_CARVE_OUTPUTS, vox_cap=None):
+        """esl_dense_carve_frames: which live voxels of the dense map do the observer frames see through, which samples of the owner
+        frames lie in them, and (params.apply = 1) their removal.  cams_obs (F_obs, 7) Tcw or None for the resident camera states,
+        depth_obs (F_obs, rows, cols) uint16; cams_own (F_own, 7), depth_own / bgr_own / inst_own as the owners were added; want names
+        the outputs to compute; vox_cap None = room for every voxel.  Returns a dict: result (status, n_voxels, n_tested, n_carved,
+        samples_found, samples_carved, removed) and, per name of want, vox (min(vox_cap, n_voxels), 4) int32 agree / nearer / through /
+        no data, carved (min(vox_cap, n_voxels),) uint8, obs (F_obs, 8) int32 in view / depth out / outside / agree / nearer / through /
+        no data / 0, depth_kept (F_own, rows, cols) uint16, mask (F_own, rows, cols) uint8, own (F_own, 4) int32 used / found / carved /
+        not found; on an invalid map (result n_voxels = -1) the arrays are as they were allocated and vox, carved are empty."""
+        p = params if params is not None else abi.default_dense_carve_params()
+        want = set(want)
+        unknown = want - set(self.DENSE_CARVE_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        _ip, _up, _bp = C.POINTER(C.c_int32), C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)
+        rows, cols = int(rows), int(cols)
+        if cams_obs is None:
+            Fo, cop = self.graph_sizes()["n_cams"], None
+        else:
+            cams_obs = np.ascontiguousarray(cams_obs, dtype=np.float64).reshape(-1, 7)
+            Fo, cop = len(cams_obs), (cams_obs.ctypes.data_as(_dp) if len(cams_obs) else None)
+        cams_own = np.ascontiguousarray(np.zeros((0, 7)) if cams_own is None else cams_own, dtype=np.float64).reshape(-1, 7)
+        Fw = len(cams_own)
+
+        def img(a, F, dt, t, what, tail=()):
+            if a is None:
+                return None, None
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.shape != (F, rows, cols) + tail:
+                raise ValueError(f"{what} has shape {a.shape}, expected {(F, rows, cols) + tail}")
+            return a, a.ctypes.data_as(t)          # an empty array has a valid address too
+        depth_obs, dop = img(depth_obs, Fo, np.uint16, _up, "depth_obs")
+        depth_own, dwp = img(depth_own, Fw, np.uint16, _up, "depth_own")
+        bgr_own, bwp = img(bgr_own, Fw, np.uint8, _bp, "bgr_own", (3,))
+        inst_own, iwp = img(inst_own, Fw, np.int32, _ip, "inst_own")
+        Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(4)
+        r, c = (rows, cols) if rows > 0 and cols > 0 else (0, 0)          # the library refuses such a shape before it writes
+        if "vox" in want or "carved" in want:
+            if vox_cap is None:
+                vox_cap = max(self.dense_info()["n_voxels"], 0) if self._dense_begun() else 0
+            vox_cap = int(vox_cap)
+        else:
+            vox_cap = 0
+        out = {}
+        if "vox" in want:
+            out["vox"] = np.zeros((max(vox_cap, 0), 4), dtype=np.int32)
+        if "carved" in want:
+            out["carved"] = np.zeros(max(vox_cap, 0), dtype=np.uint8)
+        if "obs" in want:
+            out["obs"] = np.zeros((Fo, 8), dtype=np.int32)
+        if "depth_kept" in want:
+            out["depth_kept"] = np.zeros((Fw, r, c), dtype=np.uint16)
+        if "mask" in want:
+            out["mask"] = np.zeros((Fw, r, c), dtype=np.uint8)
+        if "own" in want:
+            out["own"] = np.zeros((Fw, 4), dtype=np.int32)
+
+        def optr(k, t):
+            return out[k].ctypes.data_as(t) if k in out and out[k].size else None
+        res = abi.EslDenseCarveResult()
+        t0 = time.perf_counter()
+        rc = load().esl_dense_carve_frames(self._h, cop, Fo, dop, cams_own.ctypes.data_as(_dp) if Fw else None, Fw, dwp, bwp, iwp,
+                                           Kc.ctypes.data_as(_dp), rows, cols, C.byref(p), vox_cap, optr("vox", _ip), optr("carved", _bp),
+                                           optr("obs", _ip), optr("depth_kept", _up), optr("mask", _bp), optr("own", _ip), C.byref(res))
+        self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
+        _check(rc, "esl_dense_carve_frames")
+        out["result"] = res.as_dict()
+        m = min(vox_cap, max(res.n_voxels, 0))
+        for k in ("vox", "carved"):
+            if k in out:
+                out[k] = out[k][:m]
         return out
 
     def _dense_begun(self):
