@@ -24,6 +24,7 @@
 // esl_dense_objects.hip, esl_dense_planes.hip and esl_dense_render.hip work on that sorted list; what they share with this unit, and
 // the rule that every kernel of the four keeps, is esl_dense_int.hpp's.
 #include "esl_dense_int.hpp"
+#include "esl_dense_check.hpp"
 
 #include <rocprim/rocprim.hpp>   // after <cstring>: its headers call memset unqualified
 
@@ -55,10 +56,7 @@ static __global__ __launch_bounds__(kDenseThreads) void k_dense_insert(DenseArgs
   const long long i = (long long)blockIdx.x * kDenseThreads + threadIdx.x;
   const bool in = i < per;
   int row = 0, col = 0;
-  if (in) {
-    const int sr = (int)(i / a.scols);
-    row = sr * a.stride; col = (int)(i - (long long)sr * a.scols) * a.stride;   // row < rows, col < cols
-  }
+  if (in) { const DensePixel p = dense_sample_pixel(i, a.stride, a.scols); row = p.row; col = p.col; }
   for (int f = blockIdx.y; f < a.F; f += gridDim.y) {
     const double* P = a.pose + (size_t)f * kDensePose;
     int cat = -1, id = -1;
@@ -68,6 +66,7 @@ static __global__ __launch_bounds__(kDenseThreads) void k_dense_insert(DenseArgs
       const size_t px = ((size_t)f * a.rows + row) * a.cols + col;
       double pc[3], pw[3];
       int k[3];
+      // dense_sample_key's three calls, written out: through the helper the four listings change
       cat = dense_sample(a.depth[px], col, row, a.K, a.depth_scale, a.depth_min, a.depth_max, pc);
       if (cat == DENSE_USED) {
         dense_world(P, pc, pw);
@@ -359,37 +358,40 @@ void dense_release(esl_ctx* c) {   // called by esl_ctx_destroy
   c->dense = nullptr;
 }
 
-int dense_list_grow(esl_ctx* c, DenseState& d, DenseOutArgs& k, size_t* temp_bytes) {
+int dense_list_begin(esl_ctx* c, DenseState& d, DenseList& L) {
   ScratchSet<DB_COUNT>& s = d.set;
+  DenseOutArgs& k = L.k;
   const size_t n = (size_t)d.n_voxels;
   std::memset(&k, 0, sizeof(k));
   if (const int rc = s.grow(c, DB_LKEY, n * sizeof(u64))) return rc;
   if (const int rc = s.grow(c, DB_LVAL, n * sizeof(unsigned int))) return rc;
   if (const int rc = s.grow(c, DB_SKEY, n * sizeof(u64))) return rc;
   if (const int rc = s.grow(c, DB_SVAL, n * sizeof(unsigned int))) return rc;
-  *temp_bytes = 0;
-  ESL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, *temp_bytes, s.at<u64>(DB_LKEY), s.at<u64>(DB_SKEY), s.at<unsigned int>(DB_LVAL),
+  L.temp_bytes = 0;
+  ESL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, L.temp_bytes, s.at<u64>(DB_LKEY), s.at<u64>(DB_SKEY), s.at<unsigned int>(DB_LVAL),
                                         s.at<unsigned int>(DB_SVAL), n, 0, 63, c->stream));
-  if (const int rc = s.grow(c, DB_TEMP, *temp_bytes)) return rc;
+  if (const int rc = s.grow(c, DB_TEMP, L.temp_bytes)) return rc;
   k.keys = s.at<u64>(DB_KEYS); k.rec = s.at<DenseRec>(DB_REC);
   k.H = d.H; k.P = 2 * d.H; k.ctr = s.at<u64>(DB_CTR);
   k.lkey = s.at<u64>(DB_LKEY); k.lval = s.at<unsigned int>(DB_LVAL); k.list_cap = (u64)n;
   k.skey = s.at<u64>(DB_SKEY); k.sval = s.at<unsigned int>(DB_SVAL);
+  // k_dense_compact counts from 0.  Nothing between here and the caller's dense_list_launch reads or writes the word: the clear is an
+  // independent command on the one stream, wherever among the caller's own clears and uploads it stands
+  ESL_HIP_TRY(hipMemsetAsync(k.ctr + DC_LIST, 0, sizeof(u64), c->stream));
   return ESL_OK;
 }
 
-int dense_list_launch(esl_ctx* c, DenseState& d, DenseOutArgs& k, bool vote, size_t temp_bytes) {
+int dense_list_launch(esl_ctx* c, DenseState& d, DenseList& L, bool vote, bool gather) {
   ScratchSet<DB_COUNT>& s = d.set;
+  DenseOutArgs& k = L.k;
   if (vote) { k.pkeys = s.at<u64>(DB_PKEYS); k.pcnt = s.at<unsigned int>(DB_PCNT); }
   hipLaunchKernelGGL(k_dense_compact, dim3(dense_blocks(k.H)), dim3(kDenseThreads), 0, c->stream, k);
   if (vote) hipLaunchKernelGGL(k_dense_vote, dim3(dense_blocks(k.P)), dim3(kDenseThreads), 0, c->stream, k);
-  ESL_HIP_TRY(rocprim::radix_sort_pairs(s.buf[DB_TEMP], temp_bytes, s.at<u64>(DB_LKEY), s.at<u64>(DB_SKEY),
+  ESL_HIP_TRY(rocprim::radix_sort_pairs(s.buf[DB_TEMP], L.temp_bytes, s.at<u64>(DB_LKEY), s.at<u64>(DB_SKEY),
                                         s.at<unsigned int>(DB_LVAL), s.at<unsigned int>(DB_SVAL), (size_t)d.n_voxels, 0, 63, c->stream));
+  if (gather && k.n_write > 0)   // no caller asks with n_write == 0; an empty grid is no launch
+    hipLaunchKernelGGL(k_dense_gather, dim3(dense_blocks((u64)k.n_write)), dim3(kDenseThreads), 0, c->stream, k);
   return ESL_OK;
-}
-
-void dense_gather_launch(esl_ctx* c, const DenseOutArgs& k) {
-  hipLaunchKernelGGL(k_dense_gather, dim3(dense_blocks((u64)k.n_write)), dim3(kDenseThreads), 0, c->stream, k);
 }
 
 // esl_dense_planes' select (esl_dense_int.hpp).  It stays in this unit: without rocprim::select's device code beside them the
@@ -511,11 +513,7 @@ int dense_frames_check(esl_ctx* c, const char* who, int32_t F, const double K[4]
                        const uint8_t* bgr, const int32_t* inst, bool res_cams) {
   if (!c) return dense_fail(ESL_ERR_INVALID, who, "null ctx");
   if (F < 0) return dense_fail(ESL_ERR_INVALID, who, "negative F");
-  if (!K) return dense_fail(ESL_ERR_INVALID, who, "null K");
-  if (rows < 1 || rows > kDenseMaxDim) return dense_fail(ESL_ERR_INVALID, who, "rows < 1 or > 16384");
-  if (cols < 1 || cols > kDenseMaxDim) return dense_fail(ESL_ERR_INVALID, who, "cols < 1 or > 16384");
-  if (!std::isfinite(K[0]) || !(K[0] > 0)) return dense_fail(ESL_ERR_INVALID, who, "fx not finite or <= 0");
-  if (!std::isfinite(K[1]) || !(K[1] > 0)) return dense_fail(ESL_ERR_INVALID, who, "fy not finite or <= 0");
+  if (const char* m = dense_image_check(K, rows, cols)) return dense_fail(ESL_ERR_INVALID, who, m);
   if (F > 0 && !depth) return dense_fail(ESL_ERR_INVALID, who, "null depth");
   const DenseState* d = dense_begun(c, who);
   if (!d) return ESL_ERR_STATE;
@@ -763,9 +761,9 @@ extern "C" int esl_dense_extract(esl_ctx* c, int64_t cap, int32_t* key_out, doub
   if (nw == 0 || !any) return ESL_OK;
   ESL_HIP_TRY(hipSetDevice(c->device));
   ScratchSet<DB_COUNT>& s = d.set;
-  DenseOutArgs k;
-  size_t temp_bytes = 0;
-  if (const int rc = dense_list_grow(c, d, k, &temp_bytes)) return rc;
+  DenseList L;
+  if (const int rc = dense_list_begin(c, d, L)) return rc;
+  DenseOutArgs& k = L.k;
   if (key_out) { if (const int rc = s.grow(c, DB_OKEY, (size_t)nw * 3 * sizeof(int32_t))) return rc; k.okey = s.at<int>(DB_OKEY); }
   if (xyz_out) { if (const int rc = s.grow(c, DB_OXYZ, (size_t)nw * 3 * sizeof(double))) return rc; k.oxyz = s.at<double>(DB_OXYZ); }
   if (count_out) { if (const int rc = s.grow(c, DB_OCNT, (size_t)nw * sizeof(int32_t))) return rc; k.ocnt = s.at<int>(DB_OCNT); }
@@ -774,11 +772,9 @@ extern "C" int esl_dense_extract(esl_ctx* c, int64_t cap, int32_t* key_out, doub
   if (votes_out) { if (const int rc = s.grow(c, DB_OVOTES, (size_t)nw * sizeof(int32_t))) return rc; k.ovotes = s.at<int>(DB_OVOTES); }
   k.n_write = nw; k.with_color = d.with_color;
   const bool vote = d.with_inst && (inst_out || votes_out);
-  ESL_HIP_TRY(hipMemsetAsync(k.ctr + DC_LIST, 0, sizeof(u64), c->stream));
   {
     ProfScope ps(c, 4);
-    if (const int rc = dense_list_launch(c, d, k, vote, temp_bytes)) return rc;
-    dense_gather_launch(c, k);
+    if (const int rc = dense_list_launch(c, d, L, vote, true)) return rc;
   }
   ESL_HIP_TRY(hipGetLastError());
   if (key_out) ESL_HIP_TRY(hipMemcpyAsync(key_out, k.okey, (size_t)nw * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));

@@ -6,8 +6,8 @@
 //                   record, sums the moments in that order and runs the Jacobi in registers.  No atomics but the two counts (ballot +
 //                   popcount): the per-lane loop is the summation order.
 //   k_dal_accum     grid = (sampled pixels / 256, frames); a workgroup's frame is uniform, so its R, t, K and its flag are scalar loads
-//                   and a stopped frame is skipped by a uniform branch.  One lane per sample does steps a to c: the sample as
-//                   k_dense_insert forms it, (2 reach + 1)^3 probes, slot -> index -> valid, centroid and normal, the 28 terms.  The 29
+//                   and a stopped frame is skipped by a uniform branch.  One lane per sample does steps a to c: the sample as k_dense_insert
+//                   forms it (dense_sample_pixel / _key), (2 reach + 1)^3 probes, slot -> index -> valid, centroid and normal, the 28 terms.  The 29
 //                   integers are folded across the wave by a shuffle butterfly, the waves meet in LDS, and one 64-bit atomicAdd per
 //                   workgroup and non-zero term goes into the frame's row; the eight counts by ballot + popcount, one atomic per wave
 //                   and count.  No atomic returns a value.
@@ -15,6 +15,7 @@
 // up, 37 words per frame come back.
 #include "esl_dense_int.hpp"
 #include "esl_dense_align.hpp"
+#include "esl_dense_check.hpp"
 
 namespace esl {
 
@@ -95,10 +96,7 @@ static __global__ __launch_bounds__(kDenseThreads) void k_dal_accum(DalArgs a) {
   const long long i = (long long)blockIdx.x * kDenseThreads + threadIdx.x;
   const bool in = i < per;
   int row = 0, col = 0;
-  if (in) {
-    const int sr = (int)(i / a.scols);
-    row = sr * a.stride; col = (int)(i - (long long)sr * a.scols) * a.stride;   // row < rows, col < cols
-  }
+  if (in) { const DensePixel p = dense_sample_pixel(i, a.stride, a.scols); row = p.row; col = p.col; }
   for (int f = blockIdx.y; f < a.F; f += gridDim.y) {   // at most F rounds; workgroup-uniform, and so is the flag
     if (a.flag[f] == 0) continue;
     const double* P = a.pose + (size_t)f * kDensePose;
@@ -112,11 +110,7 @@ static __global__ __launch_bounds__(kDenseThreads) void k_dal_accum(DalArgs a) {
       const size_t px = ((size_t)f * a.rows + row) * a.cols + col;
       double pc[3], pw[3];
       int k[3];
-      cat = dense_sample(a.depth[px], col, row, a.K, a.depth_scale, a.depth_min, a.depth_max, pc);
-      if (cat == DENSE_USED) {
-        dense_world(P, pc, pw);
-        if (!dense_key(pw, a.leaf, k)) cat = DENSE_KEY_OUT;
-      }
+      cat = dense_sample_key(a.depth[px], col, row, a.K, a.depth_scale, a.depth_min, a.depth_max, P, a.leaf, pc, pw, k);
       if (cat == DENSE_USED) {
         long long best = -1;
         double best_d2 = 0;
@@ -190,39 +184,28 @@ extern "C" void esl_dense_align_params_default(esl_dense_align_params* p) {
 
 namespace {
 
-int dnr_params_check(const char* who, const esl_dense_normal_params& p) {
-  if (!std::isfinite(p.max_curvature) || p.max_curvature < 0) return dense_fail(ESL_ERR_INVALID, who, "max_curvature not finite or negative");
-  if (p.radius < 1 || p.radius > kDnrMaxRadius) return dense_fail(ESL_ERR_INVALID, who, "radius outside 1 .. 2");
-  if (p.min_count < 1) return dense_fail(ESL_ERR_INVALID, who, "min_count < 1");
-  if (p.min_neighbors < 1) return dense_fail(ESL_ERR_INVALID, who, "min_neighbors < 1");
-  return ESL_OK;
-}
-
 // Steps N1 to N5 over the map as it is: the sorted list, the centroids (extract's gather) and the normals into al_set, sidx rebuilt.
 // counts: DAC_*.  The caller has checked the map's status and set the device.
 int dnr_run(esl_ctx* c, DenseState& d, const esl_dense_normal_params& p, DnrArgs& a, u64 counts[DAC_COUNT]) {
   ScratchSet<DA_COUNT>& s = d.al_set;
   const size_t n = (size_t)d.n_voxels;
-  DenseOutArgs k;
-  size_t temp_bytes = 0;
-  if (const int rc = dense_list_grow(c, d, k, &temp_bytes)) return rc;
+  DenseList L;
+  if (const int rc = dense_list_begin(c, d, L)) return rc;
+  DenseOutArgs& k = L.k;
   const DenseSlot want[] = {{DA_XYZ, n * 3 * sizeof(double)}, {DA_SIDX, (size_t)d.H * sizeof(int32_t)}, {DA_NRM, n * 3 * sizeof(double)},
                             {DA_CURV, n * sizeof(double)}, {DA_M, n * sizeof(int32_t)}, {DA_VALID, n}, {DA_CTR, DAC_COUNT * sizeof(u64)}};
-  for (const DenseSlot& w : want)
-    if (const int rc = s.grow(c, w.slot, w.bytes)) return rc;
+  if (const int rc = dense_grow(c, s, want, false)) return rc;
   std::memset(&a, 0, sizeof(a));
   a.keys = k.keys; a.rec = k.rec; a.H = k.H; a.skey = k.skey; a.sval = k.sval; a.n = (int)n;
   a.radius = p.radius; a.min_count = p.min_count; a.min_neighbors = p.min_neighbors; a.max_curvature = p.max_curvature;
   a.sidx = s.at<int>(DA_SIDX); a.nrm = s.at<double>(DA_NRM); a.curv = s.at<double>(DA_CURV); a.m = s.at<int>(DA_M);
   a.valid = s.at<unsigned char>(DA_VALID); a.ctr = s.at<u64>(DA_CTR);
   k.oxyz = s.at<double>(DA_XYZ); k.n_write = (long long)n; k.with_color = d.with_color;
-  ESL_HIP_TRY(hipMemsetAsync(k.ctr + DC_LIST, 0, sizeof(u64), c->stream));
   ESL_HIP_TRY(hipMemsetAsync(a.ctr, 0, DAC_COUNT * sizeof(u64), c->stream));
   ESL_HIP_TRY(hipMemsetAsync(a.sidx, 0xFF, (size_t)d.H * sizeof(int32_t), c->stream));   // every slot -1
   if (n > 0) {
     ProfScope ps(c, 4);
-    if (const int rc = dense_list_launch(c, d, k, false, temp_bytes)) return rc;
-    dense_gather_launch(c, k);
+    if (const int rc = dense_list_launch(c, d, L, false, true)) return rc;
     hipLaunchKernelGGL(k_dnr_normals, dim3(dense_blocks((u64)n)), dim3(kDenseThreads), 0, c->stream, a);
   }
   ESL_HIP_TRY(hipGetLastError());
@@ -230,8 +213,6 @@ int dnr_run(esl_ctx* c, DenseState& d, const esl_dense_normal_params& p, DnrArgs
   ESL_HIP_TRY(hipStreamSynchronize(c->stream));
   return ESL_OK;
 }
-
-bool dal_nonneg(double v) { return std::isfinite(v) && v >= 0; }
 
 }  // namespace
 
@@ -243,11 +224,11 @@ extern "C" int esl_dense_normals(esl_ctx* c, const esl_dense_normal_params* pp, 
   if (cap < 0) return dense_fail(ESL_ERR_INVALID, who, "negative cap");
   esl_dense_normal_params p;
   if (pp) p = *pp; else esl_dense_normal_params_default(&p);
-  if (const int rc = dnr_params_check(who, p)) return rc;
+  if (const char* m = dnr_params_check(p)) return dense_fail(ESL_ERR_INVALID, who, m);
   if (!dense_begun(c, who)) return ESL_ERR_STATE;
   DenseState& d = *c->dense;
   std::memset(out, 0, sizeof(*out));
-  if (d.status) { out->status = d.status; out->n_voxels = -1; return ESL_OK; }
+  if (dense_map_invalid(d, out)) return ESL_OK;
   ESL_HIP_TRY(hipSetDevice(c->device));
   DnrArgs a;
   u64 counts[DAC_COUNT];
@@ -271,30 +252,17 @@ extern "C" int esl_dense_align_frames(esl_ctx* c, const double* cams, int32_t F,
   if (!c) return dense_fail(ESL_ERR_INVALID, who, "null ctx");
   if (!out) return dense_fail(ESL_ERR_INVALID, who, "null out");
   if (F < 0) return dense_fail(ESL_ERR_INVALID, who, "negative F");
-  if (!K) return dense_fail(ESL_ERR_INVALID, who, "null K");
-  if (rows < 1 || rows > kDenseMaxDim) return dense_fail(ESL_ERR_INVALID, who, "rows < 1 or > 16384");
-  if (cols < 1 || cols > kDenseMaxDim) return dense_fail(ESL_ERR_INVALID, who, "cols < 1 or > 16384");
-  if (!std::isfinite(K[0]) || !(K[0] > 0)) return dense_fail(ESL_ERR_INVALID, who, "fx not finite or <= 0");
-  if (!std::isfinite(K[1]) || !(K[1] > 0)) return dense_fail(ESL_ERR_INVALID, who, "fy not finite or <= 0");
+  if (const char* m = dense_image_check(K, rows, cols)) return dense_fail(ESL_ERR_INVALID, who, m);
   if (!std::isfinite(K[2]) || !std::isfinite(K[3])) return dense_fail(ESL_ERR_INVALID, who, "cx or cy not finite");
   if (F > 0 && !depth) return dense_fail(ESL_ERR_INVALID, who, "null depth");
   esl_dense_align_params p;
   if (pp) p = *pp; else esl_dense_align_params_default(&p);
-  if (!dal_nonneg(p.max_dist)) return dense_fail(ESL_ERR_INVALID, who, "max_dist not finite or negative");
-  if (!dal_nonneg(p.damping)) return dense_fail(ESL_ERR_INVALID, who, "damping not finite or negative");
-  if (!dal_nonneg(p.min_pivot_ratio)) return dense_fail(ESL_ERR_INVALID, who, "min_pivot_ratio not finite or negative");
-  if (!dal_nonneg(p.tol_t)) return dense_fail(ESL_ERR_INVALID, who, "tol_t not finite or negative");
-  if (!dal_nonneg(p.tol_r)) return dense_fail(ESL_ERR_INVALID, who, "tol_r not finite or negative");
-  if (p.iters < 0 || p.iters > kDalMaxIters) return dense_fail(ESL_ERR_INVALID, who, "iters outside 0 .. 64");
-  if (p.stride < 1) return dense_fail(ESL_ERR_INVALID, who, "stride < 1");
-  if (p.reach < 0 || p.reach > kDalMaxReach) return dense_fail(ESL_ERR_INVALID, who, "reach outside 0 .. 2");
-  if (p.min_inliers < 1) return dense_fail(ESL_ERR_INVALID, who, "min_inliers < 1");
-  if (const int rc = dnr_params_check(who, p.normals)) return rc;
+  if (const char* m = dal_params_check(p)) return dense_fail(ESL_ERR_INVALID, who, m);
   if (!dense_begun(c, who)) return ESL_ERR_STATE;
   if (const int rc = resident_source_check(c, who, !cams && F > 0, F, false, 0)) return rc;
   DenseState& d = *c->dense;
   std::memset(out, 0, sizeof(*out));
-  if (d.status) { out->status = d.status; out->n_voxels = -1; return ESL_OK; }   // step e: the map is invalid, nothing is written
+  if (dense_map_invalid(d, out)) return ESL_OK;   // step e: nothing is written
   ESL_HIP_TRY(hipSetDevice(c->device));
   if (F > 0) {
     if (const int rc = dense_frames_poses(c, who, cams, F, d.cams, d.pose)) return rc;

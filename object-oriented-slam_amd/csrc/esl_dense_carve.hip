@@ -10,7 +10,7 @@
 //                   verdict as a byte at the voxel's table slot (through the sorted list's slot values), n_carved and n_tested by
 //                   ballot + popcount.
 //   k_dcv_mark      one lane per sampled pixel of an owner frame, the frame uniform per workgroup.  The sample by k_dense_insert's
-//                   header functions (dense-map steps 1 to 3), dense_lookup (nothing is claimed), a live test on the record's count, the
+//                   header functions (dense_sample_pixel, steps 1 to 3 as in dense_sample_key), dense_lookup (nothing is claimed), a live count, the
 //                   slot's byte.  Only a carved pixel is written: 0 into the kept image (which starts as a device copy of depth_own), the
 //                   raw value into the cleared carved-depth image, 1 into the cleared mask.  The frame's four counts by ballot +
 //                   popcount.
@@ -19,6 +19,7 @@
 // the removal's kernels as they are.  The copy costs 2 bytes per owner pixel down and, inside the removal, 2 up again.
 #include "esl_dense_int.hpp"
 #include "esl_dense_carve.hpp"
+#include "esl_dense_check.hpp"
 
 namespace esl {
 
@@ -118,10 +119,7 @@ static __global__ __launch_bounds__(kDenseThreads) void k_dcv_mark(DcvArgs a) {
   const long long i = (long long)blockIdx.x * kDenseThreads + threadIdx.x;
   const bool in = i < per;
   int row = 0, col = 0;
-  if (in) {
-    const int sr = (int)(i / a.scols);
-    row = sr * a.stride; col = (int)(i - (long long)sr * a.scols) * a.stride;   // row < rows, col < cols
-  }
+  if (in) { const DensePixel p = dense_sample_pixel(i, a.stride, a.scols); row = p.row; col = p.col; }
   for (int f = blockIdx.y; f < a.F_own; f += gridDim.y) {   // at most F_own rounds; workgroup-uniform
     const double* P = a.pose_own + (size_t)f * kDensePose;
     bool used = false, found = false, carve = false;
@@ -130,6 +128,7 @@ static __global__ __launch_bounds__(kDenseThreads) void k_dcv_mark(DcvArgs a) {
       const unsigned raw = a.kept[px];   // still depth_own's value: only this lane writes this pixel
       double pc[3], pw[3];
       int k[3];
+      // dense_sample_key's three calls, written out: through the helper the listing changes
       if (dense_sample(raw, col, row, a.K, a.m_scale, a.m_min, a.m_max, pc) == DENSE_USED) {
         dense_world(P, pc, pw);
         if (dense_key(pw, a.leaf, k)) {
@@ -176,24 +175,11 @@ extern "C" int esl_dense_carve_frames(esl_ctx* c, const double* cams_obs, int32_
   if (!out) return dense_fail(ESL_ERR_INVALID, who, "null out");
   if (F_obs < 0) return dense_fail(ESL_ERR_INVALID, who, "negative F_obs");
   if (F_own < 0) return dense_fail(ESL_ERR_INVALID, who, "negative F_own");
-  if (!K) return dense_fail(ESL_ERR_INVALID, who, "null K");
-  if (rows < 1 || rows > kDenseMaxDim) return dense_fail(ESL_ERR_INVALID, who, "rows < 1 or > 16384");
-  if (cols < 1 || cols > kDenseMaxDim) return dense_fail(ESL_ERR_INVALID, who, "cols < 1 or > 16384");
-  if (!std::isfinite(K[0]) || !(K[0] > 0)) return dense_fail(ESL_ERR_INVALID, who, "fx not finite or <= 0");
-  if (!std::isfinite(K[1]) || !(K[1] > 0)) return dense_fail(ESL_ERR_INVALID, who, "fy not finite or <= 0");
+  if (const char* m = dense_image_check(K, rows, cols)) return dense_fail(ESL_ERR_INVALID, who, m);
   if (vox_cap < 0) return dense_fail(ESL_ERR_INVALID, who, "negative vox_cap");
   esl_dense_carve_params p;
   if (pp) p = *pp; else esl_dense_carve_params_default(&p);
-  if (!std::isfinite(p.depth_scale) || !(p.depth_scale > 0)) return dense_fail(ESL_ERR_INVALID, who, "depth_scale not finite or <= 0");
-  if (!std::isfinite(p.depth_min) || p.depth_min < 0) return dense_fail(ESL_ERR_INVALID, who, "depth_min not finite or negative");
-  if (!std::isfinite(p.depth_max) || p.depth_max < 0) return dense_fail(ESL_ERR_INVALID, who, "depth_max not finite or negative");
-  if (!std::isfinite(p.depth_tol) || p.depth_tol < 0) return dense_fail(ESL_ERR_INVALID, who, "depth_tol not finite or negative");
-  if (p.depth_min > p.depth_max) return dense_fail(ESL_ERR_INVALID, who, "depth_min > depth_max");
-  if (p.depth_max > kDrnDepthMax) return dense_fail(ESL_ERR_INVALID, who, "depth_max > 4095");
-  if (p.window < 0 || p.window > kDcvMaxWindow) return dense_fail(ESL_ERR_INVALID, who, "window outside 0 .. 4");
-  if (p.min_through < 1) return dense_fail(ESL_ERR_INVALID, who, "min_through < 1");
-  if (p.through_per_agree < 0) return dense_fail(ESL_ERR_INVALID, who, "negative through_per_agree");
-  if (p.apply != 0 && p.apply != 1) return dense_fail(ESL_ERR_INVALID, who, "apply not 0 or 1");
+  if (const char* m = dcv_params_check(p)) return dense_fail(ESL_ERR_INVALID, who, m);
   if (F_obs > kDcvMaxObs) return dense_fail(ESL_ERR_INVALID, who, "F_obs > 65535");
   if (F_obs > 0 && !depth_obs) return dense_fail(ESL_ERR_INVALID, who, "null depth_obs");
   if (F_own > 0 && !cams_own) return dense_fail(ESL_ERR_INVALID, who, "null cams_own");
@@ -204,7 +190,7 @@ extern "C" int esl_dense_carve_frames(esl_ctx* c, const double* cams_obs, int32_
   if (p.apply && F_own > 0 && d.with_inst && !inst_own) return dense_fail(ESL_ERR_STATE, who, "null inst_own on a map begun with labels");
   if (const int rc = resident_source_check(c, who, !cams_obs && F_obs > 0, F_obs, false, 0)) return rc;
   std::memset(out, 0, sizeof(*out));
-  if (d.status) { out->status = d.status; out->n_voxels = -1; return ESL_OK; }   // step C7
+  if (dense_map_invalid(d, out)) return ESL_OK;   // step C7
   ESL_HIP_TRY(hipSetDevice(c->device));
   // the poses: R and t of every frame on the host, before anything runs
   if (F_obs > 0) {
@@ -221,10 +207,10 @@ extern "C" int esl_dense_carve_frames(esl_ctx* c, const double* cams_obs, int32_
   const bool apply = p.apply && F_own > 0, want_mask = mask_out && F_own > 0;
   out->n_voxels = (int32_t)n;
   ScratchSet<DV_COUNT>& s = d.cv_set;
-  DenseOutArgs k;
-  size_t temp_bytes = 0;
+  DenseList L;
+  DenseOutArgs& k = L.k;
   if (n > 0) {
-    if (const int rc = dense_list_grow(c, d, k, &temp_bytes)) return rc;
+    if (const int rc = dense_list_begin(c, d, L)) return rc;
   }
   {
     const size_t sn = (size_t)n;
@@ -235,9 +221,7 @@ extern "C" int esl_dense_carve_frames(esl_ctx* c, const double* cams_obs, int32_
                               {DV_POSE_OWN, (size_t)F_own * kDensePose * sizeof(double)}, {DV_KEPT, n_own * sizeof(uint16_t)},
                               {DV_CDEPTH, apply ? n_own * sizeof(uint16_t) : 0}, {DV_MASK, want_mask ? n_own : 0},
                               {DV_OWN, (size_t)F_own * DVO_COUNT * sizeof(int32_t)}};
-    for (const DenseSlot& w : want)
-      if (w.bytes)
-        if (const int rc = s.grow(c, w.slot, w.bytes)) return rc;
+    if (const int rc = dense_grow(c, s, want, true)) return rc;
   }
   DcvArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -270,12 +254,10 @@ extern "C" int esl_dense_carve_frames(esl_ctx* c, const double* cams_obs, int32_
     k.oxyz = s.at<double>(DV_XYZ);
     k.n_write = n; k.with_color = d.with_color;
     a.sval = k.sval;
-    ESL_HIP_TRY(hipMemsetAsync(k.ctr + DC_LIST, 0, sizeof(u64), c->stream));
     ESL_HIP_TRY(hipMemsetAsync(a.acc, 0, (size_t)n * sizeof(u64), c->stream));
     {
       ProfScope ps(c, 4);
-      if (const int rc = dense_list_launch(c, d, k, false, temp_bytes)) return rc;
-      dense_gather_launch(c, k);
+      if (const int rc = dense_list_launch(c, d, L, false, true)) return rc;
       if (F_obs > 0) hipLaunchKernelGGL(k_dcv_observe, dim3(dense_blocks((u64)n), (unsigned)a.n_chunks), blk, 0, c->stream, a);
       hipLaunchKernelGGL(k_dcv_verdict, dim3(dense_blocks((u64)n)), blk, 0, c->stream, a);
     }

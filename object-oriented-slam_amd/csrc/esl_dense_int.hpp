@@ -1,8 +1,10 @@
 // esl_dense_int.hpp — what the six units of the dense map share: esl_dense.hip (the map), esl_dense_objects.hip and
 // esl_dense_planes.hip (the two extractors that read it), esl_dense_render.hip (the view of it), esl_dense_align.hip (its normals
-// and the poses refined against it) and esl_dense_carve.hip (the voxels that later frames see through).  The record and the counters, the map's state and its buffers, the probes of
-// the voxel table, the sorted list of the live voxels (DenseOutArgs, dense_list_grow / _launch: defined in esl_dense.hip, whose
-// kernels they launch) and the entries' small helpers.  Internal: only those six units include it.
+// and the poses refined against it) and esl_dense_carve.hip (the voxels that later frames see through).  The record and the counters,
+// the map's state and its buffers, the probes of the voxel table, the sorted list of the live voxels as one step (DenseList,
+// dense_list_begin / _launch: defined in esl_dense.hip, whose kernels they launch), the growth of a unit's own buffers from a table
+// (DenseSlot, dense_grow) and the entries' small helpers (dense_fail, dense_begun, dense_map_invalid).  What an entry refuses for a
+// parameter's value alone is esl_dense_check.hpp's.  Internal: only those six units include it.
 // The rule of all six: every store to global memory is a vector store or an atomic in plain C++; no loop waits for another thread: a
 // probe that finds no slot within the table's size, or a map over its capacity, raises the sticky status 3 and gives up.
 #pragma once
@@ -142,14 +144,15 @@ struct DenseOutArgs {
   int* okey; double* oxyz; int* ocnt; unsigned char* obgr; int* oinst; int* ovotes;   // null: not asked for
 };
 
-// The map's voxels as a list of (packed key, slot) in ascending key order, shared by esl_dense_extract and the two extractors.
-// dense_list_grow: the list's buffers and the table pointers of `k`; dense_list_launch (inside the caller's ProfScope, after
-// ctr[DC_LIST] was cleared on the stream): k_dense_compact, k_dense_vote when asked for, the radix sort.
-int dense_list_grow(esl_ctx* c, DenseState& d, DenseOutArgs& k, size_t* temp_bytes);
-int dense_list_launch(esl_ctx* c, DenseState& d, DenseOutArgs& k, bool vote, size_t temp_bytes);
-// esl_dense_extract's gather of the first k.n_write voxels of the sorted list into the non-null outputs of `k` (after dense_list_launch,
-// inside the caller's ProfScope); esl_dense_render points them at buffers of its own
-void dense_gather_launch(esl_ctx* c, const DenseOutArgs& k);
+// The map's voxels as a list of (packed key, slot) in ascending key order, shared by esl_dense_extract and the five units that read
+// the map.  A call's step: dense_list_begin, the caller's own buffers and the outputs it wants in L.k, dense_list_launch.
+struct DenseList { DenseOutArgs k; size_t temp_bytes; };   // the kernels' arguments and the sort's temporary storage
+// the list's buffers grown, the table pointers of L.k set (the rest zero), ctr[DC_LIST] cleared on the stream: outside every ProfScope
+int dense_list_begin(esl_ctx* c, DenseState& d, DenseList& L);
+// inside the caller's ProfScope: k_dense_compact, k_dense_vote when asked for, the radix sort and, when asked for, esl_dense_extract's
+// gather of the first L.k.n_write (> 0) voxels of the sorted list into the non-null outputs of L.k (the readers point them at buffers
+// of their own)
+int dense_list_launch(esl_ctx* c, DenseState& d, DenseList& L, bool vote, bool gather);
 // step 2 on the host: R and t of every frame, from the given poses or (cams == nullptr) the resident camera states; an invalid pose
 // gives ESL_ERR_INVALID.  host / pose: the caller's staging vectors
 int dense_frames_poses(esl_ctx* c, const char* who, const double* cams, int F, std::vector<double>& host, std::vector<double>& pose);
@@ -172,6 +175,25 @@ inline DenseState* dense_begun(esl_ctx* c, const char* who) {
 
 inline unsigned dense_blocks(u64 n) { return (unsigned)((n + kDenseThreads - 1) / kDenseThreads); }
 
-struct DenseSlot { int slot; size_t bytes; };   // a row of an extractor's table of the buffers it grows, in order
+// a row of a unit's table of the buffers it grows, in order.  skip_empty: a row of 0 bytes is left alone (esl_dense_render and
+// esl_dense_carve_frames: a buffer that this call has no use for); otherwise it is grown like any other, which gives an empty slot its
+// 16 bytes and counts as an allocation (esl_dense_objects, esl_dense_planes, esl_dense_normals: every slot of theirs exists after a call)
+struct DenseSlot { int slot; size_t bytes; };
+template <int N, size_t R>
+int dense_grow(esl_ctx* c, ScratchSet<N>& s, const DenseSlot (&want)[R], bool skip_empty) {
+  for (const DenseSlot& w : want) {
+    if (skip_empty && !w.bytes) continue;
+    if (const int rc = s.grow(c, w.slot, w.bytes)) return rc;
+  }
+  return ESL_OK;
+}
+
+// an invalid map (over capacity or inconsistent): the result says so and the entry writes nothing more
+template <class Result>
+bool dense_map_invalid(const DenseState& d, Result* out) {
+  if (!d.status) return false;
+  out->status = d.status; out->n_voxels = -1;
+  return true;
+}
 
 }  // namespace esl

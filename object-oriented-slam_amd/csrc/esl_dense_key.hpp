@@ -88,6 +88,27 @@ ESL_DENSE_HD void dense_unpack(unsigned long long key, int k[3]) {
   k[2] = (int)(key & 0x1FFFFFull) - kDenseKeyOff;
 }
 
+// The sample as k_dense_insert forms it: esl_dense_align_frames and esl_dense_carve_frames find the voxels that insertion made only
+// while k_dense_insert, k_dal_accum and k_dcv_mark form it bit for bit alike.
+// sample i of a frame, consecutive i on consecutive sampled columns: row < rows and col < cols for i < srows scols.  By value: with
+// two output pointers the three kernels' listings change
+struct DensePixel { int row, col; };
+ESL_DENSE_HD DensePixel dense_sample_pixel(long long i, int stride, int scols) {
+  const int sr = (int)(i / scols);
+  return {sr * stride, (int)(i - (long long)sr * scols) * stride};
+}
+// steps 1 to 3 of one raw depth at (col, row): the category with DENSE_KEY_OUT folded in; pc, pw and k are set when it is DENSE_USED.
+// k_dal_accum calls it; k_dense_insert and k_dcv_mark keep the three calls written out (tests/dense_key_main.cpp holds the two equal)
+ESL_DENSE_HD int dense_sample_key(unsigned raw, int col, int row, const double K[4], double depth_scale, double depth_min, double depth_max,
+                                  const double P[kDensePose], double leaf, double pc[3], double pw[3], int k[3]) {
+  int cat = dense_sample(raw, col, row, K, depth_scale, depth_min, depth_max, pc);
+  if (cat == DENSE_USED) {
+    dense_world(P, pc, pw);
+    if (!dense_key(pw, leaf, k)) cat = DENSE_KEY_OUT;
+  }
+  return cat;
+}
+
 // step 4: a coordinate's term of S_a (round to nearest, ties to even; the product with 2^30 is exact)
 ESL_DENSE_HD long long dense_fix(double v) { return (long long)std::llrint(v * kDenseFix); }
 // step 7: the centroid and the mean colour of a voxel

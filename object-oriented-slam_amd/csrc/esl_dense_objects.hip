@@ -293,7 +293,7 @@ extern "C" int esl_dense_objects(esl_ctx* c, int32_t N, const double ground_worl
   DenseState& d = *c->dense;
   if (!d.with_inst) return dense_fail(ESL_ERR_STATE, who, "the map was begun without labels");
   std::memset(out, 0, sizeof(*out));
-  if (d.status) { out->status = d.status; out->n_voxels = -1; return ESL_OK; }   // over capacity or inconsistent: the map is invalid, nothing is written
+  if (dense_map_invalid(d, out)) return ESL_OK;   // nothing is written
   const long long n = d.n_voxels;
   const long long n_comp_w_max = comp_cap, n_vox_w = std::min<long long>(n, voxel_cap);
   out->n_voxels = (int32_t)n;
@@ -307,9 +307,9 @@ extern "C" int esl_dense_objects(esl_ctx* c, int32_t N, const double ground_worl
 
   ESL_HIP_TRY(hipSetDevice(c->device));
   ScratchSet<DB_OBJ_COUNT>& s = d.obj_set;
-  DenseOutArgs k;
-  size_t temp_bytes = 0;
-  if (const int rc = dense_list_grow(c, d, k, &temp_bytes)) return rc;
+  DenseList L;
+  if (const int rc = dense_list_begin(c, d, L)) return rc;
+  const DenseOutArgs& k = L.k;
   const long long table_cap = std::min<long long>(p.max_components, n);
   {
     const size_t sn = (size_t)n, sN = (size_t)N, st = (size_t)table_cap;
@@ -318,8 +318,7 @@ extern "C" int esl_dense_objects(esl_ctx* c, int32_t N, const double ground_worl
         {DB_CSAMP, sn * 4}, {DB_OCTR, DO_COUNT * sizeof(u64)}, {DB_LABKEPT, sN * 4}, {DB_TABLE, st * kDobjRow * 4}, {DB_ROWROOT, st * 4},
         {DB_ROWOBJ, st * 4}, {DB_KBOX, sN * 6 * 4}, {DB_MOM, sN * kDobjMoments * 8}, {DB_AXES, sN * 9 * 8}, {DB_EXT, sN * 6 * 8},
         {DB_VOUT, (size_t)n_vox_w * 4}};
-    for (const DenseSlot& w : want)
-      if (const int rc = s.grow(c, w.slot, w.bytes)) return rc;
+    if (const int rc = dense_grow(c, s, want, false)) return rc;
   }
   DobjArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -338,12 +337,11 @@ extern "C" int esl_dense_objects(esl_ctx* c, int32_t N, const double ground_worl
   const dim3 blk(kDenseThreads), grid_n(dense_blocks((u64)n));
 
   // steps 1 to 3 on the device
-  ESL_HIP_TRY(hipMemsetAsync(k.ctr + DC_LIST, 0, sizeof(u64), c->stream));
   ESL_HIP_TRY(hipMemsetAsync(a.ctr, 0, DO_COUNT * sizeof(u64), c->stream));
   if (N > 0) ESL_HIP_TRY(hipMemsetAsync(a.labkept, 0, (size_t)N * 4, c->stream));
   {
     ProfScope ps(c, 4);
-    if (const int rc = dense_list_launch(c, d, k, true, temp_bytes)) return rc;
+    if (const int rc = dense_list_launch(c, d, L, true, false)) return rc;
     hipLaunchKernelGGL(k_dobj_gate, grid_n, blk, 0, c->stream, a);
     const u64 items = (u64)n * (u64)a.n_off;
     hipLaunchKernelGGL(k_dobj_union, dim3(std::min<unsigned>(dense_blocks(std::min<u64>(items, 1ull << 40)), 1u << 16)), blk, 0, c->stream, a);

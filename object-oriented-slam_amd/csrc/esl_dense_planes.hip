@@ -280,7 +280,7 @@ extern "C" int esl_dense_planes(esl_ctx* c, const esl_dense_plane_params* pp, do
   if (!dense_begun(c, who)) return ESL_ERR_STATE;
   DenseState& d = *c->dense;
   std::memset(out, 0, sizeof(*out));
-  if (d.status) { out->status = d.status; out->n_voxels = -1; return ESL_OK; }   // over capacity or inconsistent: the map is invalid, nothing is written
+  if (dense_map_invalid(d, out)) return ESL_OK;   // nothing is written
   const long long n = d.n_voxels, n_vox_w = std::min<long long>(n, voxel_cap);
   const int Hn = p.n_hypotheses, P = p.max_planes;
   out->n_voxels = (int32_t)n; out->ground_index = -1; out->stop_reason = 1;
@@ -294,16 +294,16 @@ extern "C" int esl_dense_planes(esl_ctx* c, const esl_dense_plane_params* pp, do
 
   ESL_HIP_TRY(hipSetDevice(c->device));
   ScratchSet<DB_PL_COUNT>& s = d.pl_set;
-  DenseOutArgs k;
-  size_t temp_bytes = 0, sel_bytes = 0;
-  if (const int rc = dense_list_grow(c, d, k, &temp_bytes)) return rc;
+  DenseList L;
+  size_t sel_bytes = 0;
+  if (const int rc = dense_list_begin(c, d, L)) return rc;
+  const DenseOutArgs& k = L.k;
   {
     const size_t sn = (size_t)n, sh = (size_t)Hn;
     const DenseSlot want[] = {{DB_PSTATE, sn * 4}, {DB_PCTR, DP_COUNT * sizeof(u64)}, {DB_PBOX, 6 * 4}, {DB_PLIST, sn * 4},
                               {DB_PVOX, sn * sizeof(DplVox)}, {DB_PGKEY, sh * 3 * 8}, {DB_PPLANES, sh * 4 * 8}, {DB_PVALID, sh * 4},
                               {DB_PHACC, sh * 2 * 8}, {DB_PMOM, kDplMoments * sizeof(u64)}, {DB_PVOUT, (size_t)n_vox_w * 4}};
-    for (const DenseSlot& w : want)
-      if (const int rc = s.grow(c, w.slot, w.bytes)) return rc;
+    if (const int rc = dense_grow(c, s, want, false)) return rc;
   }
   DplArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -322,12 +322,11 @@ extern "C" int esl_dense_planes(esl_ctx* c, const esl_dense_plane_params* pp, do
   // step 1
   int box[6] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN};
   u64 ctr[DP_COUNT];
-  ESL_HIP_TRY(hipMemsetAsync(k.ctr + DC_LIST, 0, sizeof(u64), c->stream));
   ESL_HIP_TRY(hipMemsetAsync(a.ctr, 0, DP_COUNT * sizeof(u64), c->stream));
   ESL_HIP_TRY(hipMemcpyAsync(a.box, box, sizeof(box), hipMemcpyHostToDevice, c->stream));
   {
     ProfScope ps(c, 4);
-    if (const int rc = dense_list_launch(c, d, k, d.with_inst && a.skip_labelled, temp_bytes)) return rc;
+    if (const int rc = dense_list_launch(c, d, L, d.with_inst && a.skip_labelled, false)) return rc;
     hipLaunchKernelGGL(k_dpl_gate, dim3(std::min<unsigned>(dense_blocks((u64)n), kDplReduceBlocks)), blk, 0, c->stream, a);
   }
   ESL_HIP_TRY(hipGetLastError());

@@ -14,6 +14,7 @@
 // A build with -DESL_DRN_COUNT also counts the candidates formed and the atomicMins issued and prints both on stderr: timing-only, the
 // shipped kernel carries no such counter.
 #include "esl_dense_int.hpp"
+#include "esl_dense_check.hpp"
 #include "esl_dense_proj.hpp"
 
 #include <cstdio>
@@ -173,31 +174,18 @@ extern "C" int esl_dense_render(esl_ctx* c, const double* cams, int32_t F, const
   if (!c) return dense_fail(ESL_ERR_INVALID, who, "null ctx");
   if (!out) return dense_fail(ESL_ERR_INVALID, who, "null out");
   if (F < 0) return dense_fail(ESL_ERR_INVALID, who, "negative F");
-  if (!K) return dense_fail(ESL_ERR_INVALID, who, "null K");
-  if (rows < 1 || rows > kDenseMaxDim) return dense_fail(ESL_ERR_INVALID, who, "rows < 1 or > 16384");
-  if (cols < 1 || cols > kDenseMaxDim) return dense_fail(ESL_ERR_INVALID, who, "cols < 1 or > 16384");
-  if (!std::isfinite(K[0]) || !(K[0] > 0)) return dense_fail(ESL_ERR_INVALID, who, "fx not finite or <= 0");
-  if (!std::isfinite(K[1]) || !(K[1] > 0)) return dense_fail(ESL_ERR_INVALID, who, "fy not finite or <= 0");
+  if (const char* m = dense_image_check(K, rows, cols)) return dense_fail(ESL_ERR_INVALID, who, m);
   if (vox_cap < 0) return dense_fail(ESL_ERR_INVALID, who, "negative vox_cap");
   if (vox_cap > 0 && !vox_out) return dense_fail(ESL_ERR_INVALID, who, "null vox_out with vox_cap > 0");
   esl_dense_render_params p;
   if (pp) p = *pp; else esl_dense_render_params_default(&p);
-  if (!std::isfinite(p.depth_scale) || !(p.depth_scale > 0)) return dense_fail(ESL_ERR_INVALID, who, "depth_scale not finite or <= 0");
-  if (!std::isfinite(p.depth_min) || p.depth_min < 0) return dense_fail(ESL_ERR_INVALID, who, "depth_min not finite or negative");
-  if (!std::isfinite(p.depth_max) || p.depth_max < 0) return dense_fail(ESL_ERR_INVALID, who, "depth_max not finite or negative");
-  if (!std::isfinite(p.depth_tol) || p.depth_tol < 0) return dense_fail(ESL_ERR_INVALID, who, "depth_tol not finite or negative");
-  if (p.depth_min > p.depth_max) return dense_fail(ESL_ERR_INVALID, who, "depth_min > depth_max");
-  if (p.depth_max > kDrnDepthMax) return dense_fail(ESL_ERR_INVALID, who, "depth_max > 4095");
-  if (!std::isfinite(p.footprint) || p.footprint < 0) return dense_fail(ESL_ERR_INVALID, who, "footprint not finite or negative");
-  if (p.max_radius < 0 || p.max_radius > kDrnMaxRadius) return dense_fail(ESL_ERR_INVALID, who, "max_radius outside 0 .. 64");
-  if (p.min_count < 1) return dense_fail(ESL_ERR_INVALID, who, "min_count < 1");
   const size_t npix = (size_t)rows * cols;
-  if (p.zbuf_bytes < (int64_t)(8 * npix)) return dense_fail(ESL_ERR_INVALID, who, "zbuf_bytes < 8 rows cols");
+  if (const char* m = drn_params_check(p, npix)) return dense_fail(ESL_ERR_INVALID, who, m);
   if (!dense_begun(c, who)) return ESL_ERR_STATE;
   if (const int rc = resident_source_check(c, who, !cams && F > 0, F, false, 0)) return rc;
   DenseState& d = *c->dense;
   std::memset(out, 0, sizeof(*out));
-  if (d.status) { out->status = d.status; out->n_voxels = -1; return ESL_OK; }   // step 8: the map is invalid, nothing is written
+  if (dense_map_invalid(d, out)) return ESL_OK;   // step 8: nothing is written
   ESL_HIP_TRY(hipSetDevice(c->device));
   // the poses: R and t of every frame on the host, before anything runs
   if (F > 0) {
@@ -220,9 +208,9 @@ extern "C" int esl_dense_render(esl_ctx* c, const double* cams, int32_t F, const
   }
 
   ScratchSet<DR_COUNT>& s = d.rn_set;
-  DenseOutArgs k;
-  size_t temp_bytes = 0;
-  if (const int rc = dense_list_grow(c, d, k, &temp_bytes)) return rc;
+  DenseList L;
+  if (const int rc = dense_list_begin(c, d, L)) return rc;
+  DenseOutArgs& k = L.k;
   const int cf = (int)std::min<long long>(F, chunk);   // frames per chunk
   {
     const size_t sn = (size_t)n, sc = (size_t)cf * npix;
@@ -233,9 +221,7 @@ extern "C" int esl_dense_render(esl_ctx* c, const double* cams, int32_t F, const
                               {DR_ZBUF, frames ? sc * sizeof(u64) : 0}, {DR_MEAS, frames && depth_meas ? sc * sizeof(uint16_t) : 0},
                               {DR_ODEPTH, frames && depth_out ? sc * sizeof(double) : 0}, {DR_OVOX, frames && voxel_out ? sc * sizeof(int32_t) : 0},
                               {DR_OBGR, frames && bgr_out ? sc * 3 : 0}, {DR_OINST, frames && inst_out ? sc * sizeof(int32_t) : 0}};
-    for (const DenseSlot& w : want)
-      if (w.bytes)
-        if (const int rc = s.grow(c, w.slot, w.bytes)) return rc;
+    if (const int rc = dense_grow(c, s, want, true)) return rc;
   }
   DrnArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -255,12 +241,10 @@ extern "C" int esl_dense_render(esl_ctx* c, const double* cams, int32_t F, const
   const dim3 blk(kDenseThreads);
 
   // step 1: the list, the voxels' numbers, n_small
-  ESL_HIP_TRY(hipMemsetAsync(k.ctr + DC_LIST, 0, sizeof(u64), c->stream));
   ESL_HIP_TRY(hipMemsetAsync(a.ctr, 0, DRC_COUNT * sizeof(u64), c->stream));
   {
     ProfScope ps(c, 4);
-    if (const int rc = dense_list_launch(c, d, k, d.with_inst && frames && inst_out, temp_bytes)) return rc;
-    dense_gather_launch(c, k);
+    if (const int rc = dense_list_launch(c, d, L, d.with_inst && frames && inst_out, true)) return rc;
     hipLaunchKernelGGL(k_drn_small, dim3(dense_blocks((u64)n)), blk, 0, c->stream, a);
   }
   ESL_HIP_TRY(hipGetLastError());

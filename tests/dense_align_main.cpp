@@ -9,6 +9,10 @@
 //   dense_align_main terms     stdin: "n o[3]", then n rows "pw[3] c[3] n[3]".  stdout per row: the 28 terms
 //   dense_align_main step      stdin: "n", then per frame "T[28] n_inlier min_inliers damping min_pivot_ratio cam[7]".  stdout per frame:
 //                              "status H[36] g[6] delta[6] ok cam_new[7] |v| |omega|"
+//   dense_align_main check     csrc/esl_dense_check.hpp; the one mode whose doubles cross as text ("nan", "inf" and 17 digits).  stdin per line:
+//                              "max_dist damping min_pivot_ratio tol_t tol_r iters stride reach min_inliers max_curvature radius min_count
+//                              min_neighbors"; stdout per line dal_params_check's refusal text, or "ok"
+//   dense_align_main check_normals   the last four of those per line; dnr_params_check's refusal text, or "ok"
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -16,6 +20,7 @@
 #include <vector>
 
 #include "../object-oriented-slam_amd/csrc/esl_dense_align.hpp"
+#include "../object-oriented-slam_amd/csrc/esl_dense_check.hpp"
 
 using namespace esl;
 
@@ -144,7 +149,22 @@ static int step() {
   return 0;
 }
 
+static int check(bool normals_only) {
+  esl_dense_align_params p;
+  esl_dense_normal_params& q = p.normals;
+  for (;;) {
+    if (!normals_only && std::scanf("%lf %lf %lf %lf %lf %d %d %d %d", &p.max_dist, &p.damping, &p.min_pivot_ratio, &p.tol_t, &p.tol_r, &p.iters,
+                                    &p.stride, &p.reach, &p.min_inliers) != 9) break;
+    if (std::scanf("%lf %d %d %d", &q.max_curvature, &q.radius, &q.min_count, &q.min_neighbors) != 4) break;
+    const char* m = normals_only ? dnr_params_check(q) : dal_params_check(p);
+    std::printf("%s\n", m ? m : "ok");
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && std::strcmp(argv[1], "check") == 0) return check(false);
+  if (argc > 1 && std::strcmp(argv[1], "check_normals") == 0) return check(true);
   if (argc > 1 && std::strcmp(argv[1], "normal") == 0) return normal();
   if (argc > 1 && std::strcmp(argv[1], "match") == 0) return match();
   if (argc > 1 && std::strcmp(argv[1], "terms") == 0) return terms();

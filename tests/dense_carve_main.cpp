@@ -5,12 +5,15 @@
 //                                cy n F", then n lines "x y z", then per frame a pose line "tx ty tz qx qy qz qw" and rows cols raw
 //                                values.  stdout: per frame one line of n classes (0 agree, 1 nearer, 2 through, 3 no data, 4 depth
 //                                out, 5 outside), then per voxel "agree nearer through nodata carved" from the packed accumulator
+//   dense_carve_main check       csrc/esl_dense_check.hpp.  stdin per line: "depth_scale depth_min depth_max depth_tol window min_through
+//                                through_per_agree apply"; stdout per line dcv_params_check's refusal text, or "ok"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "../object-oriented-slam_amd/csrc/esl_dense_carve.hpp"
+#include "../object-oriented-slam_amd/csrc/esl_dense_check.hpp"
 
 using namespace esl;
 
@@ -84,7 +87,18 @@ static int run(const char* path) {
   return 0;
 }
 
+static int check() {
+  esl_dense_carve_params p;
+  while (std::scanf("%lf %lf %lf %lf %d %d %d %d", &p.depth_scale, &p.depth_min, &p.depth_max, &p.depth_tol, &p.window, &p.min_through,
+                    &p.through_per_agree, &p.apply) == 8) {
+    const char* m = dcv_params_check(p);
+    std::printf("%s\n", m ? m : "ok");
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && std::strcmp(argv[1], "check") == 0) return check();
   if (argc > 1) return run(argv[1]);
   return self_check();
 }

@@ -3,12 +3,15 @@
 //                exit status 0 when all hold.
 //   "samples":   reads from stdin  leaf depth_scale depth_min depth_max  then  K(4)  then  n  and n lines  cam(7) raw col row ;
 //                prints per line  category packed_key fix_x fix_y fix_z  (zeros unless the sample is used): the CPU test compares them
-//                with the numpy statement.
+//                with the numpy statement.  Every line is also formed by dense_sample_key and must come out the same, and every (row, col)
+//                of a strided image by dense_sample_pixel (exit status 3 otherwise).
+//   "check":     stdin per line  null_K rows cols fx fy cx cy ; stdout per line dense_image_check's refusal text, or "ok"
 // Built and run by tests/test_dense_ref.py, also under -fsanitize=address,undefined.  Compile with -ffp-contract=off.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
+#include "../object-oriented-slam_amd/csrc/esl_dense_check.hpp"
 #include "../object-oriented-slam_amd/csrc/esl_dense_key.hpp"
 
 using namespace esl;
@@ -57,6 +60,20 @@ static void self_checks() {
     const double huge[7] = {0, 0, 0, 1e200, 1e200, 0, 0};   // the norm overflows
     CHECK(!dense_pose(huge, P));
   }
+  // the sampled pixels: sample i of a frame against the two loops it flattens, sizes that no stride divides included
+  for (int stride = 1; stride <= 4; ++stride) {
+    const int rows = 7, cols = 10, srows = (rows + stride - 1) / stride, scols = (cols + stride - 1) / stride;
+    long long i = 0;
+    for (int r = 0; r < rows; r += stride) for (int c = 0; c < cols; c += stride, ++i) {
+      const DensePixel p = dense_sample_pixel(i, stride, scols);
+      CHECK(p.row == r && p.col == c);
+    }
+    CHECK(i == (long long)srows * scols);
+  }
+  {   // beyond 2^31 samples the division is still the 64-bit one
+    const DensePixel p = dense_sample_pixel(16384ll * 16384 * 9 + 5, 1, 16384);
+    CHECK(p.row == 16384 * 9 && p.col == 5);
+  }
 }
 
 static int samples() {
@@ -77,13 +94,32 @@ static int samples() {
       if (dense_key(pw, leaf, k)) { key = dense_pack(k[0], k[1], k[2]); for (int a = 0; a < 3; ++a) fx[a] = dense_fix(pw[a]); }
       else cat = DENSE_KEY_OUT;
     }
+    {   // the helper the kernels call gives the category, the points and the key of the three calls above, bit for bit
+      double hc[3] = {0, 0, 0}, hw[3] = {0, 0, 0};
+      int hk[3] = {0, 0, 0};
+      const int hcat = dense_sample_key(raw, col, row, K, scale, dmin, dmax, P, leaf, hc, hw, hk);
+      if (hcat != cat) return 3;
+      if (cat == DENSE_USED && (std::memcmp(hc, pc, sizeof(pc)) || std::memcmp(hw, pw, sizeof(pw)) || std::memcmp(hk, k, sizeof(k)))) return 3;
+      if (cat == DENSE_KEY_OUT && (std::memcmp(hc, pc, sizeof(pc)) || std::memcmp(hw, pw, sizeof(pw)))) return 3;
+    }
     std::printf("%d %llu %lld %lld %lld\n", cat, key, fx[0], fx[1], fx[2]);
+  }
+  return 0;
+}
+
+static int check() {
+  int null_k, rows, cols;
+  double K[4];
+  while (std::scanf("%d %d %d %lf %lf %lf %lf", &null_k, &rows, &cols, &K[0], &K[1], &K[2], &K[3]) == 7) {
+    const char* m = dense_image_check(null_k ? nullptr : K, rows, cols);
+    std::printf("%s\n", m ? m : "ok");
   }
   return 0;
 }
 
 int main(int argc, char** argv) {
   if (argc > 1 && !std::strcmp(argv[1], "samples")) return samples();
+  if (argc > 1 && !std::strcmp(argv[1], "check")) return check();
   self_checks();
   if (fails) return 1;
   std::printf("dense_key ok\n");

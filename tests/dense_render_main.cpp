@@ -4,12 +4,15 @@
 //   dense_render_main project    stdin: "e max_radius rows cols depth_min depth_max fx fy cx cy n", a pose line "tx ty tz qx qy qz qw",
 //                                then n lines "x y z".  stdout per voxel: "class zbits zq c0 c1 r0 r1" (zbits = the double's 64 bits;
 //                                zq and the bounds 0 unless the class is 0 = drawn)
+//   dense_render_main check      csrc/esl_dense_check.hpp.  stdin per line: "depth_scale depth_min depth_max depth_tol footprint max_radius
+//                                min_count zbuf_bytes npix"; stdout per line drn_params_check's refusal text, or "ok"
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
+#include "../object-oriented-slam_amd/csrc/esl_dense_check.hpp"
 #include "../object-oriented-slam_amd/csrc/esl_dense_proj.hpp"
 
 using namespace esl;
@@ -68,7 +71,20 @@ static int project() {
   return 0;
 }
 
+static int check() {
+  esl_dense_render_params p;
+  long long zbuf, npix;
+  while (std::scanf("%lf %lf %lf %lf %lf %d %d %lld %lld", &p.depth_scale, &p.depth_min, &p.depth_max, &p.depth_tol, &p.footprint, &p.max_radius,
+                    &p.min_count, &zbuf, &npix) == 9) {
+    p.zbuf_bytes = zbuf;
+    const char* m = drn_params_check(p, (size_t)npix);
+    std::printf("%s\n", m ? m : "ok");
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && std::strcmp(argv[1], "check") == 0) return check();
   if (argc > 1 && std::strcmp(argv[1], "project") == 0) return project();
   return self_check();
 }

@@ -4,7 +4,6 @@ held to the statement on the host (plain and under AddressSanitizer + UBSan, as 
 Python)."""
 import math
 import os
-import shutil
 import subprocess
 import sys
 
@@ -16,6 +15,7 @@ import dense_align_ref as dar          # noqa: E402
 import dense_align_scenes as s         # noqa: E402
 import dense_planes_ref as dpr         # noqa: E402
 import dense_ref as dr                 # noqa: E402
+from dense_prog import BUILDS, BUILD_IDS, NONFINITE, build_prog, check_ladder          # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -220,14 +220,6 @@ def test_refusals_of_the_statement():
 
 
 # ---- the header against the statement -----------------------------------------------------------------------------------------------------
-def build_prog(tmp, flags):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "a C++ compiler is needed to build tests/dense_align_main.cpp"
-    exe = str(tmp / "dense_align_main")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", *flags, "-o", exe, os.path.join(ROOT, "tests", "dense_align_main.cpp")])
-    return exe
-
-
 def bits(x):
     return [str(int(b)) for b in np.asarray(x, dtype=np.float64).reshape(-1).view(np.uint64)]
 
@@ -251,7 +243,7 @@ def neighbour_lists(ext, reach, eligible):
 @pytest.mark.parametrize("flags", [(), ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan")],
                          ids=["plain", "asan_ubsan"])
 def test_align_header_matches_the_statement(tmp_path, flags):
-    exe = build_prog(tmp_path, flags)
+    exe = build_prog(tmp_path, "dense_align_main", flags)
     assert subprocess.run([exe], capture_output=True, text=True, check=True).stdout.strip() == "dense_align ok"
     # the normals: the moments in visit order, the Jacobi, the orientation, the curvature and the gates
     n_valid = n_invalid = 0
@@ -321,3 +313,37 @@ def test_align_header_matches_the_statement(tmp_path, flags):
                 break
             cam = nxt
     assert n_steps[0] >= 9 and n_steps[dar.TOO_FEW] == 1 and n_steps[dar.DEGENERATE] == 1
+
+
+# ---- what esl_dense_normals and esl_dense_align_frames refuse for their parameters (csrc/esl_dense_check.hpp), text by text and in order ----
+TINY = 5e-324          # the smallest positive double: the first value above 0, its negative the first below
+NORMAL_RUNGS = [
+    ("max_curvature not finite or negative", [dict(max_curvature=0.0)], [dict(max_curvature=-TINY)] + [dict(max_curvature=v) for v in NONFINITE]),
+    ("radius outside 1 .. 2", [dict(radius=1), dict(radius=2)], [dict(radius=0), dict(radius=3)]),
+    ("min_count < 1", [dict(min_count=1)], [dict(min_count=0)]),
+    ("min_neighbors < 1", [dict(min_neighbors=1)], [dict(min_neighbors=0)]),
+]
+
+
+@pytest.mark.parametrize("flags", BUILDS, ids=BUILD_IDS)
+def test_align_params_check_texts_and_order(tmp_path, flags):
+    """dal_params_check, and dnr_params_check which ends it and which esl_dense_normals calls alone: every rung at its last accepted and
+    first refused value, NaN and the infinities in every double, and the earlier rung's text when two fail."""
+    exe = build_prog(tmp_path, "dense_align_main", flags)
+    normals = dict(max_curvature=0.05, radius=1, min_count=1, min_neighbors=5)
+    defaults = dict(max_dist=0.0, damping=0.0, min_pivot_ratio=1e-6, tol_t=1e-5, tol_r=1e-5, iters=4, stride=2, reach=1, min_inliers=100, **normals)
+    rungs = [
+        ("max_dist not finite or negative", [dict(max_dist=0.0)], [dict(max_dist=-TINY)] + [dict(max_dist=v) for v in NONFINITE]),
+        ("damping not finite or negative", [dict(damping=0.0)], [dict(damping=-TINY)] + [dict(damping=v) for v in NONFINITE]),
+        ("min_pivot_ratio not finite or negative", [dict(min_pivot_ratio=0.0)], [dict(min_pivot_ratio=-TINY)] + [dict(min_pivot_ratio=v) for v in NONFINITE]),
+        ("tol_t not finite or negative", [dict(tol_t=0.0)], [dict(tol_t=-TINY)] + [dict(tol_t=v) for v in NONFINITE]),
+        ("tol_r not finite or negative", [dict(tol_r=0.0)], [dict(tol_r=-TINY)] + [dict(tol_r=v) for v in NONFINITE]),
+        ("iters outside 0 .. 64", [dict(iters=0), dict(iters=64)], [dict(iters=-1), dict(iters=65)]),
+        ("stride < 1", [dict(stride=1)], [dict(stride=0)]),
+        ("reach outside 0 .. 2", [dict(reach=0), dict(reach=2)], [dict(reach=-1), dict(reach=3)]),
+        ("min_inliers < 1", [dict(min_inliers=1)], [dict(min_inliers=0)]),
+    ] + NORMAL_RUNGS
+    nfields = ["max_curvature", "radius", "min_count", "min_neighbors"]
+    fields = ["max_dist", "damping", "min_pivot_ratio", "tol_t", "tol_r", "iters", "stride", "reach", "min_inliers"] + nfields
+    check_ladder(exe, fields, defaults, rungs)
+    check_ladder(exe, nfields, normals, NORMAL_RUNGS, mode="check_normals")

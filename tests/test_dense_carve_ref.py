@@ -11,7 +11,6 @@ through_per_agree 1): 7376 voxels, 208 of them with samples from box pixels only
   voxels with as many agreeing as through observations are kept (through >= through_per_agree * agree fails for 3 of the 192)
 `ghost_odd` (45 x 61): 7090 voxels, 215 box-only; window 1: 199 carved, 0 static."""
 import os
-import shutil
 import subprocess
 import sys
 
@@ -22,6 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dense_carve_ref as dcr          # noqa: E402
 import dense_carve_scenes as cs        # noqa: E402
 import dense_ref as dr                 # noqa: E402
+from dense_prog import BUILDS, BUILD_IDS, NONFINITE, build_prog, check_ladder          # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -155,14 +155,6 @@ def test_invalid_map_and_pose():
 
 
 # ---- the header against the statement -----------------------------------------------------------------------------------------------------
-def build_prog(tmp, flags):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "a C++ compiler is needed to build tests/dense_carve_main.cpp"
-    exe = str(tmp / "dense_carve_main")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", *flags, "-o", exe, os.path.join(ROOT, "tests", "dense_carve_main.cpp")])
-    return exe
-
-
 def cases():
     """(name, xyz, cams, depth, K, rows, cols, params) of every scene the program is held to"""
     for name in ("ghost", "ghost_odd"):
@@ -177,7 +169,7 @@ def cases():
 @pytest.mark.parametrize("flags", [(), ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan")],
                          ids=["plain", "asan_ubsan"])
 def test_carve_header_matches_the_statement(tmp_path, flags):
-    exe = build_prog(tmp_path, flags)
+    exe = build_prog(tmp_path, "dense_carve_main", flags)
     assert subprocess.run([exe], capture_output=True, text=True, check=True).stdout.strip() == "dense_carve ok"
     seen = set()
     for name, xyz, cams, depth, K, rows, cols, p in cases():
@@ -199,3 +191,33 @@ def test_carve_header_matches_the_statement(tmp_path, flags):
         assert np.array_equal(np.array([[int(v) for v in line.split()] for line in out[F:F + n]], np.int64).reshape(n, 5), want), name
         seen |= set(np.unique(cls).tolist())
     assert seen == {0, 1, 2, 3, 4, 5}
+
+
+# ---- what esl_dense_carve_frames refuses for its parameters (csrc/esl_dense_check.hpp), text by text and in order -------------------------
+TINY = 5e-324          # the smallest positive double: the first value above 0, its negative the first below
+# the depth gate of esl_dense_render and esl_dense_carve_frames: the six refusals in their order, the texts as the entries have always given them
+GATE_RUNGS = [
+    ("depth_scale not finite or <= 0", [dict(depth_scale=TINY)], [dict(depth_scale=0.0), dict(depth_scale=-1.0)] + [dict(depth_scale=v) for v in NONFINITE]),
+    ("depth_min not finite or negative", [dict(depth_min=0.0)], [dict(depth_min=-TINY)] + [dict(depth_min=v) for v in NONFINITE]),
+    ("depth_max not finite or negative", [dict(depth_min=0.0, depth_max=0.0)], [dict(depth_max=-TINY)] + [dict(depth_max=v) for v in NONFINITE]),
+    ("depth_tol not finite or negative", [dict(depth_tol=0.0)], [dict(depth_tol=-TINY)] + [dict(depth_tol=v) for v in NONFINITE]),
+    ("depth_min > depth_max", [dict(depth_min=6.0)], [dict(depth_min=5000.0, depth_max=4999.0), dict(depth_min=float(np.nextafter(6.0, np.inf)))]),
+    ("depth_max > 4095", [dict(depth_max=4095.0)], [dict(depth_max=float(np.nextafter(4095.0, np.inf)))]),
+]
+
+
+@pytest.mark.parametrize("flags", BUILDS, ids=BUILD_IDS)
+def test_carve_params_check_texts_and_order(tmp_path, flags):
+    """dcv_params_check: every rung at its last accepted and first refused value, NaN and the infinities in every double, and the
+    earlier rung's text when two fail."""
+    exe = build_prog(tmp_path, "dense_carve_main", flags)
+    defaults = dict(dcr.DEFAULTS)
+    assert defaults["depth_max"] == 6.0 and defaults["window"] == 1 and defaults["apply"] == 0
+    rungs = GATE_RUNGS + [
+        ("window outside 0 .. 4", [dict(window=0), dict(window=4)], [dict(window=-1), dict(window=5)]),
+        ("min_through < 1", [dict(min_through=1)], [dict(min_through=0)]),
+        ("negative through_per_agree", [dict(through_per_agree=0)], [dict(through_per_agree=-1)]),
+        ("apply not 0 or 1", [dict(apply=0), dict(apply=1)], [dict(apply=-1), dict(apply=2)]),
+    ]
+    fields = ["depth_scale", "depth_min", "depth_max", "depth_tol", "window", "min_through", "through_per_agree", "apply"]
+    check_ladder(exe, fields, defaults, rungs)

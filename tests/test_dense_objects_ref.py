@@ -4,7 +4,6 @@ import ctypes
 import functools
 import os
 import re
-import shutil
 import subprocess
 import sys
 
@@ -15,6 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dense_ref as dr                # noqa: E402
 import dense_objects_ref as dor       # noqa: E402
 import dense_scenes as sc             # noqa: E402
+from dense_prog import build_prog          # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLOOR = (0.0, 0.0, 1.0, 0.0)
@@ -162,18 +162,10 @@ def test_symbols_declared_listed_exported_and_struct_sizes(pkg):
 
 
 # ---- the header against hand-computed cases and the statement ---------------------------------------------------------------------------------------
-def build_obj_prog(tmp, flags):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "a C++ compiler is needed to build tests/dense_obj_main.cpp"
-    exe = str(tmp / "dense_obj_main")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", *flags, "-o", exe, os.path.join(ROOT, "tests", "dense_obj_main.cpp")])
-    return exe
-
-
 @pytest.mark.parametrize("flags", [(), ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan")],
                          ids=["plain", "asan_ubsan"])
 def test_obj_header_matches_the_statement(tmp_path, flags):
-    exe = build_obj_prog(tmp_path, flags)
+    exe = build_prog(tmp_path, "dense_obj_main", flags)
     assert subprocess.run([exe], capture_output=True, text=True, check=True).stdout.strip() == "dense_obj ok"
     # the guard's predicate around its boundary, against Python's integers
     cases = []
@@ -245,7 +237,7 @@ def device_table(e, N, reach, min_component, shuffle):
 @pytest.mark.parametrize("flags", [(), ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan")],
                          ids=["plain", "asan_ubsan"])
 def test_table_choice_and_statuses_match_the_statement(tmp_path, flags):
-    exe = build_obj_prog(tmp_path, flags)
+    exe = build_prog(tmp_path, "dense_obj_main", flags)
     # the random labelled map: the component table and the per-object stats of the statement
     e, N = random_labelled_extract(), 4
     r = dor.objects(e, 0.05, N, FLOOR, reach=1, min_component=20)

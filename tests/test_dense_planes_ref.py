@@ -4,7 +4,6 @@ The conditions the GPU scene tests rely on are asserted here, on the statement a
 import ctypes
 import os
 import re
-import shutil
 import struct
 import subprocess
 import sys
@@ -16,6 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dense_ref as dr                # noqa: E402
 import dense_planes_ref as dpr        # noqa: E402
 import dense_planes_scenes as ps      # noqa: E402
+from dense_prog import build_prog          # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LEAF = ps.LEAF
@@ -233,14 +233,6 @@ def test_symbols_declared_listed_exported_and_struct_sizes(pkg):
 
 
 # ---- the header against hand-computed cases and the statement, bit for bit ----------------------------------------------------------------------
-def build_prog(tmp, flags):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "a C++ compiler is needed to build tests/dense_planes_main.cpp"
-    exe = str(tmp / "dense_planes_main")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", *flags, "-o", exe, os.path.join(ROOT, "tests", "dense_planes_main.cpp")])
-    return exe
-
-
 def bits(v):
     return "%016x" % struct.unpack("<Q", struct.pack("<d", float(v)))[0]
 
@@ -252,7 +244,7 @@ def run(exe, mode, text):
 @pytest.mark.parametrize("flags", [(), ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan")],
                          ids=["plain", "asan_ubsan"])
 def test_planes_header_matches_the_statement(tmp_path, flags):
-    exe = build_prog(tmp_path, flags)
+    exe = build_prog(tmp_path, "dense_planes_main", flags)
     assert subprocess.run([exe], capture_output=True, text=True, check=True).stdout.strip() == "dense_planes ok"
     rng = np.random.default_rng(8)
     # the sampler

@@ -1,7 +1,6 @@
 """The numpy statement of esl_dense_* (tests/dense_ref.py) pinned by itself, and csrc/esl_dense_key.hpp -- the header the kernels
 compile -- held to it on the host (tests/dense_key_main.cpp).  No GPU."""
 import os
-import shutil
 import subprocess
 import sys
 
@@ -11,6 +10,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dense_ref as dr          # noqa: E402
 import dense_scenes as sc       # noqa: E402
+from dense_prog import BUILDS, BUILD_IDS, NONFINITE, build_prog, check_ladder          # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ID = [0, 0, 0, 0, 0, 0, 1.0]
@@ -133,18 +133,10 @@ def test_capacity_and_errors():
 
 
 # ---- the header against the statement ----------------------------------------------------------------------------------------------------
-def build_key_prog(tmp, flags):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "a C++ compiler is needed to build tests/dense_key_main.cpp"
-    exe = str(tmp / "dense_key_main")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", *flags, "-o", exe, os.path.join(ROOT, "tests", "dense_key_main.cpp")])
-    return exe
-
-
 @pytest.mark.parametrize("flags", [(), ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan")],
                          ids=["plain", "asan_ubsan"])
 def test_key_header_matches_the_statement(tmp_path, flags):
-    exe = build_key_prog(tmp_path, flags)
+    exe = build_prog(tmp_path, "dense_key_main", flags)
     assert subprocess.run([exe], capture_output=True, text=True, check=True).stdout.strip() == "dense_key ok"
     for leaf, stride, shift in ((0.05, 1, None), (0.01, 3, None), (1e-6, 1, None), (0.05, 1, sc.NEGATIVE_SHIFT)):
         s = sc.room_scene(0, shift=shift)
@@ -179,3 +171,25 @@ def test_key_header_matches_the_statement(tmp_path, flags):
             else:
                 assert got == want; n_used += 1
         assert n_used > 500 or leaf == 1e-6
+
+
+# ---- what the entries refuse for the image geometry (csrc/esl_dense_check.hpp), text by text and in order ---------------------------------
+TINY = 5e-324          # the smallest positive double: the first value above 0, its negative the first below
+
+
+@pytest.mark.parametrize("flags", BUILDS, ids=BUILD_IDS)
+def test_image_check_texts_and_order(tmp_path, flags):
+    """dense_image_check, which esl_dense_add / _remove / _move_frames, esl_dense_render, esl_dense_align_frames and esl_dense_carve_frames
+    call: every rung at its last accepted and first refused value, NaN and the infinities, and the earlier rung's text when two fail."""
+    exe = build_prog(tmp_path, "dense_key_main", flags)
+    defaults = dict(null_K=0, rows=480, cols=640, fx=525.0, fy=525.0, cx=319.5, cy=239.5)
+    rungs = [
+        ("null K", [], [dict(null_K=1)]),
+        ("rows < 1 or > 16384", [dict(rows=1), dict(rows=16384)], [dict(rows=0), dict(rows=16385), dict(rows=-1)]),
+        ("cols < 1 or > 16384", [dict(cols=1), dict(cols=16384)], [dict(cols=0), dict(cols=16385), dict(cols=-1)]),
+        ("fx not finite or <= 0", [dict(fx=TINY), dict(fx=1e308)], [dict(fx=0.0), dict(fx=-TINY)] + [dict(fx=v) for v in NONFINITE]),
+        # cx and cy are free here: esl_dense_align_frames alone asks them to be finite, in its entry
+        ("fy not finite or <= 0", [dict(fy=TINY), dict(fy=1e308)] + [dict(cx=v) for v in NONFINITE] + [dict(cy=v) for v in NONFINITE],
+         [dict(fy=0.0), dict(fy=-TINY)] + [dict(fy=v) for v in NONFINITE]),
+    ]
+    check_ladder(exe, ["null_K", "rows", "cols", "fx", "fy", "cx", "cy"], defaults, rungs)

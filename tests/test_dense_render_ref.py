@@ -2,7 +2,6 @@
 scene of tests/test_gpu_dense_render.py relies on, and csrc/esl_dense_proj.hpp held to the statement on the host (plain and under
 AddressSanitizer + UBSan, as a stand-alone program: nothing is preloaded into Python)."""
 import os
-import shutil
 import subprocess
 import sys
 
@@ -14,6 +13,7 @@ import dense_ref as dr                 # noqa: E402
 import dense_render_ref as drr         # noqa: E402
 import dense_render_scenes as rs       # noqa: E402
 import dense_scenes as sc              # noqa: E402
+from dense_prog import BUILDS, BUILD_IDS, NONFINITE, build_prog, check_ladder          # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -170,18 +170,10 @@ def test_grids():
 
 
 # ---- the header against the statement -----------------------------------------------------------------------------------------------------
-def build_prog(tmp, flags):
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "a C++ compiler is needed to build tests/dense_render_main.cpp"
-    exe = str(tmp / "dense_render_main")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", *flags, "-o", exe, os.path.join(ROOT, "tests", "dense_render_main.cpp")])
-    return exe
-
-
 @pytest.mark.parametrize("flags", [(), ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan")],
                          ids=["plain", "asan_ubsan"])
 def test_proj_header_matches_the_statement(tmp_path, flags):
-    exe = build_prog(tmp_path, flags)
+    exe = build_prog(tmp_path, "dense_render_main", flags)
     assert subprocess.run([exe], capture_output=True, text=True, check=True).stdout.strip() == "dense_proj ok"
     n_drawn = n_other = 0
     for name in ("axis", "half_pixel", "radius1", "footprint15", "depth_max", "nonfinite", "tie", "room", "overdraw", "grid257"):
@@ -206,3 +198,34 @@ def test_proj_header_matches_the_statement(tmp_path, flags):
                     want = f"{2 if pr['depth_in'][i] else 1} {int(zbits[i])} 0 0 0 0 0"; n_other += 1
                 assert got == want, (name, i)
     assert n_drawn > 5000 and n_other > 10
+
+
+# ---- what esl_dense_render refuses for its parameters (csrc/esl_dense_check.hpp), text by text and in order -------------------------------
+TINY = 5e-324          # the smallest positive double: the first value above 0, its negative the first below
+# the depth gate of esl_dense_render and esl_dense_carve_frames: the six refusals in their order, the texts as the entries have always given them
+GATE_RUNGS = [
+    ("depth_scale not finite or <= 0", [dict(depth_scale=TINY)], [dict(depth_scale=0.0), dict(depth_scale=-1.0)] + [dict(depth_scale=v) for v in NONFINITE]),
+    ("depth_min not finite or negative", [dict(depth_min=0.0)], [dict(depth_min=-TINY)] + [dict(depth_min=v) for v in NONFINITE]),
+    ("depth_max not finite or negative", [dict(depth_min=0.0, depth_max=0.0)], [dict(depth_max=-TINY)] + [dict(depth_max=v) for v in NONFINITE]),
+    ("depth_tol not finite or negative", [dict(depth_tol=0.0)], [dict(depth_tol=-TINY)] + [dict(depth_tol=v) for v in NONFINITE]),
+    ("depth_min > depth_max", [dict(depth_min=6.0)], [dict(depth_min=5000.0, depth_max=4999.0), dict(depth_min=float(np.nextafter(6.0, np.inf)))]),
+    ("depth_max > 4095", [dict(depth_max=4095.0)], [dict(depth_max=float(np.nextafter(4095.0, np.inf)))]),
+]
+
+
+@pytest.mark.parametrize("flags", BUILDS, ids=BUILD_IDS)
+def test_render_params_check_texts_and_order(tmp_path, flags):
+    """drn_params_check: every rung at its last accepted and first refused value, NaN and the infinities in every double, and the
+    earlier rung's text when two fail.  npix = rows cols: 16 for a 4 x 4 image, 2^28 for the largest."""
+    exe = build_prog(tmp_path, "dense_render_main", flags)
+    defaults = dict(drr.DEFAULTS, npix=16)
+    assert defaults["zbuf_bytes"] == 268435456 and defaults["depth_max"] == 6.0 and defaults["max_radius"] == 8
+    rungs = GATE_RUNGS + [
+        ("footprint not finite or negative", [dict(footprint=0.0)], [dict(footprint=-TINY)] + [dict(footprint=v) for v in NONFINITE]),
+        ("max_radius outside 0 .. 64", [dict(max_radius=0), dict(max_radius=64)], [dict(max_radius=-1), dict(max_radius=65)]),
+        ("min_count < 1", [dict(min_count=1)], [dict(min_count=0)]),
+        ("zbuf_bytes < 8 rows cols", [dict(zbuf_bytes=128), dict(npix=1 << 28, zbuf_bytes=1 << 31)],
+         [dict(zbuf_bytes=127), dict(npix=1 << 28, zbuf_bytes=(1 << 31) - 1), dict(zbuf_bytes=-1)]),
+    ]
+    fields = ["depth_scale", "depth_min", "depth_max", "depth_tol", "footprint", "max_radius", "min_count", "zbuf_bytes", "npix"]
+    check_ladder(exe, fields, defaults, rungs)

@@ -432,3 +432,50 @@ def test_profiling_class_4(pkg):
         assert set(prof) == {"reduce"} and prof["reduce"]["count"] >= 2 and prof["reduce"]["total_ms"] > 0
     finally:
         cx.close()
+
+
+# ---- the refusal ladder: every argument wrong at once, repaired one rung at a time, in the entry's order ----------------------------------------
+def test_add_frames_refusal_ladder(pkg):
+    """esl_dense_add_frames with every argument wrong at once: the status and the whole text of the first refusal, that argument repaired,
+    the next refusal, through the entry's sequence.  No map until "no esl_dense_begin before" has come out, then a map of one 4 x 4
+    frame; nothing is added until the last call, which adds that frame again."""
+    who = "esl_dense_add_frames"
+    good = np.array([[0, 0, 0, 0, 0, 0, 1.0]] * 8)
+    bad = good.copy(); bad[5, 3:] = 0
+    depth, bgr, inst = np.full((1, 4, 4), 5000, np.uint16), np.full((1, 4, 4, 3), 9, np.uint8), np.zeros((1, 4, 4), np.int32)
+    K = (60.0, 60.0, 1.5, 1.5)
+    one = dict(cams=good[:1], K=K, rows=4, cols=4, depth=depth, bgr=bgr, inst=inst)
+    a = dict(ctx_h=False, cams=None, F=-1, K=None, rows=0, cols=16385, depth=None, bgr=None, inst=None)          # every argument wrong
+    ladder = [          # (status, text, the repair); rows = cols = 16384 and F = 8 are valid and hold 2^31 samples
+        (2, "null ctx", dict(ctx_h=True)),
+        (2, "negative F", dict(F=8)),
+        (2, "null K", dict(K=(0.0, np.inf, 1.5, 1.5))),
+        (2, "rows < 1 or > 16384", dict(rows=16384)),
+        (2, "cols < 1 or > 16384", dict(cols=16384)),
+        (2, "fx not finite or <= 0", dict(K=(60.0, np.inf, 1.5, 1.5))),
+        (2, "fy not finite or <= 0", dict(K=K)),
+        (2, "null depth", dict(depth=depth)),
+        (4, "no esl_dense_begin before", "map"),
+        (4, "null bgr on a map begun with colour", dict(bgr=bgr)),
+        (4, "null inst on a map begun with labels", dict(inst=inst)),
+        (4, "NULL cams needs a resident graph with states", dict(cams=bad)),
+        (2, "a pose with a non-finite number or a quaternion of norm 0", dict(cams=good)),
+        (2, "n_samples would reach 2^31", dict(rows=4, cols=4, F=1)),
+    ]
+    cx = pkg.Context(0)
+    try:
+        for status, text, repair in ladder:
+            with pytest.raises(pkg.EslError) as e:
+                raw_add(pkg, cx, one, **a)
+            assert str(e.value) == f"{who} failed with esl_status {status}: {who}: {text}"
+            if repair == "map":
+                cx.dense_begin()
+                cx.dense_add_frames(**one)
+                before = cx.dense_info()
+                assert before["n_samples"] == 16 and before["status"] == 0
+            else:
+                a.update(repair)
+        assert cx.dense_info() == before          # every refused call left the map alone
+        assert raw_add(pkg, cx, one, **a)["n_used"] == 16 and cx.dense_info()["n_samples"] == 32
+    finally:
+        cx.close()

@@ -268,3 +268,73 @@ def test_resident_cameras_and_errors(pkg, refs):
             cx.dense_align_frames(c["cams"], c["K"], c["rows"], c["cols"], c["depth"])
     finally:
         cx.close()
+
+
+# ---- the refusal ladder: every argument wrong at once, repaired one rung at a time, in the entry's order ----------------------------------------
+def test_refusal_ladder(pkg):
+    """esl_dense_align_frames with every argument wrong at once: the status and the whole text of the first refusal, that argument
+    repaired, the next refusal, through the entry's sequence.  No map until "no esl_dense_begin before" has come out, then a map of
+    one 4 x 4 frame; no kernel of the entry runs until the last call."""
+    who = "esl_dense_align_frames"
+    P = pkg.abi.default_dense_align_params
+    L = pkg.lib.load()
+    good = np.array([[0, 0, 0, 0, 0, 0, 1.0]] * 8)
+    bad = good.copy(); bad[5, 3:] = 0
+    depth = np.full((1, 4, 4), 5000, np.uint16)
+    K = (60.0, 60.0, 1.5, 1.5)
+    a = dict(cx=None, out=False, cams=None, F=-1, K=None, rows=0, cols=16385, depth=None)          # every argument wrong
+    p = dict(max_dist=-1.0, damping=np.nan, min_pivot_ratio=-1e-9, tol_t=np.inf, tol_r=-1.0, iters=65, stride=0, reach=3, min_inliers=0,
+             max_curvature=-0.1, radius=3, min_count=0, min_neighbors=0)
+    ladder = [          # (status, text, the repair of an argument or (in a tuple) of a parameter); 16384 x 16384 x 8 frames hold 2^31 samples
+        (2, "null ctx", "ctx"),
+        (2, "null out", dict(out=True)),
+        (2, "negative F", dict(F=8)),
+        (2, "null K", dict(K=(0.0, np.inf, np.nan, 1.5))),
+        (2, "rows < 1 or > 16384", dict(rows=16384)),
+        (2, "cols < 1 or > 16384", dict(cols=16384)),
+        (2, "fx not finite or <= 0", dict(K=(60.0, np.inf, np.nan, 1.5))),
+        (2, "fy not finite or <= 0", dict(K=(60.0, 60.0, np.nan, 1.5))),
+        (2, "cx or cy not finite", dict(K=K)),
+        (2, "null depth", dict(depth=depth)),
+        (2, "max_dist not finite or negative", (dict(max_dist=65536.0),)),
+        (2, "damping not finite or negative", (dict(damping=0.0),)),
+        (2, "min_pivot_ratio not finite or negative", (dict(min_pivot_ratio=1e-6),)),
+        (2, "tol_t not finite or negative", (dict(tol_t=1e-5),)),
+        (2, "tol_r not finite or negative", (dict(tol_r=1e-5),)),
+        (2, "iters outside 0 .. 64", (dict(iters=64),)),
+        (2, "stride < 1", (dict(stride=1),)),
+        (2, "reach outside 0 .. 2", (dict(reach=2),)),
+        (2, "min_inliers < 1", (dict(min_inliers=1),)),
+        (2, "max_curvature not finite or negative", (dict(max_curvature=0.05),)),
+        (2, "radius outside 1 .. 2", (dict(radius=2),)),
+        (2, "min_count < 1", (dict(min_count=1),)),
+        (2, "min_neighbors < 1", (dict(min_neighbors=1),)),
+        (4, "no esl_dense_begin before", "map"),
+        (4, "NULL cams needs a resident graph with states", dict(cams=bad)),
+        (2, "a pose with a non-finite number or a quaternion of norm 0", dict(cams=good)),
+        (2, "more samples than a map holds: 2^31", dict(rows=4, cols=4, F=1)),
+        (2, "the sums of a frame could reach 2^62", (dict(max_dist=0.0),)),
+    ]
+    cx = pkg.Context(0)
+
+    def call():
+        return raw_align(pkg, a["cx"], a["cams"], a["F"], a["K"], a["rows"], a["cols"], a["depth"], p=P(**p), out=a["out"])
+    try:
+        for status, text, repair in ladder:
+            rc, _ = call()
+            assert (rc, L.esl_last_error().decode()) == (status, f"{who}: {text}")
+            if repair == "ctx":
+                a["cx"] = cx
+            elif repair == "map":
+                cx.dense_begin()
+                cx.dense_add_frames(good[:1], K, 4, 4, depth, np.full((1, 4, 4, 3), 9, np.uint8), np.zeros((1, 4, 4), np.int32))
+                before = snapshot(cx)
+            elif isinstance(repair, tuple):
+                p.update(repair[0])
+            else:
+                a.update(repair)
+        assert snapshot(cx) == before          # every refused call left the map alone
+        rc, res = call()
+        assert rc == 0 and res["status"] == 0 and res["n_voxels"] > 0 and 1 <= res["n_passes"] <= 65 and snapshot(cx) == before
+    finally:
+        cx.close()

@@ -330,3 +330,75 @@ def test_resident_cameras_and_errors(pkg):
             dev_carve(pkg, cx, sc, LATE, ALL)
     finally:
         cx.close()
+
+
+# ---- the refusal ladder: every argument wrong at once, repaired one rung at a time, in the entry's order ----------------------------------------
+def test_refusal_ladder(pkg):
+    """esl_dense_carve_frames with every argument wrong at once: the status and the whole text of the first refusal, that argument
+    repaired, the next refusal, through the entry's sequence.  No map until "no esl_dense_begin before" has come out, then a map of
+    one 4 x 4 frame; no kernel of the entry runs until the last call."""
+    who = "esl_dense_carve_frames"
+    P = pkg.abi.default_dense_carve_params
+    L = pkg.lib.load()
+    good = np.array([[0, 0, 0, 0, 0, 0, 1.0]] * 8)
+    bad = good.copy(); bad[5, 3:] = 0
+    depth, bgr, inst = np.full((1, 4, 4), 5000, np.uint16), np.full((1, 4, 4, 3), 9, np.uint8), np.zeros((1, 4, 4), np.int32)
+    K = (60.0, 60.0, 1.5, 1.5)
+    a = dict(cx=None, out=False, cams_obs=None, F_obs=-1, depth_obs=None, cams_own=None, F_own=-1, depth_own=None, bgr_own=None, inst_own=None,
+             K=None, rows=0, cols=16385, vox_cap=-1)          # every argument wrong
+    p = dict(depth_scale=0.0, depth_min=-1.0, depth_max=np.nan, depth_tol=np.nan, window=5, min_through=0, through_per_agree=-1, apply=2)
+    ladder = [          # (status, text, the repair of an argument or (in a tuple) of a parameter); 16384 x 16384 x 8 owners hold 2^31 samples
+        (2, "null ctx", "ctx"),
+        (2, "null out", dict(out=True)),
+        (2, "negative F_obs", dict(F_obs=65536)),
+        (2, "negative F_own", dict(F_own=8)),
+        (2, "null K", dict(K=(0.0, np.inf, 1.5, 1.5))),
+        (2, "rows < 1 or > 16384", dict(rows=16384)),
+        (2, "cols < 1 or > 16384", dict(cols=16384)),
+        (2, "fx not finite or <= 0", dict(K=(60.0, np.inf, 1.5, 1.5))),
+        (2, "fy not finite or <= 0", dict(K=K)),
+        (2, "negative vox_cap", dict(vox_cap=0)),
+        (2, "depth_scale not finite or <= 0", (dict(depth_scale=5000.0),)),
+        (2, "depth_min not finite or negative", (dict(depth_min=5000.0),)),
+        (2, "depth_max not finite or negative", (dict(depth_max=4096.0),)),
+        (2, "depth_tol not finite or negative", (dict(depth_tol=0.05),)),
+        (2, "depth_min > depth_max", (dict(depth_min=0.1),)),
+        (2, "depth_max > 4095", (dict(depth_max=4095.0),)),
+        (2, "window outside 0 .. 4", (dict(window=4),)),
+        (2, "min_through < 1", (dict(min_through=1),)),
+        (2, "negative through_per_agree", (dict(through_per_agree=0),)),
+        (2, "apply not 0 or 1", (dict(apply=1),)),
+        (2, "F_obs > 65535", dict(F_obs=1)),
+        (2, "null depth_obs", dict(depth_obs=depth)),
+        (2, "null cams_own", dict(cams_own=bad)),
+        (2, "null depth_own", dict(depth_own=depth)),
+        (4, "no esl_dense_begin before", "map"),
+        (4, "null bgr_own on a map begun with colour", dict(bgr_own=bgr)),
+        (4, "null inst_own on a map begun with labels", dict(inst_own=inst)),
+        (4, "NULL cams needs a resident graph with states", dict(cams_obs=bad[5:6])),
+        (2, "a pose with a non-finite number or a quaternion of norm 0", dict(cams_obs=good[:1])),
+        (2, "a pose with a non-finite number or a quaternion of norm 0", dict(cams_own=good)),
+        (2, "more samples than a map holds: 2^31", dict(rows=4, cols=4, F_own=1)),
+    ]
+    cx = pkg.Context(0)
+    try:
+        for status, text, repair in ladder:
+            rc, _ = raw_call(pkg, a["cx"], dict(a, p=P(**p)))
+            assert (rc, L.esl_last_error().decode()) == (status, f"{who}: {text}")
+            if repair == "ctx":
+                a["cx"] = cx
+            elif repair == "map":
+                cx.dense_begin()
+                cx.dense_add_frames(good[:1], K, 4, 4, depth, bgr, inst)
+                before = cx.dense_info()
+                assert before["n_samples"] == 16 and before["status"] == 0
+            elif isinstance(repair, tuple):
+                p.update(repair[0])
+            else:
+                a.update(repair)
+        assert cx.dense_info() == before          # every refused call left the map alone
+        rc, res = raw_call(pkg, a["cx"], dict(a, p=P(**p)))
+        # the one observer agrees with what the one owner added: nothing is carved, the removal of step C6 takes no sample
+        assert rc == 0 and res["status"] == 0 and res["n_voxels"] > 0 and res["n_carved"] == 0 and cx.dense_info() == before
+    finally:
+        cx.close()

@@ -250,3 +250,68 @@ def test_resident_cameras_and_errors(pkg):
             cx.dense_render(fr["cams"], fr["K"], 48, 64, want=("frame",))
     finally:
         cx.close()
+
+
+# ---- the refusal ladder: every argument wrong at once, repaired one rung at a time, in the entry's order ----------------------------------------
+def test_refusal_ladder(pkg):
+    """esl_dense_render with every argument wrong at once: the status and the whole text of the first refusal, that argument repaired,
+    the next refusal, through the entry's sequence.  No map until "no esl_dense_begin before" has come out, then a map of one 4 x 4
+    frame; no kernel of the entry runs until the last call."""
+    who = "esl_dense_render"
+    P = pkg.abi.default_dense_render_params
+    L = pkg.lib.load()
+    good = np.array([[0, 0, 0, 0, 0, 0, 1.0]])
+    K = (60.0, 60.0, 1.5, 1.5)
+    vox = np.full((4, 4), 77, np.int32)
+    a = dict(cx=None, out=False, cams=None, F=-1, K=None, rows=0, cols=16385, vox_cap=-1, bufs={})          # every argument wrong
+    p = dict(depth_scale=0.0, depth_min=-1.0, depth_max=np.nan, depth_tol=np.nan, footprint=-0.5, max_radius=65, min_count=0, zbuf_bytes=127)
+    ladder = [          # (status, text, the repair of an argument or (in a tuple) of a parameter)
+        (2, "null ctx", "ctx"),
+        (2, "null out", dict(out=True)),
+        (2, "negative F", dict(F=1)),
+        (2, "null K", dict(K=(0.0, np.inf, 1.5, 1.5))),
+        (2, "rows < 1 or > 16384", dict(rows=4)),
+        (2, "cols < 1 or > 16384", dict(cols=4)),
+        (2, "fx not finite or <= 0", dict(K=(60.0, np.inf, 1.5, 1.5))),
+        (2, "fy not finite or <= 0", dict(K=K)),
+        (2, "negative vox_cap", dict(vox_cap=4)),
+        (2, "null vox_out with vox_cap > 0", dict(bufs=dict(vox=vox))),
+        (2, "depth_scale not finite or <= 0", (dict(depth_scale=5000.0),)),
+        (2, "depth_min not finite or negative", (dict(depth_min=5000.0),)),
+        (2, "depth_max not finite or negative", (dict(depth_max=4096.0),)),
+        (2, "depth_tol not finite or negative", (dict(depth_tol=0.05),)),
+        (2, "depth_min > depth_max", (dict(depth_min=0.1),)),
+        (2, "depth_max > 4095", (dict(depth_max=4095.0),)),
+        (2, "footprint not finite or negative", (dict(footprint=1.0),)),
+        (2, "max_radius outside 0 .. 64", (dict(max_radius=64),)),
+        (2, "min_count < 1", (dict(min_count=1),)),
+        (2, "zbuf_bytes < 8 rows cols", (dict(zbuf_bytes=128),)),
+        (4, "no esl_dense_begin before", "map"),
+        (4, "NULL cams needs a resident graph with states", dict(cams=np.zeros((1, 7)))),
+        (2, "a pose with a non-finite number or a quaternion of norm 0", dict(cams=good)),
+    ]
+    cx = pkg.Context(0)
+
+    def call():
+        return raw_call(pkg, a["cx"], a["cams"], a["F"], a["K"], a["rows"], a["cols"], p=P(**p), bufs=a["bufs"], vox_cap=a["vox_cap"], out=a["out"])
+    try:
+        for status, text, repair in ladder:
+            rc, _ = call()
+            assert (rc, L.esl_last_error().decode()) == (status, f"{who}: {text}")
+            if repair == "ctx":
+                a["cx"] = cx
+            elif repair == "map":
+                cx.dense_begin()
+                cx.dense_add_frames(good, K, 4, 4, np.full((1, 4, 4), 5000, np.uint16), np.full((1, 4, 4, 3), 9, np.uint8), np.zeros((1, 4, 4), np.int32))
+                before = cx.dense_info()
+                assert before["n_samples"] == 16 and before["status"] == 0
+            elif isinstance(repair, tuple):
+                p.update(repair[0])
+            else:
+                a.update(repair)
+        assert (vox == 77).all() and cx.dense_info() == before          # every refused call wrote nothing
+        rc, res = call()
+        assert rc == 0 and res["status"] == 0 and res["n_voxels"] == cx.dense_extract(want=("key",))["n_voxels"] > 0 and res["n_chunks"] == 1
+        assert (vox != 77).all()
+    finally:
+        cx.close()
