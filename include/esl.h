@@ -58,7 +58,8 @@ extern "C" {
                              *    its exact de-integration (esl_dense_remove_frames / _move_frames / _purge / _slots_get), and its
                              *    view from any pose, checked against measured depth (esl_dense_render), and its per-voxel normals
                              *    (esl_dense_normals) and the poses refined against it (esl_dense_align_frames), and the carving of the
-                             *    voxels that later frames see through (esl_dense_carve_frames) */
+                             *    voxels that later frames see through (esl_dense_carve_frames), and the covisibility of the frames
+                             *    through it with their redundancy (esl_dense_covis_frames) */
 #define ESL_MAX_TRACE 32
 
 typedef enum {
@@ -1402,6 +1403,74 @@ int esl_dense_carve_frames(esl_ctx* ctx,
                            uint8_t* mask_out /* F_own x rows x cols or NULL: 1 = carved sample */,
                            int32_t* own_out /* F_own x 4 or NULL: used, found, carved, not found */,
                            esl_dense_carve_result* out);
+
+/* ---- covisibility of the dense map: which frames see the same voxels, which frames are redundant (additive part of ABI 5: detect by
+ * the symbol) -----------------------------------------------------------------------------------------------------------------------------
+ * Frames a and b are covisible in the voxels of the map that both of them see, and "sees" is the class agree of step C2 of the carving.
+ * esl_dense_covis_frames gives, for F frames with their measured depth: per voxel the number of frames that see it, per pair of frames
+ * the number of voxels both see (the covisibility graph's weights: candidates for loop-closure edges, observers and owners of a
+ * carving), and the keyframe-culling rule of feature-based SLAM on the map's voxels: a frame is redundant when a given fraction of
+ * what it sees is seen by at least min_others other frames; redundant frames leave one by one, the counts following.  The call reads the
+ * map as esl_dense_carve_frames with apply = 0 does.  Everything is integers after step V2; every choice is a comparison and every sum
+ * an integer sum, so runs are bit-reproducible and a permutation of the frames permutes the outputs.
+ *  V1. Voxels.  As step C1: the live voxels in ascending packed-key order, index i, xyz as esl_dense_extract gives them.
+ *  V2. Sees.  Frame f sees voxel i iff step C2 of the carving gives the class agree, with this call's depth_scale, depth_min, depth_max,
+ *      depth_tol and window.  Poses are validated and turned into R, t on the host as dense-map step 2 does.
+ *  V3. Counts.  vox_out[i] = k_i, the number of frames that see voxel i.  frame_out[8 f ..] = in view, depth out, outside, seen,
+ *      covered, unique, cull round, 0 of frame f: seen_f = the voxels f sees, unique_f = those of them with k_i = 1, the first three
+ *      as in obs_out of the carving.
+ *  V4. Pairs.  pair_out[a F + b] = the number of voxels that a and b both see, as int32: symmetric, its diagonal is seen_a.
+ *  V5. Covered and redundant.  A voxel that f sees is covered without f iff k_i - 1 >= min_others; covered_f counts such voxels among
+ *      the voxels f sees.  f is redundant iff seen_f >= 1 and covered_f cover_den >= cover_num seen_f, both products as 64-bit integers.
+ *  V6. Cull rounds r = 0 .. max_cull - 1; the alive frames start as all frames.  k_i^r counts alive frames only and covered_f^r
+ *      follows from k_i^r as in V5.  The candidates are the alive frames with keep_in[f] == 0 that are redundant under k^r (a protected
+ *      frame still counts as an observer).  The candidate with the smallest seen_f - covered_f^r, ties to the lowest f, leaves the alive
+ *      set: its cull round is r.  The rounds stop when there is no candidate; a frame never culled has round -1.  frame_out's covered
+ *      column and vox_out are the values of round 0; pair_out always covers all F frames.  n_culled = the rounds done; with
+ *      max_cull = 0 nothing is culled.
+ *  V7. Map status.  As C7: on a map whose status is not 0 the call returns ESL_OK, sets that status and n_voxels = -1 and writes
+ *      nothing else.
+ * Limits: F <= 4096 (pair_out is at most 64 MiB); window <= 4; rows, cols <= 16384; every count is an int32.  Not part of this call:
+ * emitting graph edges, aligning or removing frames on the result, weights other than voxel counts, bits kept on the device between
+ * calls, more than one GPU. */
+typedef struct {
+  double  depth_scale;        /* 5000: raw units per metre of depth; finite, > 0 */
+  double  depth_min;          /* 0.1: the gate of a voxel's z and of a measured sample (step C2); finite, >= 0 */
+  double  depth_max;          /* 6.0: finite, >= depth_min, <= 4095 */
+  double  depth_tol;          /* 0.05 m: |z_meas - z| <= depth_tol agrees; finite, >= 0 */
+  int32_t window;             /* 1: the pixels read around the centre pixel reach this far; 0 .. 4 */
+  int32_t min_others;         /* 3: a voxel is covered without f when this many other frames see it; >= 1 */
+  int32_t cover_num;          /* 9: f is redundant when covered_f / seen_f >= cover_num / cover_den; 0 .. cover_den */
+  int32_t cover_den;          /* 10: 1 .. 2^20 */
+  int32_t max_cull;           /* 0: the cull rounds of step V6 at most; >= 0 */
+  int32_t reserved;           /* 0 */
+} esl_dense_covis_params;   /* 56 bytes; design choices, not values tuned on real data */
+void esl_dense_covis_params_default(esl_dense_covis_params* p);
+
+typedef struct {
+  int32_t status, n_voxels, n_seen, n_culled;   /* n_seen: the voxels with k_i >= 1 */
+  int64_t sum_seen;                             /* the sum of seen_f over the frames = the sum of k_i over the voxels */
+  int64_t sum_pairs;                            /* the sum of pair[a][b] over a < b = the sum of k_i (k_i - 1) / 2 over the voxels,
+                                                 * which is how it is formed: it is there without pair_out too */
+} esl_dense_covis_result;   /* 32 bytes */
+
+/* Errors follow esl_dense_carve_frames, case by case and in this order.  ESL_ERR_INVALID: null ctx or out; negative F; null K; rows or
+ * cols < 1 or > 16384; fx or fy not finite or <= 0; negative vox_cap; depth_scale not finite or <= 0; depth_min, depth_max or depth_tol
+ * not finite or negative; depth_min > depth_max; depth_max > 4095; window outside 0 .. 4; min_others < 1; cover_den outside 1 .. 2^20;
+ * cover_num outside 0 .. cover_den; negative max_cull; reserved not 0; F > 4096; null depth with F > 0.  ESL_ERR_STATE: no
+ * esl_dense_begin before; cams == NULL without a resident graph and states.  ESL_ERR_INVALID again: F differing from the resident
+ * graph's n_cams when cams == NULL; an invalid pose.  A refused call changes nothing.  F = 0 and an empty map are valid; any output but
+ * `out` may be NULL (vox_out receives the first min(vox_cap, n_voxels) values; without pair_out the pair counts are not formed).  Its
+ * buffers are a set of its own beside the dense map's (grow-only; a warm call of the same shape allocates nothing:
+ * esl_debug_dense_allocs counts them; 2 bytes per pixel, 8 F ceil(n / 64) for the bits, 28 per voxel and a quarter more for two
+ * masks, 4 F F with pair_out, 136 per frame).  Per cull round the host reads back F int32 and launches two kernels.  One GPU, no
+ * collective, launches bracketed as kernel class 4. */
+int esl_dense_covis_frames(esl_ctx* ctx, const double* cams /* F x 7 Tcw; NULL = resident camera states */, int32_t F,
+                           const uint16_t* depth /* F x rows x cols */, const uint8_t* keep_in /* F or NULL: != 0 protects a frame */,
+                           const double K[4], int32_t rows, int32_t cols, const esl_dense_covis_params* p /* NULL = defaults */,
+                           int64_t vox_cap, int32_t* vox_out /* vox_cap or NULL: k_i */,
+                           int32_t* frame_out /* F x 8 or NULL: in view, depth out, outside, seen, covered, unique, cull round, 0 */,
+                           int32_t* pair_out /* F x F or NULL */, esl_dense_covis_result* out);
 
 /* ---- diagnostics ---------------------------------------------------------------------------------*/
 /* Dense FP64-MFMA Cholesky factor + solve (the reduced-camera solver of SLAM mode) on a procedurally generated,

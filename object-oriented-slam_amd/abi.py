@@ -487,10 +487,49 @@ def default_dense_carve_params(**kw):
     return p
 
 
+class EslDenseCovisParams(C.Structure):
+    """esl_dense_covis_params: the carving's depth gates and window, the redundancy rule (min_others, cover_num / cover_den) and the
+    cull rounds at most."""
+    _fields_ = [("depth_scale", C.c_double), ("depth_min", C.c_double), ("depth_max", C.c_double), ("depth_tol", C.c_double),
+                ("window", C.c_int32), ("min_others", C.c_int32), ("cover_num", C.c_int32), ("cover_den", C.c_int32),
+                ("max_cull", C.c_int32), ("reserved", C.c_int32)]
+
+
+class EslDenseCovisResult(C.Structure):
+    """esl_dense_covis_result: status 3 / 4 = an invalid map (n_voxels = -1); the voxels some frame sees, the frames culled, the sums of
+    seen_f over the frames and of the pair counts over a < b."""
+    _fields_ = [("status", C.c_int32), ("n_voxels", C.c_int32), ("n_seen", C.c_int32), ("n_culled", C.c_int32),
+                ("sum_seen", C.c_int64), ("sum_pairs", C.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert C.sizeof(EslDenseCovisParams) == 56 and C.sizeof(EslDenseCovisResult) == 32
+
+DENSE_COVIS_DEFAULTS = dict(depth_scale=5000.0, depth_min=0.1, depth_max=6.0, depth_tol=0.05, window=1, min_others=3, cover_num=9, cover_den=10,
+                            max_cull=0, reserved=0)
+
+
+def default_dense_covis_params(**kw):
+    """esl_dense_covis_params_default: design choices, not values tuned on real data (include/esl.h)"""
+    p = EslDenseCovisParams(**DENSE_COVIS_DEFAULTS)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
 def dense_argtypes(L):
     """the esl_dense_* calls take nullable pointers: declared, so that None passes as NULL and a wrong type raises"""
     dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
     up, bp = C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)
+    L.esl_dense_covis_params_default.argtypes = [C.POINTER(EslDenseCovisParams)]
+    L.esl_dense_covis_params_default.restype = None
+    L.esl_dense_covis_frames.argtypes = [C.c_void_p, dp, C.c_int32, up, bp, dp, C.c_int32, C.c_int32, C.POINTER(EslDenseCovisParams), C.c_int64,
+                                         ip, ip, ip, C.POINTER(EslDenseCovisResult)]
+    L.esl_dense_covis_frames.restype = C.c_int
     L.esl_dense_carve_params_default.argtypes = [C.POINTER(EslDenseCarveParams)]
     L.esl_dense_carve_params_default.restype = None
     L.esl_dense_carve_frames.argtypes = [C.c_void_p, dp, C.c_int32, up, dp, C.c_int32, up, bp, ip, dp, C.c_int32, C.c_int32,

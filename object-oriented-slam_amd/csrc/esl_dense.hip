@@ -348,12 +348,12 @@ static __global__ __launch_bounds__(kDenseThreads) void k_dense_gather(DenseOutA
 void dense_scratch_stats(const esl_ctx* c, int64_t* allocs, int64_t* bytes) {
   if (!c->dense) return;
   const DenseState& d = *c->dense;
-  *allocs = d.set.allocs() + d.obj_set.allocs() + d.pl_set.allocs() + d.rn_set.allocs() + d.al_set.allocs() + d.cv_set.allocs();
-  *bytes = (int64_t)(d.set.held() + d.obj_set.held() + d.pl_set.held() + d.rn_set.held() + d.al_set.held() + d.cv_set.held());
+  *allocs = d.set.allocs() + d.obj_set.allocs() + d.pl_set.allocs() + d.rn_set.allocs() + d.al_set.allocs() + d.cv_set.allocs() + d.co_set.allocs();
+  *bytes = (int64_t)(d.set.held() + d.obj_set.held() + d.pl_set.held() + d.rn_set.held() + d.al_set.held() + d.cv_set.held() + d.co_set.held());
 }
 
 void dense_release(esl_ctx* c) {   // called by esl_ctx_destroy
-  if (c->dense) { c->dense->set.release(); c->dense->obj_set.release(); c->dense->pl_set.release(); c->dense->rn_set.release(); c->dense->al_set.release(); c->dense->cv_set.release(); }
+  if (c->dense) { c->dense->set.release(); c->dense->obj_set.release(); c->dense->pl_set.release(); c->dense->rn_set.release(); c->dense->al_set.release(); c->dense->cv_set.release(); c->dense->co_set.release(); }
   delete c->dense;
   c->dense = nullptr;
 }

@@ -1,6 +1,6 @@
 // esl_dense_check.hpp — what the entries that read the dense map refuse for a parameter's value alone, stated once: the image geometry
-// (esl_dense_add / _remove / _move_frames, esl_dense_render, esl_dense_align_frames, esl_dense_carve_frames), the depth gate (render and
-// carve) and one function per parameter struct.  Every function gives the text of the first refusal in the order the entry keeps, or
+// (esl_dense_add / _remove / _move_frames, esl_dense_render, esl_dense_align_frames, esl_dense_carve_frames, esl_dense_covis_frames), the
+// depth gate (render, carve and covis) and one function per parameter struct.  Every function gives the text of the first refusal in the order the entry keeps, or
 // nullptr; the entry does  if (const char* m = ...) return dense_fail(ESL_ERR_INVALID, who, m);  What needs the context, the map's state
 // or the caller's pointers stays in the entry.  Plain C++ for the host, no HIP include: tests/dense_*_main.cpp run these functions
 // with an ordinary compiler (mode "check").
@@ -12,6 +12,7 @@
 #include "../../include/esl.h"
 #include "esl_dense_align.hpp"
 #include "esl_dense_carve.hpp"
+#include "esl_dense_covis.hpp"
 #include "esl_dense_key.hpp"
 #include "esl_dense_proj.hpp"
 
@@ -56,6 +57,17 @@ inline const char* dcv_params_check(const esl_dense_carve_params& p) {
   if (p.min_through < 1) return "min_through < 1";
   if (p.through_per_agree < 0) return "negative through_per_agree";
   if (p.apply != 0 && p.apply != 1) return "apply not 0 or 1";
+  return nullptr;
+}
+
+inline const char* dco_params_check(const esl_dense_covis_params& p) {
+  if (const char* m = dense_gate_check(p.depth_scale, p.depth_min, p.depth_max, p.depth_tol)) return m;
+  if (p.window < 0 || p.window > kDcvMaxWindow) return "window outside 0 .. 4";
+  if (p.min_others < 1) return "min_others < 1";
+  if (p.cover_den < 1 || p.cover_den > kDcoMaxCoverDen) return "cover_den outside 1 .. 2^20";
+  if (p.cover_num < 0 || p.cover_num > p.cover_den) return "cover_num outside 0 .. cover_den";
+  if (p.max_cull < 0) return "negative max_cull";
+  if (p.reserved != 0) return "reserved not 0";
   return nullptr;
 }
 

@@ -1,11 +1,12 @@
-// esl_dense_int.hpp — what the six units of the dense map share: esl_dense.hip (the map), esl_dense_objects.hip and
+// esl_dense_int.hpp — what the seven units of the dense map share: esl_dense.hip (the map), esl_dense_objects.hip and
 // esl_dense_planes.hip (the two extractors that read it), esl_dense_render.hip (the view of it), esl_dense_align.hip (its normals
-// and the poses refined against it) and esl_dense_carve.hip (the voxels that later frames see through).  The record and the counters,
+// and the poses refined against it), esl_dense_carve.hip (the voxels that later frames see through) and esl_dense_covis.hip (the
+// frames' covisibility through it).  The record and the counters,
 // the map's state and its buffers, the probes of the voxel table, the sorted list of the live voxels as one step (DenseList,
 // dense_list_begin / _launch: defined in esl_dense.hip, whose kernels they launch), the growth of a unit's own buffers from a table
 // (DenseSlot, dense_grow) and the entries' small helpers (dense_fail, dense_begun, dense_map_invalid).  What an entry refuses for a
-// parameter's value alone is esl_dense_check.hpp's.  Internal: only those six units include it.
-// The rule of all six: every store to global memory is a vector store or an atomic in plain C++; no loop waits for another thread: a
+// parameter's value alone is esl_dense_check.hpp's.  Internal: only those seven units include it.
+// The rule of all seven: every store to global memory is a vector store or an atomic in plain C++; no loop waits for another thread: a
 // probe that finds no slot within the table's size, or a map over its capacity, raises the sticky status 3 and gives up.
 #pragma once
 #include <algorithm>
@@ -40,6 +41,8 @@ static_assert(sizeof(esl_dense_align_frame) == 384, "include/esl.h states this s
 static_assert(sizeof(esl_dense_align_result) == 16, "include/esl.h states this size");
 static_assert(sizeof(esl_dense_carve_params) == 48, "include/esl.h states this size");
 static_assert(sizeof(esl_dense_carve_result) == 96, "include/esl.h states this size");
+static_assert(sizeof(esl_dense_covis_params) == 56, "include/esl.h states this size");
+static_assert(sizeof(esl_dense_covis_result) == 32, "include/esl.h states this size");
 
 constexpr int kDenseThreads = 256;
 typedef unsigned long long u64;
@@ -57,7 +60,7 @@ enum { DC_SAMPLED, DC_ZERO, DC_DEPTH_OUT, DC_KEY_OUT, DC_USED, DC_VOXELS, DC_PAI
 // pose set and esl_dense_purge's live records and pairs.  Each extractor keeps a set of its own, its slots named in its unit.
 enum { DB_KEYS, DB_REC, DB_PKEYS, DB_PCNT, DB_CTR, DB_POSE, DB_DEPTH, DB_BGR, DB_INST, DB_LKEY, DB_LVAL, DB_SKEY, DB_SVAL, DB_TEMP,
        DB_OKEY, DB_OXYZ, DB_OCNT, DB_OBGR, DB_OINST, DB_OVOTES, DB_POSE2, DB_XKEY, DB_XREC, DB_XPKEY, DB_XPID, DB_XPCNT, DB_COUNT };
-constexpr int kDobjBufs = 17, kDplBufs = 12, kDrnBufs = 14, kDalBufs = 11, kDcvBufs = 14;   // the lengths of the other units' own enums (asserted there)
+constexpr int kDobjBufs = 17, kDplBufs = 12, kDrnBufs = 14, kDalBufs = 11, kDcvBufs = 14, kDcoBufs = 12;   // the lengths of the other units' own enums (asserted there)
 struct DenseState {
   ScratchSet<DB_COUNT> set;
   ScratchSet<kDobjBufs> obj_set;   // esl_dense_objects
@@ -65,6 +68,7 @@ struct DenseState {
   ScratchSet<kDrnBufs> rn_set;     // esl_dense_render
   ScratchSet<kDalBufs> al_set;     // esl_dense_normals, esl_dense_align_frames
   ScratchSet<kDcvBufs> cv_set;     // esl_dense_carve_frames
+  ScratchSet<kDcoBufs> co_set;     // esl_dense_covis_frames
   bool begun = false, combine = true;
   esl_dense_params p;
   int with_color = 0, with_inst = 0;
@@ -144,7 +148,7 @@ struct DenseOutArgs {
   int* okey; double* oxyz; int* ocnt; unsigned char* obgr; int* oinst; int* ovotes;   // null: not asked for
 };
 
-// The map's voxels as a list of (packed key, slot) in ascending key order, shared by esl_dense_extract and the five units that read
+// The map's voxels as a list of (packed key, slot) in ascending key order, shared by esl_dense_extract and the six units that read
 // the map.  A call's step: dense_list_begin, the caller's own buffers and the outputs it wants in L.k, dense_list_launch.
 struct DenseList { DenseOutArgs k; size_t temp_bytes; };   // the kernels' arguments and the sort's temporary storage
 // the list's buffers grown, the table pointers of L.k set (the rest zero), ctr[DC_LIST] cleared on the stream: outside every ProfScope

@@ -36,6 +36,7 @@ EXPORTS = [
     "esl_dense_render_params_default", "esl_dense_render",
     "esl_dense_normal_params_default", "esl_dense_normals", "esl_dense_align_params_default", "esl_dense_align_frames",
     "esl_dense_carve_params_default", "esl_dense_carve_frames",
+    "esl_dense_covis_params_default", "esl_dense_covis_frames",
 ]
 
 
@@ -1110,6 +1111,64 @@ class Context:
         for k in ("vox", "carved"):
             if k in out:
                 out[k] = out[k][:m]
+        return out
+
+    DENSE_COVIS_OUTPUTS = ("vox", "frame", "pair")
+
+    def dense_covis_frames(self, cams, depth, K, rows, cols, keep=None, params=None, want=DENSE_COVIS_OUTPUTS, vox_cap=None):
+        """esl_dense_covis_frames: which voxels of the dense map does each frame see, how many do two frames share, which frames are
+        redundant.  cams (F, 7) Tcw or None for the resident camera states, depth (F, rows, cols) uint16, keep (F,) non-zero = never
+        culled, or None; want names the outputs to compute; vox_cap None = room for every voxel.  Returns a dict: result (status,
+        n_voxels, n_seen, n_culled, sum_seen, sum_pairs) and, per name of want, vox (min(vox_cap, n_voxels),) int32 k_i, frame (F, 8)
+        int32 in view / depth out / outside / seen / covered / unique / cull round / 0, pair (F, F) int32; on an invalid map (result
+        n_voxels = -1) the arrays are as they were allocated and vox is empty."""
+        p = params if params is not None else abi.default_dense_covis_params()
+        want = set(want)
+        unknown = want - set(self.DENSE_COVIS_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        _ip, _up, _bp = C.POINTER(C.c_int32), C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)
+        rows, cols = int(rows), int(cols)
+        if cams is None:
+            F, cp = self.graph_sizes()["n_cams"], None
+        else:
+            cams = np.ascontiguousarray(cams, dtype=np.float64).reshape(-1, 7)
+            F, cp = len(cams), (cams.ctypes.data_as(_dp) if len(cams) else None)
+        depth = np.ascontiguousarray(depth, dtype=np.uint16)
+        if depth.shape != (F, rows, cols):
+            raise ValueError(f"depth has shape {depth.shape}, expected {(F, rows, cols)}")
+        kp = None
+        if keep is not None:
+            keep = np.ascontiguousarray(keep, dtype=np.uint8).reshape(-1)
+            if len(keep) != F:
+                raise ValueError(f"keep has {len(keep)} entries, expected {F}")
+            kp = keep.ctypes.data_as(_bp)
+        Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(4)
+        if "vox" in want:
+            if vox_cap is None:
+                vox_cap = max(self.dense_info()["n_voxels"], 0) if self._dense_begun() else 0
+            vox_cap = int(vox_cap)
+        else:
+            vox_cap = 0
+        out = {}
+        if "vox" in want:
+            out["vox"] = np.zeros(max(vox_cap, 0), dtype=np.int32)
+        if "frame" in want:
+            out["frame"] = np.zeros((F, 8), dtype=np.int32)
+        if "pair" in want:
+            out["pair"] = np.zeros((F, F), dtype=np.int32)
+
+        def optr(k):
+            return out[k].ctypes.data_as(_ip) if k in out and out[k].size else None
+        res = abi.EslDenseCovisResult()
+        t0 = time.perf_counter()
+        rc = load().esl_dense_covis_frames(self._h, cp, F, depth.ctypes.data_as(_up), kp, Kc.ctypes.data_as(_dp), rows, cols, C.byref(p), vox_cap,
+                                           optr("vox"), optr("frame"), optr("pair"), C.byref(res))
+        self.last_call_s = time.perf_counter() - t0      # the C-ABI call alone
+        _check(rc, "esl_dense_covis_frames")
+        out["result"] = res.as_dict()
+        if "vox" in out:
+            out["vox"] = out["vox"][:min(vox_cap, max(res.n_voxels, 0))]
         return out
 
     def _dense_begun(self):
